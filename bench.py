@@ -38,6 +38,38 @@ from benchlib.cpu import config1_cpu, cpu_baseline  # noqa: E402,F401
 from benchlib.ranks import emulate_world, launch_ranks  # noqa: E402,F401
 from benchlib.stages import bell_stage, config5_stage, conv_path_stage, conv_step_stage, extras  # noqa: E402,F401
 
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: what all ranks together write, at most
+
+
+def dump_sample_index(numel, cap, unit):
+    """Which elements of a unit's C --dump-outputs writes: all of them when they fit in `cap`, else `cap` of them, drawn without
+    replacement by a generator seeded with the unit (layer, batch begin, batch end) and sorted: the same for every build and run."""
+    import numpy as np
+    if numel <= cap:
+        return None
+    return np.sort(np.random.default_rng([0x5EED, *unit]).choice(numel, cap, replace=False))
+
+
+def dump_outputs(out_dir, layers, world):
+    """C of every unit of this rank, as float32, one DIR/C_layer<i>_b<lo>-<hi>.npy per unit; each unit gets an equal share of
+    DUMP_MAX_BYTES / world.  Returns what was written."""
+    import numpy as np
+    import torch
+    units = {}
+    for L in layers:
+        units.setdefault(L["unit"], L["C_unit"])
+    cap = DUMP_MAX_BYTES // 4 // (len(units) * world)
+    os.makedirs(out_dir, exist_ok=True)
+    nbytes, sampled = 0, 0
+    for unit, C in sorted(units.items()):
+        idx = dump_sample_index(C.numel(), cap, unit)
+        x = C if idx is None else C[torch.from_numpy(idx).to(C.device)]
+        a = x.float().cpu().numpy()
+        np.save(os.path.join(out_dir, "C_layer%03d_b%d-%d.npy" % unit), a)
+        nbytes += a.nbytes
+        sampled += idx is not None
+    return {"dir": out_dir, "arrays": len(units), "sampled": sampled, "elements_per_sampled_array": cap, "bytes": nbytes, "dtype": "float32"}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -132,9 +164,18 @@ def main():
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="multi-rank rehearsal on a ONE-GPU box: gloo backend, every rank on cuda:0 (control flow only; "
                          "the ranks share the device, so the numbers mean nothing)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed -- the C of every (layer, batch range) unit of "
+                         "this rank -- as float32 to DIR/C_layer<i>_b<lo>-<hi>.npy, at most 60 MiB in all: a C larger than its share is "
+                         "written as a fixed, seeded sample of its elements (dump_sample_index).  The inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
+    if args.dump_outputs and args.emulate_world:
+        raise SystemExit("bench: --dump-outputs is not supported with --emulate-world")
     if args.emulate_world and args.emu_rank is None:
         raise SystemExit(emulate_world(args))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -232,7 +273,7 @@ def main():
             C = torch.empty(b * m * n, dtype=tdt, device=dev)
             S = args.batch_split if args.batch_split > 1 and b % args.batch_split == 0 else 1
             if S == 1:
-                layers.append(dict(li=li, m=m, n=n, k=k, b=b, A=A, B=B, blob=blob, C=C))
+                layers.append(dict(li=li, m=m, n=n, k=k, b=b, A=A, B=B, blob=blob, C=C, unit=(li, lo, hi), C_unit=C))
             else:
                 # --batch-split S: the layer's batch as S independent problems of b / S batch entries (views of the same operands; own
                 # blobs): more, smaller work items for the streams to interleave -- same kernels, same C
@@ -240,7 +281,7 @@ def main():
                 for s_ in range(S):
                     layers.append(dict(li=li, m=m, n=n, k=k, b=bs, A=A[s_ * bs * m * k:(s_ + 1) * bs * m * k], B=B,
                                        blob=torch.empty(sm.compress24_size(m, k, es, bs), dtype=torch.uint8, device=dev),
-                                       C=C[s_ * bs * m * n:(s_ + 1) * bs * m * n]))
+                                       C=C[s_ * bs * m * n:(s_ + 1) * bs * m * n], unit=(li, lo, hi), C_unit=C))
         return layers
     layers = build_layers(shapes, units)
     flops = mg.unit_flops(shapes, units)
@@ -528,6 +569,8 @@ def main():
     tot_flops, wall_max = mg.rollup(flops * args.steps, wall, None if args.rehearse_gloo else dev)
     ms_per_step = wall_max / args.steps * 1e3
     value = tot_flops / wall_max / 1e9
+    # --dump-outputs: the C buffers as the last timed step left them, before any later pass (verification, stages) touches them
+    dumped = dump_outputs(args.dump_outputs, layers, world) if args.dump_outputs else None
 
     # BASELINE config 4 in the same run (every rank takes part: the timed loop is bracketed by collectives): the three ResNet tables
     # as 300 whole layers placed by LPT, launched like the step (grouped, over the streams).  north_star's ">= 7x aggregate at 8 GPUs"
@@ -658,6 +701,8 @@ def main():
         out.setdefault("stages", {})["config4_sweep"] = config4
     if args.emu_rank is not None:
         out["emulated"] = {"world": plan_world, "rank": plan_rank, "units": len(units), "dense_equiv_gflop_per_step": flops / 1e9}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0 and not args.no_extras:
         extras(args, sm, torch, dev, layers, flops, wall / args.steps, Forked, make_runner, timed, event_seconds, use_fused, out,
                (fused_groups, run_group, spread, ForkedItems, sk_takes) if grouped else None, step_full)

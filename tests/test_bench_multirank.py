@@ -49,6 +49,46 @@ def test_bench_prints_one_small_contract_line_and_writes_the_detail_file(tmp_pat
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_hold_the_timed_steps_c(gpu, tmp_path):
+    """--dump-outputs DIR: after the K timed steps (the line's `steps`) one float32 file per layer, at most 64 MB in all; a layer's file
+    holds its C at the seeded sample positions, bit for bit the C of compress + spmma recomputed here on the same seeded operands."""
+    import csv
+
+    import numpy as np
+    import torch
+    import bench
+    import __graft_entry__ as ge
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--settle-ms", "0", "--no-extras",
+                          "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(tmp_path / "dump")],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.splitlines()[-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["verified"] is True
+    files = sorted((tmp_path / "dump").iterdir())
+    assert len(files) == 49 and all(f.suffix == ".npy" for f in files) and sum(f.stat().st_size for f in files) <= 64e6
+    got = {f.name: np.load(f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    with open(os.path.join(ROOT, "datasets", "resnet50.csv"), newline="") as fh:
+        shapes = [tuple(int(x) for x in r[:4]) for r in list(csv.reader(fh))[1:] if r]
+    mg = ge.load_package_module("multigpu")
+    cap = bench.DUMP_MAX_BYTES // 4 // len(shapes)
+    for li in (0, len(shapes) - 1):   # the stem layer (ragged k) and the last one
+        m, n, k, b = shapes[li]
+        A = torch.empty(b * m * k, dtype=torch.float16, device="cuda")
+        B = torch.empty(k * n, dtype=torch.float16, device="cuda")
+        for bi in range(b):
+            gpu.fill_uniform(A[bi * m * k:(bi + 1) * m * k], mg.unit_seed(0x5EED0000, li, bi), 0.0, 1.0)
+        gpu.fill_uniform(B, mg.unit_seed(0xB0000000, li, -1), 0.0, 1.0)
+        blob = torch.empty(gpu.compress24_size(m, k, 2, b), dtype=torch.uint8, device="cuda")
+        C = torch.empty(b * m * n, dtype=torch.float16, device="cuda")
+        gpu.compress24(A, m, k, k, b, m * k, blob)
+        gpu.spmma(blob, B, C, m, n, k, b, 0)
+        idx = bench.dump_sample_index(C.numel(), cap, (li, 0, b))
+        want = (C if idx is None else C[torch.from_numpy(idx).to(C.device)]).float().cpu().numpy()
+        assert np.array_equal(got["C_layer%03d_b0-%d.npy" % (li, b)], want), li
+
+
+@pytest.mark.gpu
 def test_bench_gpus2_starts_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher around it: the process starts two ranks itself (child processes),
     relays rank 0's line and reports n_gpus == 2 (it used to run one rank silently)."""
