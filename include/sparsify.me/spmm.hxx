@@ -8,10 +8,13 @@
 // (examples/spmm.cu:96,102,115), `B` is shared by all batches.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 
 #include <cstddef>
 #include <cstdint>
 #include <iostream>
+#include <type_traits>
 #include <vector>
 
 #include <sparsifyme.h>
@@ -22,6 +25,60 @@
 
 namespace sparsifyme {
 namespace batched {
+namespace detail {
+// The 16-bit element types of batched::spmm (the spellings spmma_fns<> accepts): fp16 and bfloat16 storage, fp32 accumulation.
+template <typename type_t>
+struct bell16_type {
+  static constexpr bool bf16 = std::is_same<type_t, __bf16>::value || std::is_same<type_t, __hip_bfloat16>::value;
+  static constexpr bool f16 = std::is_same<type_t, __half>::value || std::is_same<type_t, _Float16>::value;
+  static_assert(bf16 || f16, "batched::spmm: 2-byte element types are __half, _Float16, __bf16 and __hip_bfloat16");
+  static int batched(const void* const* v, const std::uint64_t* const* i, std::size_t rows, std::size_t cols, std::size_t bs,
+                     std::size_t ell_cols, const void* B, void* const* C, std::size_t n, std::size_t batch, float al, float be) {
+    return bf16 ? sm_spmm_bell_batched_bf16(v, i, rows, cols, bs, ell_cols, B, C, n, batch, al, be, nullptr)
+                : sm_spmm_bell_batched_f16(v, i, rows, cols, bs, ell_cols, B, C, n, batch, al, be, nullptr);
+  }
+  static int single(const void* v, const std::uint64_t* i, std::size_t rows, std::size_t cols, std::size_t bs, std::size_t ell_cols,
+                    const void* B, void* C, std::size_t n, float al, float be) {
+    return bf16 ? sm_spmm_bell_bf16(v, i, rows, cols, bs, ell_cols, B, C, n, al, be, nullptr)
+                : sm_spmm_bell_f16(v, i, rows, cols, bs, ell_cols, B, C, n, al, be, nullptr);
+  }
+};
+
+// fp16 / bfloat16: the blocks are expanded inside the product (sm_spmm_bell_*_{f16,bf16}); no workspace
+template <typename type_t>
+float spmm16(ell_t<type_t, memory_space_t::device>* As, type_t* B, type_t** Cs, std::size_t n, std::size_t batch_size, float alpha,
+             float beta) {
+  using fns = bell16_type<type_t>;
+  (void)hipDeviceSynchronize();
+  util::timer_t t;
+  int rc = SM_STATUS_SUCCESS;
+  bool uniform = batch_size > 0;
+  for (std::size_t b = 1; b < batch_size; ++b)
+    uniform = uniform && As[b].rows == As[0].rows && As[b].cols == As[0].cols &&
+              As[b].block_size == As[0].block_size && As[b].ell_cols == As[0].ell_cols;
+  std::vector<const void*> vals(batch_size);
+  std::vector<const std::uint64_t*> idx(batch_size);
+  for (std::size_t b = 0; b < batch_size; ++b) {
+    vals[b] = static_cast<const void*>(As[b].values.data().get());
+    idx[b] = reinterpret_cast<const std::uint64_t*>(As[b].column_indices.data().get());
+  }
+  t.begin();
+  util::range_t range("batched-SpMM");  // the reference's NVTX range (spmm.hxx:92,121)
+  if (uniform) {
+    rc = fns::batched(vals.data(), idx.data(), As[0].rows, As[0].cols, As[0].block_size, As[0].ell_cols, B,
+                      reinterpret_cast<void* const*>(Cs), n, batch_size, alpha, beta);
+  } else {
+    for (std::size_t b = 0; b < batch_size; ++b) {
+      auto& A = As[b];
+      const int rb = fns::single(vals[b], idx[b], A.rows, A.cols, A.block_size, A.ell_cols, B, Cs[b], n, alpha, beta);
+      if (rc == SM_STATUS_SUCCESS) rc = rb;  // the first failing status is the one reported
+    }
+  }
+  t.end();
+  if (rc != SM_STATUS_SUCCESS) std::cerr << "sparsifyme::batched::spmm: " << sm_last_error() << std::endl;
+  return t.milliseconds();
+}
+}  // namespace detail
 
 template <typename type_t>
 float spmm(ell_t<type_t, memory_space_t::device>* As,
@@ -35,51 +92,55 @@ float spmm(ell_t<type_t, memory_space_t::device>* As,
            operation_t transpose_b = operation_t::N,
            float alpha = 1.0f,
            float beta = 0.0f) {
-  static_assert(sizeof(type_t) == 4, "this build implements the fp32 Blocked-ELL SpMM");
+  static_assert(sizeof(type_t) == 4 || sizeof(type_t) == 2, "Blocked-ELL SpMM: fp32, fp16 or bfloat16 elements");
   (void)transpose_a;
   (void)transpose_b;
-  (void)hipDeviceSynchronize();
-  util::timer_t t;
-  int rc = SM_STATUS_SUCCESS;
-  // The reference creates its per-batch cuSPARSE descriptors and buffers before its timed region (spmm.hxx:70-88);
-  // the analogue here is the dense-expansion workspace.  Equal-shaped batches (what every driver builds) go down
-  // in one submission; ragged ones batch by batch through a single reused workspace.
-  bool uniform = batch_size > 0;
-  for (std::size_t b = 1; b < batch_size; ++b)
-    uniform = uniform && As[b].rows == As[0].rows && As[b].cols == As[0].cols &&
-              As[b].block_size == As[0].block_size && As[b].ell_cols == As[0].ell_cols;
-  std::size_t ws_bytes = 0;
-  std::vector<const float*> vals(batch_size);
-  std::vector<const std::uint64_t*> idx(batch_size);
-  for (std::size_t b = 0; b < batch_size; ++b) {
-    std::size_t w = 0;
-    (void)sm_spmm_bell_workspace_size(As[b].rows, As[b].cols, &w);
-    ws_bytes = w > ws_bytes ? w : ws_bytes;
-    vals[b] = reinterpret_cast<const float*>(As[b].values.data().get());
-    idx[b] = reinterpret_cast<const std::uint64_t*>(As[b].column_indices.data().get());
-  }
-  if (uniform) (void)sm_spmm_bell_batched_workspace_size(As[0].rows, As[0].cols, batch_size, &ws_bytes);
-  device_vector<unsigned char> ws(ws_bytes);
-  t.begin();
-  util::range_t range("batched-SpMM");  // the reference's NVTX range (spmm.hxx:92,121)
-  if (uniform) {
-    rc = sm_spmm_bell_batched_f32(vals.data(), idx.data(), As[0].rows, As[0].cols, As[0].block_size, As[0].ell_cols,
-                                  reinterpret_cast<const float*>(B), reinterpret_cast<float* const*>(Cs), n, batch_size,
-                                  alpha, beta, ws.data().get(), nullptr);
-  } else {
-    for (std::size_t b = 0; b < batch_size; ++b) {
-      auto& A = As[b];
-      const int rb = sm_spmm_bell_f32_ws(vals[b], idx[b], A.rows, A.cols, A.block_size, A.ell_cols,
-                                         reinterpret_cast<const float*>(B), reinterpret_cast<float*>(Cs[b]), n, alpha, beta,
-                                         ws.data().get(), nullptr);
-      if (rc == SM_STATUS_SUCCESS) rc = rb;  // the first failing status is the one reported
-    }
-  }
   (void)m;
   (void)k;
-  t.end();
-  if (rc != SM_STATUS_SUCCESS) std::cerr << "sparsifyme::batched::spmm: " << sm_last_error() << std::endl;
-  return t.milliseconds();
+  if constexpr (sizeof(type_t) == 2) {
+    return detail::spmm16(As, B, Cs, n, batch_size, alpha, beta);
+  } else {
+    (void)hipDeviceSynchronize();
+    util::timer_t t;
+    int rc = SM_STATUS_SUCCESS;
+    // The reference creates its per-batch cuSPARSE descriptors and buffers before its timed region (spmm.hxx:70-88);
+    // the analogue here is the dense-expansion workspace.  Equal-shaped batches (what every driver builds) go down
+    // in one submission; ragged ones batch by batch through a single reused workspace.
+    bool uniform = batch_size > 0;
+    for (std::size_t b = 1; b < batch_size; ++b)
+      uniform = uniform && As[b].rows == As[0].rows && As[b].cols == As[0].cols &&
+                As[b].block_size == As[0].block_size && As[b].ell_cols == As[0].ell_cols;
+    std::size_t ws_bytes = 0;
+    std::vector<const float*> vals(batch_size);
+    std::vector<const std::uint64_t*> idx(batch_size);
+    for (std::size_t b = 0; b < batch_size; ++b) {
+      std::size_t w = 0;
+      (void)sm_spmm_bell_workspace_size(As[b].rows, As[b].cols, &w);
+      ws_bytes = w > ws_bytes ? w : ws_bytes;
+      vals[b] = reinterpret_cast<const float*>(As[b].values.data().get());
+      idx[b] = reinterpret_cast<const std::uint64_t*>(As[b].column_indices.data().get());
+    }
+    if (uniform) (void)sm_spmm_bell_batched_workspace_size(As[0].rows, As[0].cols, batch_size, &ws_bytes);
+    device_vector<unsigned char> ws(ws_bytes);
+    t.begin();
+    util::range_t range("batched-SpMM");  // the reference's NVTX range (spmm.hxx:92,121)
+    if (uniform) {
+      rc = sm_spmm_bell_batched_f32(vals.data(), idx.data(), As[0].rows, As[0].cols, As[0].block_size, As[0].ell_cols,
+                                    reinterpret_cast<const float*>(B), reinterpret_cast<float* const*>(Cs), n, batch_size,
+                                    alpha, beta, ws.data().get(), nullptr);
+    } else {
+      for (std::size_t b = 0; b < batch_size; ++b) {
+        auto& A = As[b];
+        const int rb = sm_spmm_bell_f32_ws(vals[b], idx[b], A.rows, A.cols, A.block_size, A.ell_cols,
+                                           reinterpret_cast<const float*>(B), reinterpret_cast<float*>(Cs[b]), n, alpha, beta,
+                                           ws.data().get(), nullptr);
+        if (rc == SM_STATUS_SUCCESS) rc = rb;  // the first failing status is the one reported
+      }
+    }
+    t.end();
+    if (rc != SM_STATUS_SUCCESS) std::cerr << "sparsifyme::batched::spmm: " << sm_last_error() << std::endl;
+    return t.milliseconds();
+  }
 }
 
 // strided_coo computes in full fp32 by default, as the reference's cusparseSpMM call does (CUDA_R_32F operands and compute type,

@@ -310,11 +310,43 @@ int sm_spmm_bell_f32_ws(const float* values, const uint64_t* column_indices, siz
  * exactly what the reference's driver builds).  Workspace: sm_spmm_bell_batched_workspace_size() bytes, required.
  * NOT hipGraph-capturable, unlike every other entry point: the three pointer tables are copied from the caller's HOST
  * arrays onto the stream (a synchronously staged copy from pageable memory); capture the per-matrix
- * sm_spmm_bell_f32_ws instead, or keep the host arrays alive and unchanged for the lifetime of the graph. */
+ * sm_spmm_bell_f32_ws instead, or keep the host arrays alive and unchanged for the lifetime of the graph.
+ * (The 16-bit forms below, sm_spmm_bell_batched_{f16,bf16}, pass their tables in the kernel arguments and can be captured.) */
 int sm_spmm_bell_batched_workspace_size(size_t rows, size_t cols, size_t batch, size_t* bytes /*host*/);
 int sm_spmm_bell_batched_f32(const float* const* values, const uint64_t* const* column_indices, size_t rows,
                              size_t cols, size_t block_size, size_t ell_cols, const float* B, float* const* C,
                              size_t n, size_t batch, float alpha, float beta, void* workspace, sm_stream_t stream);
+
+/* Blocked-ELL on the 16-bit matrix cores (fp16 / bfloat16 values, B and C; fp32 accumulation, one rounding of the result):
+ * the operand types the reference's descriptors declare (CUDA_R_16F, spmm.hxx:57-67,107-110).  Same layout and meaning as
+ * sm_spmm_bell_f32: values [rows][ell_cols] row-major, column_indices [ceil(rows/block_size)][ell_cols/block_size] (an id
+ * >= cols/block_size, ~0 included, marks an empty block), B cols x n column-major (ldb = cols), C rows x n column-major
+ * (ldc = rows); C is not read when beta == 0.  Any block_size >= 1 with ell_cols % block_size == 0; rows, cols and n need
+ * not be multiples of anything.  The blocks are expanded inside the product (in LDS): no workspace, no device allocation, no
+ * host synchronisation, deterministic.  A block row that stores its blocks in ascending order (every producer here does)
+ * takes the fast path when ell_cols <= 65535 and the per-tile stage table (2 bytes per block row of a 128-row tile and per
+ * 64 columns of A) fits in LDS beside the stage buffers: for n > 128, cols up to about 16 000 for block_size 1 and 32 000 for
+ * block_size 2 (about 28 000 and 56 000 for n <= 64).
+ * Any other order, and any larger shape, takes the generic path: the same C bit for bit, but every 64-column stage walks
+ * whole rows of A, a cost that grows with cols * ell_cols.  A block column repeated within one block
+ * row gives an unspecified result, as in the fp32 path.
+ * The batched forms take HOST arrays of `batch` device pointers (one A and one C per entry, B shared), read during the call
+ * and passed in the kernel arguments: the caller may free the arrays as soon as the call returns.
+ * Status: SM_STATUS_INVALID_VALUE for a null pointer, block_size == 0 or ell_cols % block_size != 0;
+ * SM_STATUS_NOT_SUPPORTED when rows, cols, n or ell_cols exceeds 2^31-1; SM_STATUS_SUCCESS without work when rows, n or
+ * batch is 0 -- all decided before any HIP call.  Every one of these four entry points can be captured into a hipGraph. */
+int sm_spmm_bell_f16(const void* values, const uint64_t* column_indices, size_t rows, size_t cols,
+                     size_t block_size, size_t ell_cols, const void* B, void* C, size_t n,
+                     float alpha, float beta, sm_stream_t stream);
+int sm_spmm_bell_bf16(const void* values, const uint64_t* column_indices, size_t rows, size_t cols,
+                      size_t block_size, size_t ell_cols, const void* B, void* C, size_t n,
+                      float alpha, float beta, sm_stream_t stream);
+int sm_spmm_bell_batched_f16(const void* const* values, const uint64_t* const* column_indices, size_t rows,
+                             size_t cols, size_t block_size, size_t ell_cols, const void* B, void* const* C,
+                             size_t n, size_t batch, float alpha, float beta, sm_stream_t stream);
+int sm_spmm_bell_batched_bf16(const void* const* values, const uint64_t* const* column_indices, size_t rows,
+                              size_t cols, size_t block_size, size_t ell_cols, const void* B, void* const* C,
+                              size_t n, size_t batch, float alpha, float beta, sm_stream_t stream);
 
 /* COO with a caller-provided workspace of sm_spmm_coo_workspace_size() bytes (the reference allocates its
  * cuSPARSE buffer inside the call, spmm.hxx:183): row-sorted input runs as CSR, row-parallel, without

@@ -133,6 +133,11 @@ _SIGS["sm_spmma_fused_f16_ws"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 8 + [_c_
 _SIGS["sm_spmma_fused_bf16_ws"] = _SIGS["sm_spmma_fused_f16_ws"]
 _SIGS["sm_spmma_fused_f16_grouped_ws"] = [_c_size, _c_ptr, _c_ptr, _c_ptr] + [_c_size] * 8 + [_c_f, _c_f, _c_ptr, _c_size, _c_ptr]
 _SIGS["sm_spmma_fused_bf16_grouped_ws"] = _SIGS["sm_spmma_fused_f16_grouped_ws"]
+# Blocked-ELL on the 16-bit matrix cores (spmm_bell16.hip)
+_SIGS["sm_spmm_bell_f16"] = _SIGS["sm_spmm_bell_f32"]
+_SIGS["sm_spmm_bell_bf16"] = _SIGS["sm_spmm_bell_f32"]
+_SIGS["sm_spmm_bell_batched_f16"] = [_c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_size, _c_ptr, _c_ptr, _c_size, _c_size, _c_f, _c_f, _c_ptr]
+_SIGS["sm_spmm_bell_batched_bf16"] = _SIGS["sm_spmm_bell_batched_f16"]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -528,6 +533,53 @@ def conv_spmma(X, B, C, N, Cin, H, W, kh, kw, stride, pad, dilation, n_out, work
     wb = workspace.numel() * workspace.element_size() if workspace is not None else 0
     _check(fn(_dev(X), _dev(B), _dev(C), N, Cin, H, W, kh, kw, stride, pad, dilation, n_out, float(alpha), float(beta),
               _dev(workspace) if workspace is not None else None, wb, _stream()), "sm_conv_spmma")
+
+
+def _bell_sfx(values):
+    torch = _t()
+    sfx = {torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32"}.get(values.dtype)
+    if sfx is None:
+        raise SparsifymeError(f"spmm_bell: values must be float16, bfloat16 or float32, not {values.dtype}")
+    return sfx
+
+
+def spmm_bell(values, column_indices, B, C, rows, cols, block_size, ell_cols, n, alpha=1.0, beta=0.0):
+    """sparsifyme::batched::spmm for one Blocked-ELL A (spmm.hxx:57-67,107-110): C (rows x n, column-major) = alpha * A * B + beta * C.
+    values [rows][ell_cols] and B / C in fp16, bf16 (the 16-bit matrix-core kernel) or fp32 (the fp32 route, with its workspace
+    allocated here); column_indices int64 / uint64 [ceil(rows/block_size)][ell_cols/block_size]."""
+    sfx = _bell_sfx(values)
+    if sfx in ("f16", "bf16"):
+        fn = getattr(lib(), "sm_spmm_bell_" + sfx)
+        _check(fn(_dev(values), _dev(column_indices), rows, cols, block_size, ell_cols, _dev(B), _dev(C), n, float(alpha), float(beta),
+                  _stream()), "sm_spmm_bell_" + sfx)
+        return
+    nb = _c_size(0)
+    _check(lib().sm_spmm_bell_workspace_size(rows, cols, ctypes.byref(nb)), "sm_spmm_bell_workspace_size")
+    ws = _t().empty(max(nb.value, 1), dtype=_t().uint8, device=values.device)
+    _check(lib().sm_spmm_bell_f32_ws(_dev(values), _dev(column_indices), rows, cols, block_size, ell_cols, _dev(B), _dev(C), n, float(alpha),
+                                     float(beta), _dev(ws), _stream()), "sm_spmm_bell_f32_ws")
+
+
+def spmm_bell_batched(values_list, indices_list, B, C_list, rows, cols, block_size, ell_cols, n, alpha=1.0, beta=0.0):
+    """All batches of sparsifyme::batched::spmm in one submission: one A (values, indices) and one C per entry, B shared.
+    fp16 / bf16: sm_spmm_bell_batched_{f16,bf16} (no workspace); fp32: sm_spmm_bell_batched_f32 with its workspace allocated here."""
+    if not (len(values_list) == len(indices_list) == len(C_list)):
+        raise SparsifymeError("spmm_bell_batched: operand lists differ in length")
+    if not values_list:
+        return
+    sfx = _bell_sfx(values_list[0])
+    pv, pi, pc = _ptr_table(values_list), _ptr_table(indices_list), _ptr_table(C_list)
+    batch = len(values_list)
+    if sfx in ("f16", "bf16"):
+        fn = getattr(lib(), "sm_spmm_bell_batched_" + sfx)
+        _check(fn(pv, pi, rows, cols, block_size, ell_cols, _dev(B), pc, n, batch, float(alpha), float(beta), _stream()),
+               "sm_spmm_bell_batched_" + sfx)
+        return
+    nb = _c_size(0)
+    _check(lib().sm_spmm_bell_batched_workspace_size(rows, cols, batch, ctypes.byref(nb)), "sm_spmm_bell_batched_workspace_size")
+    ws = _t().empty(max(nb.value, 1), dtype=_t().uint8, device=values_list[0].device)
+    _check(lib().sm_spmm_bell_batched_f32(pv, pi, rows, cols, block_size, ell_cols, _dev(B), pc, n, batch, float(alpha), float(beta),
+                                          _dev(ws), _stream()), "sm_spmm_bell_batched_f32")
 
 
 def gemm_batched(A_ptrs, B_ptrs, C_ptrs, m, n, k, batch, dtype_suffix, alpha=1.0, beta=0.0, ta=0, tb=0, workspace=None):
