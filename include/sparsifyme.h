@@ -469,6 +469,48 @@ int sm_spmma_fused_i8(const void* A, const void* B, int32_t* C, size_t m, size_t
 int sm_spmma_fused_i8_q(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch,
                         size_t strideA, size_t strideB, size_t strideC, float scale, sm_stream_t stream);
 
+/* ---- OCP fp8 forms (extension).  Elements are bytes in one of the two OCP 8-bit float encodings (torch.float8_e4m3fn /
+ *      torch.float8_e5m2; not the fnuz encodings), named by `fmt`.  The rules are the fp16 rules on the exact fp16 image of
+ *      the bytes: the result of sm_prune24_fp8 is that of sm_prune24_f16 on the image, mapped back, bit for bit.  Keys are
+ *      bits & 0x7f (-0 and +0 equal, NaN above every finite value and inf; an e5m2 NaN keys as its quieted image does:
+ *      0x7d as 0x7f), ties keep the lower k; TILE adds the image's magnitudes in fp32 as sm_prune24_f16 does.  Dropped
+ *      positions become 0x00, kept bytes are left as they are (NaN payloads included).  A byte is zero when
+ *      (v & 0x7f) == 0: 0x80 (-0) is zero, NaN is not.  Same blob geometry as int8 (sm_compress24_size(m, k, 1, batch,
+ *      ...)); the 2-bit codes of a strip are those sm_compress24_f16 stores for the image.
+ *      sm_spmma_fp8: C_b = alpha * row_scale[i] * (A_2:4,b . B_b) + beta * C_b on v_smfmac_f32_16x16x128_<A>_<B>, fp32
+ *      accumulation, one rounding to the output type at the end (beta reads C in that type; beta == 0 does not read C).
+ *      A and B may be in different formats.  B is [n][k], K-CONTIGUOUS per output column as for sm_spmma_i8
+ *      (sm_transpose_i8 turns a row-major k x n B into it), B_b = B + b * strideB (0 = shared); C is row-major m x n of
+ *      out_type, C_b = C + b * strideC (elements).  row_scale: NULL (= 1) or a device array of m floats, the per-output-
+ *      channel dequantisation scale of fp8 weights (a per-tensor scale folds into alpha).
+ *      Needs k % 64 == 0, an even m, a 16-byte aligned B and strideB % 16 == 0 (the fused form also 16-byte aligned rows
+ *      of A: lda % 16 == 0, strideA % 16 == 0), each dimension below 2^31: SM_STATUS_NOT_SUPPORTED otherwise, decided
+ *      before any device work.  A null operand, a bad fmt / out_type / alg or ld < k: SM_STATUS_INVALID_VALUE.  Like every
+ *      entry point here they only enqueue work, so they can be captured into a hipGraph. */
+#define SM_FP8_E4M3 0 /* OCP e4m3 ("fn": no inf, NaN = 0x7f / 0xff), torch.float8_e4m3fn */
+#define SM_FP8_E5M2 1 /* OCP e5m2 (IEEE-like: inf and NaN), torch.float8_e5m2 */
+#define SM_OUT_F32 0
+#define SM_OUT_F16 1
+#define SM_OUT_BF16 2
+/* A_in / A_out row-major m x k, ld; may alias (in place).  alg = SM_PRUNE_TILE or SM_PRUNE_STRIP; fmt matters to TILE only
+ * for the magnitudes and to both for e5m2 NaN keys. */
+int sm_prune24_fp8(const void* A_in, void* A_out, size_t m, size_t k, size_t ld, int alg, int fmt, sm_stream_t stream);
+/* *d_valid = 0 iff every strip holds <= 2 non-zeros ((v & 0x7f) != 0), else 1 (the same for both formats). */
+int sm_prune24_check_fp8(const void* A, size_t m, size_t k, size_t ld, int* d_valid, sm_stream_t stream);
+/* STRIP selection of the two largest keys per strip, as sm_compress24_i8 but with the fp8 keys of `fmt`; blob 16-byte aligned. */
+int sm_compress24_fp8(const void* A, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, void* blob, int fmt,
+                      sm_stream_t stream);
+int sm_decompress24_fp8(const void* blob, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, void* A,
+                        sm_stream_t stream);
+int sm_spmma_fp8(const void* blob, const void* B, void* C, size_t m, size_t n, size_t k, size_t batch, size_t strideB,
+                 size_t strideC, int fmt_a, int fmt_b, int out_type, float alpha, float beta, const float* row_scale,
+                 sm_stream_t stream);
+/* prune (STRIP) + compress + matmul in one kernel straight from the dense fp8 A (row-major, lda, batch stride strideA):
+ * C bit-identical to sm_prune24_fp8(STRIP) + sm_compress24_fp8 + sm_spmma_fp8, no blob. */
+int sm_spmma_fused_fp8(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                       size_t strideA, size_t strideB, size_t strideC, int fmt_a, int fmt_b, int out_type, float alpha,
+                       float beta, const float* row_scale, sm_stream_t stream);
+
 /* ---- im2col front end (extension).  X: N x C x H x W activations (NCHW, contiguous).
  *      A: per image the row-major L x K operand of the layer's matmul, L = out_h * out_w rows (row oh * out_w + ow),
  *      K = C * kh * kw columns (column c * kh * kw + r * kw + u), images back to back -- the transpose of torch's

@@ -138,6 +138,13 @@ _SIGS["sm_spmm_bell_f16"] = _SIGS["sm_spmm_bell_f32"]
 _SIGS["sm_spmm_bell_bf16"] = _SIGS["sm_spmm_bell_f32"]
 _SIGS["sm_spmm_bell_batched_f16"] = [_c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_size, _c_ptr, _c_ptr, _c_size, _c_size, _c_f, _c_f, _c_ptr]
 _SIGS["sm_spmm_bell_batched_bf16"] = _SIGS["sm_spmm_bell_batched_f16"]
+# OCP fp8 (e4m3 / e5m2) 2:4 path (spmma_fp8.hip)
+_SIGS["sm_prune24_fp8"] = [_c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_i, _c_i, _c_ptr]
+_SIGS["sm_prune24_check_fp8"] = _SIGS["sm_prune24_check_f16"]
+_SIGS["sm_compress24_fp8"] = [_c_ptr, _c_size, _c_size, _c_size, _c_size, _c_size, _c_ptr, _c_i, _c_ptr]
+_SIGS["sm_decompress24_fp8"] = _SIGS["sm_decompress24_f16"]
+_SIGS["sm_spmma_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 6 + [_c_i, _c_i, _c_i, _c_f, _c_f, _c_ptr, _c_ptr]
+_SIGS["sm_spmma_fused_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 8 + [_c_i, _c_i, _c_i, _c_f, _c_f, _c_ptr, _c_ptr]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -358,6 +365,74 @@ def spmma_i8_q(blob, B, C, m, n, k, scale, batch=1, strideB=0, strideC=None):
     strideC = m * n if strideC is None else strideC
     _check(lib().sm_spmma_i8_q(_dev(blob), _dev(B), _dev(C), m, n, k, batch, strideB, strideC, float(scale), _stream()),
            "sm_spmma_i8_q")
+
+
+# ---- OCP fp8 (include/sparsifyme.h: SM_FP8_*, SM_OUT_*) ----------------------------------------
+FP8_E4M3, FP8_E5M2 = 0, 1
+OUT_F32, OUT_F16, OUT_BF16 = 0, 1, 2
+
+
+def fp8_format(dtype):
+    """SM_FP8_* of a torch dtype: float8_e4m3fn or float8_e5m2 (the OCP encodings; the fnuz ones are refused)."""
+    torch = _t()
+    fmts = {torch.float8_e4m3fn: FP8_E4M3, torch.float8_e5m2: FP8_E5M2}
+    if dtype not in fmts:
+        raise SparsifymeError(f"expected torch.float8_e4m3fn or torch.float8_e5m2, not {dtype}")
+    return fmts[dtype]
+
+
+def _fp8_out_type(C):
+    torch = _t()
+    outs = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+    if C.dtype not in outs:
+        raise SparsifymeError(f"fp8 spmma writes float32, float16 or bfloat16, not {C.dtype}")
+    return outs[C.dtype]
+
+
+def prune24_fp8(A_in, A_out, m, k, ld, alg=PRUNE_STRIP):
+    """2:4 prune of an fp8 matrix: the fp16 rule on its exact fp16 image, mapped back (dropped bytes become 0x00)."""
+    fmt = fp8_format(A_in.dtype)
+    if A_out.dtype != A_in.dtype:
+        raise SparsifymeError("prune24_fp8: A_in and A_out differ in dtype")
+    _check(lib().sm_prune24_fp8(_dev(A_in), _dev(A_out), m, k, ld, alg, fmt, _stream()), "sm_prune24_fp8")
+
+
+def prune24_check_fp8(A, m, k, ld, d_valid):
+    fp8_format(A.dtype)
+    _check(lib().sm_prune24_check_fp8(_dev(A), m, k, ld, _dev(d_valid), _stream()), "sm_prune24_check_fp8")
+
+
+def compress24_fp8(A, m, k, ld, batch, strideA, blob):
+    """blob: compress24_size(m, k, 1, batch) bytes."""
+    _check(lib().sm_compress24_fp8(_dev(A), m, k, ld, batch, strideA, _dev(blob), fp8_format(A.dtype), _stream()), "sm_compress24_fp8")
+
+
+def decompress24_fp8(blob, m, k, ld, batch, strideA, A):
+    fp8_format(A.dtype)
+    _check(lib().sm_decompress24_fp8(_dev(blob), m, k, ld, batch, strideA, _dev(A), _stream()), "sm_decompress24_fp8")
+
+
+def spmma_fp8(blob, B, C, m, n, k, batch=1, strideB=0, strideC=None, alpha=1.0, beta=0.0, row_scale=None, a_dtype=None):
+    """fp8 2:4 product: C = alpha * row_scale[i] * (A_2:4 . B) + beta * C.  B [n][k] fp8 (k-contiguous per output column);
+    C float32 / float16 / bfloat16; row_scale None or m float32 on the device.  a_dtype: A's fp8 dtype (the blob does not
+    carry it); None = B's."""
+    strideC = m * n if strideC is None else strideC
+    fa = fp8_format(B.dtype if a_dtype is None else a_dtype)
+    ot = _fp8_out_type(C)
+    rs = _dev(row_scale) if row_scale is not None else None
+    _check(lib().sm_spmma_fp8(_dev(blob), _dev(B), _dev(C), m, n, k, batch, strideB, strideC, fa, fp8_format(B.dtype), ot, float(alpha),
+                              float(beta), rs, _stream()), "sm_spmma_fp8")
+
+
+def spmma_fused_fp8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, alpha=1.0, beta=0.0, row_scale=None):
+    """prune (STRIP) + compress + spmma_fp8 in one kernel from the dense fp8 A; the same C bit for bit."""
+    lda = k if lda is None else lda
+    strideA = m * lda if strideA is None else strideA
+    strideC = m * n if strideC is None else strideC
+    ot = _fp8_out_type(C)
+    rs = _dev(row_scale) if row_scale is not None else None
+    _check(lib().sm_spmma_fused_fp8(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, fp8_format(A.dtype),
+                                    fp8_format(B.dtype), ot, float(alpha), float(beta), rs, _stream()), "sm_spmma_fused_fp8")
 
 
 def spmma_fused_workspace_size():
