@@ -468,6 +468,16 @@ int sm_spmma_fused_i8(const void* A, const void* B, int32_t* C, size_t m, size_t
                       size_t strideA, size_t strideB, size_t strideC, int accumulate, sm_stream_t stream);
 int sm_spmma_fused_i8_q(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch,
                         size_t strideA, size_t strideB, size_t strideC, float scale, sm_stream_t stream);
+/* Dense int8 GEMM in the same layout, the like-for-like dense denominator of sm_spmma_i8: C (int32) = A . B (+ C when
+ * accumulate != 0), or requantised as sm_spmma_i8_q, exact integer arithmetic on v_mfma_i32_16x16x64_i8.  A is row-major
+ * m x k (lda, A_b = A + b * strideA), B [n][k] as for sm_spmma_i8 (strideB = 0: shared), C row-major m x n (strideC).
+ * Shared B with contiguous A and C runs as one tall matrix.  Needs k % 64 == 0 and 16-byte aligned rows of A and B
+ * (lda, strideA, strideB multiples of 16), each dimension below 2^31; any m (no even-m rule): SM_STATUS_NOT_SUPPORTED
+ * otherwise.  A null operand or lda < k: SM_STATUS_INVALID_VALUE.  Both decided before any device work. */
+int sm_gemm_rowmajor_i8(const void* A, const void* B, int32_t* C, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                        size_t strideA, size_t strideB, size_t strideC, int accumulate, sm_stream_t stream);
+int sm_gemm_rowmajor_i8_q(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                          size_t strideA, size_t strideB, size_t strideC, float scale, sm_stream_t stream);
 
 /* ---- OCP fp8 forms (extension).  Elements are bytes in one of the two OCP 8-bit float encodings (torch.float8_e4m3fn /
  *      torch.float8_e5m2; not the fnuz encodings), named by `fmt`.  The rules are the fp16 rules on the exact fp16 image of
@@ -510,6 +520,13 @@ int sm_spmma_fp8(const void* blob, const void* B, void* C, size_t m, size_t n, s
 int sm_spmma_fused_fp8(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch,
                        size_t strideA, size_t strideB, size_t strideC, int fmt_a, int fmt_b, int out_type, float alpha,
                        float beta, const float* row_scale, sm_stream_t stream);
+/* Dense fp8 GEMM in the same layout, the like-for-like dense denominator of sm_spmma_fp8: C_b = alpha * row_scale[i] *
+ * (A_b . B_b) + beta * C_b with the epilogue, formats, output types and statuses of sm_spmma_fused_fp8, on the full-rate
+ * dense v_mfma_f32_16x16x128_f8f6f4 (fp32 accumulation).  A is row-major m x k (lda, A_b = A + b * strideA), every
+ * element multiplied.  Any m (no even-m rule). */
+int sm_gemm_rowmajor_fp8(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                         size_t strideA, size_t strideB, size_t strideC, int fmt_a, int fmt_b, int out_type, float alpha,
+                         float beta, const float* row_scale, sm_stream_t stream);
 
 /* ---- im2col front end (extension).  X: N x C x H x W activations (NCHW, contiguous).
  *      A: per image the row-major L x K operand of the layer's matmul, L = out_h * out_w rows (row oh * out_w + ow),

@@ -145,6 +145,10 @@ _SIGS["sm_compress24_fp8"] = [_c_ptr, _c_size, _c_size, _c_size, _c_size, _c_siz
 _SIGS["sm_decompress24_fp8"] = _SIGS["sm_decompress24_f16"]
 _SIGS["sm_spmma_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 6 + [_c_i, _c_i, _c_i, _c_f, _c_f, _c_ptr, _c_ptr]
 _SIGS["sm_spmma_fused_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 8 + [_c_i, _c_i, _c_i, _c_f, _c_f, _c_ptr, _c_ptr]
+# dense 1-byte GEMM (gemm_b8.hip): the signatures of the fused forms
+_SIGS["sm_gemm_rowmajor_fp8"] = _SIGS["sm_spmma_fused_fp8"]
+_SIGS["sm_gemm_rowmajor_i8"] = _SIGS["sm_spmma_fused_i8"]
+_SIGS["sm_gemm_rowmajor_i8_q"] = _SIGS["sm_spmma_fused_i8_q"]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -433,6 +437,41 @@ def spmma_fused_fp8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0
     rs = _dev(row_scale) if row_scale is not None else None
     _check(lib().sm_spmma_fused_fp8(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, fp8_format(A.dtype),
                                     fp8_format(B.dtype), ot, float(alpha), float(beta), rs, _stream()), "sm_spmma_fused_fp8")
+
+
+def gemm_rowmajor_fp8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, alpha=1.0, beta=0.0, row_scale=None):
+    """dense fp8 GEMM: C = alpha * row_scale[i] * (A . B) + beta * C.  A row-major m x k fp8, B [n][k] fp8 (formats from their
+    dtypes), C float32 / float16 / bfloat16 (the output type from its dtype); the dense denominator of spmma_fp8."""
+    lda = k if lda is None else lda
+    strideA = m * lda if strideA is None else strideA
+    strideC = m * n if strideC is None else strideC
+    fa, fb = fp8_format(A.dtype), fp8_format(B.dtype)
+    ot = _fp8_out_type(C)
+    rs = _dev(row_scale) if row_scale is not None else None
+    _check(lib().sm_gemm_rowmajor_fp8(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, fa, fb, ot, float(alpha),
+                                      float(beta), rs, _stream()), "sm_gemm_rowmajor_fp8")
+
+
+def gemm_rowmajor_i8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, accumulate=False):
+    """dense int8 GEMM: C (int32) = A . B (+ C when accumulate); A row-major m x k int8, B [n][k] int8."""
+    lda = k if lda is None else lda
+    strideA = m * lda if strideA is None else strideA
+    strideC = m * n if strideC is None else strideC
+    if C.dtype != _t().int32:
+        raise SparsifymeError("gemm_rowmajor_i8 writes int32; use gemm_rowmajor_i8_q for a requantised int8 result")
+    _check(lib().sm_gemm_rowmajor_i8(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, 1 if accumulate else 0,
+                                     _stream()), "sm_gemm_rowmajor_i8")
+
+
+def gemm_rowmajor_i8_q(A, B, C, m, n, k, scale, lda=None, batch=1, strideA=None, strideB=0, strideC=None):
+    """dense int8 GEMM requantised to int8: C = saturate(rne(scale * acc))."""
+    lda = k if lda is None else lda
+    strideA = m * lda if strideA is None else strideA
+    strideC = m * n if strideC is None else strideC
+    if C.dtype != _t().int8:
+        raise SparsifymeError("gemm_rowmajor_i8_q writes int8")
+    _check(lib().sm_gemm_rowmajor_i8_q(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, float(scale), _stream()),
+           "sm_gemm_rowmajor_i8_q")
 
 
 def spmma_fused_workspace_size():

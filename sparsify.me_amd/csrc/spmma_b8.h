@@ -13,6 +13,8 @@
 //   D lane l, register q: row 4 (l >> 4) + q, column l & 15 (the fp16 SMFMAC's map).
 // Stage = 128 k = two 64-k planes of the blob: A values image [BM][64 B] (plane 0 | plane 1 per row: lane g's chunk is
 // chunk g), metadata [2][BM][8 B], B image [BN][128 B]; all by global_load_lds, ring of 2, one barrier per stage.
+// Three A modes: STAGED (the blob's values and metadata), FUSED (the dense tile [BM][128 B], selected in registers) and
+// DENSE (the same dense tile fed whole to the dense instruction, MmaI8Dense / MmaF8Dense: the dense GEMM).
 #pragma once
 #include "select24.h"
 #include "mma_tile.h"
@@ -328,18 +330,19 @@ struct Spmma8Args {
 typedef int i4v __attribute__((ext_vector_type(4)));
 typedef int i8v __attribute__((ext_vector_type(8)));
 
-// the matrix instruction of an element kind: Elem = A's kind (the fused form's selection), acc_t, mma
+// the matrix instruction of an element kind: Elem = A's kind (the fused form's selection), acc_t, mma; kDense: the
+// dense instruction of the same kind (A's fragment is 32 dense bytes, no index operand)
 struct MmaI8 {
   using Elem = ElemI8;
   using acc_t = i4v;
-  static constexpr bool kFloat = false;
+  static constexpr bool kFloat = false, kDense = false;
   static __device__ __forceinline__ i4v mma(i4v a, i8v b, i4v c, int idx) { return __builtin_amdgcn_smfmac_i32_16x16x128_i8(a, b, c, idx, 0, 0); }
 };
 template <int FA, int FB>
 struct MmaF8 {
   using Elem = ElemF8<FA>;
   using acc_t = f4;
-  static constexpr bool kFloat = true;
+  static constexpr bool kFloat = true, kDense = false;
   static __device__ __forceinline__ f4 mma(i4v a, i8v b, f4 c, int idx) {
     if constexpr (FA == SM_FP8_E4M3 && FB == SM_FP8_E4M3) return __builtin_amdgcn_smfmac_f32_16x16x128_fp8_fp8(a, b, c, idx, 0, 0);
     else if constexpr (FA == SM_FP8_E4M3) return __builtin_amdgcn_smfmac_f32_16x16x128_fp8_bf8(a, b, c, idx, 0, 0);
@@ -347,6 +350,39 @@ struct MmaF8 {
     else return __builtin_amdgcn_smfmac_f32_16x16x128_bf8_bf8(a, b, c, idx, 0, 0);
   }
 };
+
+// Dense forms.  A's fragment is read from a dense [rows][128 B] image exactly as B's is (frag_b8: chunks g and 4 + g), so A
+// and B share one k-to-lane map and every product pairs the right k whatever order the instruction sums in.
+//   int8: two v_mfma_i32_16x16x64_i8, one per 64-k half of the stage (bytes 0-15: k 16 g .., bytes 16-31: k 64 + 16 g ..).
+//   fp8: v_mfma_f32_16x16x128_f8f6f4 with cbsz / blgp = A's / B's format (0 = e4m3, 1 = e5m2, as SM_FP8_*) -- the
+//   full-rate dense fp8 instruction; literal-0 scale operands select its unscaled encoding (scale 1: exact products
+//   in tests/test_gpu_dense8.py).
+struct MmaI8Dense {
+  using Elem = ElemI8;
+  using acc_t = i4v;
+  static constexpr bool kFloat = false, kDense = true;
+  static __device__ __forceinline__ i4v mma(i8v a, i8v b, i4v c) {
+    c = __builtin_amdgcn_mfma_i32_16x16x64_i8(a.lo, b.lo, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a.hi, b.hi, c, 0, 0, 0);
+  }
+};
+template <int FA, int FB>
+struct MmaF8Dense {
+  static_assert(SM_FP8_E4M3 == 0 && SM_FP8_E5M2 == 1, "SM_FP8_* are the f8f6f4 format codes");
+  using Elem = ElemF8<FA>;
+  using acc_t = f4;
+  static constexpr bool kFloat = true, kDense = true;
+  static __device__ __forceinline__ f4 mma(i8v a, i8v b, f4 c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FA, FB, 0, 0, 0, 0);
+  }
+};
+
+// one lane's 32 operand bytes of row `row` of a [rows][128 B] stage image (a_off swizzle): chunks g and 4 + g
+__device__ __forceinline__ i8v frag_b8(const char* img, unsigned row, unsigned g) {
+  const u4 lo = *reinterpret_cast<const u4*>(img + a_off(row, g));
+  const u4 hi = *reinterpret_cast<const u4*>(img + a_off(row, 4u + g));
+  return i8v{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
 
 // fp8 epilogue of one output type: v = (alpha * row_scale[i]) * acc (+ beta * C), one rounding to the output type.
 // The accumulators were staged in the LDS image (4-byte words, CP bytes per row) when vec; otherwise they come from acc.
@@ -436,13 +472,16 @@ __device__ __forceinline__ void store_c_f8(const Spmma8Args& p, char* smem, cons
 // image is the DENSE tile [BM][128 B] (128 k), no metadata, and the lane that feeds the matrix instruction selects its
 // 8 strips (dense k 32 g .. 32 g + 31 = chunks 2 g, 2 g + 1 of its row) in registers: the same kept bytes and codes as
 // the compress kernel would have stored, so the result is bit-identical to compress + spmma; no blob exists.
+// DENSE (MM::kDense, FUSED false): the same dense tile, fed whole (frag_b8) to the dense instruction: C = A . B.
 template <class MM, int BN, int WM, int WN, bool FUSED = false>
 __global__ __launch_bounds__(64 * WM * WN) void spmma_b8_kernel(const Spmma8Args p) {
   using E = typename MM::Elem;
   using acc_t = typename MM::acc_t;
+  constexpr bool DENSE = MM::kDense, DA = FUSED || DENSE;  // DA: the stage holds the dense A tile
+  static_assert(!(FUSED && DENSE), "the dense instruction takes the dense tile as it is");
   constexpr int BM = 128, NW = WM * WN, TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
-  constexpr int SA = FUSED ? BM * 128 : BM * 64, SM_ = FUSED ? 0 : 2 * BM * 8, SB = BN * 128, STAGE = SA + SM_ + SB;
-  constexpr int A_N = FUSED ? BM / 8 : BM / 16, M_N = FUSED ? 0 : 2, B_N = BN / 8, W = A_N + M_N + B_N;  // 1 KiB DMA wave-instructions per stage
+  constexpr int SA = DA ? BM * 128 : BM * 64, SM_ = DA ? 0 : 2 * BM * 8, SB = BN * 128, STAGE = SA + SM_ + SB;
+  constexpr int A_N = DA ? BM / 8 : BM / 16, M_N = DA ? 0 : 2, B_N = BN / 8, W = A_N + M_N + B_N;  // 1 KiB DMA wave-instructions per stage
   constexpr int SL = (W + NW - 1) / NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -469,7 +508,7 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_b8_kernel(const Spmma8Args
   for (int i = 0; i < SL; ++i) {
     const unsigned t = wave + (unsigned)NW * i;
     src[i] = nullptr; step[i] = 0; loff[i] = 0; second[i] = false;
-    if (FUSED && t < (unsigned)A_N) {  // 8 rows x 128 B of the dense A
+    if (DA && t < (unsigned)A_N) {  // 8 rows x 128 B of the dense A
       const unsigned row = 8u * t + (lane >> 3), cs = (lane & 7u) ^ (row & 7u);
       int gr = m0 + (int)row;
       gr = gr < mlast ? gr : mlast;
@@ -534,9 +573,14 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_b8_kernel(const Spmma8Args
     const char* Bs = Ms + SM_;
     i4v af[FM];
     int idx[FM];
+    i8v ad[FM];
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
       const unsigned row = wm * TM + i * 16 + r;
+      if constexpr (DENSE) {
+        ad[i] = frag_b8(As, row, g);
+        continue;
+      }
       if constexpr (FUSED) {
         const u4 lo = *reinterpret_cast<const u4*>(As + a_off(row, 2u * g));
         const u4 hi = *reinterpret_cast<const u4*>(As + a_off(row, 2u * g + 1u));
@@ -555,12 +599,12 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_b8_kernel(const Spmma8Args
     }
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
-      const unsigned col = wn * TN + j * 16 + r;
-      const u4 lo = *reinterpret_cast<const u4*>(Bs + a_off(col, g));
-      const u4 hi = *reinterpret_cast<const u4*>(Bs + a_off(col, 4u + g));
-      const i8v bf = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+      const i8v bf = frag_b8(Bs, wn * TN + j * 16 + r, g);
 #pragma unroll
-      for (int i = 0; i < FM; ++i) acc[i][j] = MM::mma(af[i], bf, acc[i][j], idx[i]);
+      for (int i = 0; i < FM; ++i) {
+        if constexpr (DENSE) acc[i][j] = MM::mma(ad[i], bf, acc[i][j]);
+        else acc[i][j] = MM::mma(af[i], bf, acc[i][j], idx[i]);
+      }
     }
   }
   __syncthreads();
@@ -676,7 +720,7 @@ static int launch_spmma_b8(const Spmma8Args& a0, hipStream_t st, const char* wha
     set_error("%s: grid too large", what);
     return SM_STATUS_NOT_SUPPORTED;
   }
-  constexpr size_t lds_main = 2 * ((FUSED ? (size_t)128 * 128 : (size_t)128 * 64 + 2 * 128 * 8) + (size_t)BN * 128);
+  constexpr size_t lds_main = 2 * ((FUSED || MM::kDense ? (size_t)128 * 128 : (size_t)128 * 64 + 2 * 128 * 8) + (size_t)BN * 128);
   constexpr size_t lds_epi = (size_t)128 * (BN * 4 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static LdsOptIn lds_optin;
