@@ -14,7 +14,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SPARSIFYME_LIB: diagnostic builds only (e.g. the cycle-stamped library of tools/); default is the in-tree product library
+# SPARSIFYME_LIB: another build of the library to load; default is the in-tree product library
 LIB_PATH = os.environ.get("SPARSIFYME_LIB") or os.path.join(_HERE, "libsparsifyme.so")
 
 PRUNE_TILE = 0

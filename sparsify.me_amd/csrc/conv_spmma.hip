@@ -35,7 +35,6 @@ struct ConvArgs {
   int a_n;     // patch DMA instructions per stage
   int patch_bytes;  // per stage buffer, 16-byte multiple (incl. the zero tail after the last row)
   float alpha, beta;
-  int ablate;  // diagnostic timing builds (-DSM_TUNING, SM_CONV_ABLATE): 1 no patch DMA, 2 no gather, 4 no B DMA, 8 no SMFMAC; 0 in the product
 };
 
 __device__ __attribute__((aligned(256))) const unsigned char sm_conv_zero_page[256] = {0};
@@ -122,7 +121,7 @@ __global__ __launch_bounds__(256, SMALL ? (BN == 64 ? 4 : 3) : 1) void conv_spmm
     for (int i = 0; i < MAXA; ++i) {
       const int t = (int)wave + NW * i;  // wave-uniform
       if (t >= p.a_n) break;
-      if (a_on[i] && !(p.ablate & 1)) {
+      if (a_on[i]) {
         const bool live = a_src[i] >= 0 && cbase + a_ch[i] < p.Cin;
         if constexpr (V16) {
           gptr_t* g = live ? (gptr_t*)(Xc + a_src[i]) : (gptr_t*)(sm_conv_zero_page + 16u * (lane & 15u));
@@ -137,7 +136,6 @@ __global__ __launch_bounds__(256, SMALL ? (BN == 64 ? 4 : 3) : 1) void conv_spmm
     for (int i = 0; i < SLB; ++i) {
       const unsigned j = wave + (unsigned)NW * i;
       if (j >= (unsigned)B_N) break;
-      if (p.ablate & 4) continue;
       __builtin_amdgcn_global_load_lds((gptr_t*)(b_src[i] + (size_t)kt * 64 * p.Nout * 2), (lptr_t*)(base + p.patch_bytes + b_lds[i]), 16, 0, 0);
     }
   };
@@ -176,16 +174,11 @@ __global__ __launch_bounds__(256, SMALL ? (BN == 64 ? 4 : 3) : 1) void conv_spmm
     for (int i = 0; i < FM; ++i) {
       const char* base = Ps + poff[i];
       uint32_t d[8];
-      if (p.ablate & 2) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) d[e] = tw[e] + poff[i];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const uint32_t lo = *reinterpret_cast<const unsigned short*>(base + (tw[e] & 0xffffu));
-          const uint32_t hi = *reinterpret_cast<const unsigned short*>(base + (tw[e] >> 16));
-          d[e] = lo | (hi << 16);
-        }
+      for (int e = 0; e < 8; ++e) {
+        const uint32_t lo = *reinterpret_cast<const unsigned short*>(base + (tw[e] & 0xffffu));
+        const uint32_t hi = *reinterpret_cast<const unsigned short*>(base + (tw[e] >> 16));
+        d[e] = lo | (hi << 16);
       }
       uint32_t k0, k1, k2, k3, q0, q1, q2, q3;
       strip_select_f16(d[0], d[1], k0, q0);
@@ -220,9 +213,8 @@ __global__ __launch_bounds__(256, SMALL ? (BN == 64 ? 4 : 3) : 1) void conv_spmm
       const s16 all = {x0[c][0], x0[c][1], x0[c][2], x0[c][3], x1[c][0], x1[c][1], x1[c][2], x1[c][3],
                        x2[c][0], x2[c][1], x2[c][2], x2[c][3], x3[c][0], x3[c][1], x3[c][2], x3[c][3]};
       const h16 bf = __builtin_bit_cast(h16, all);
-      if (!(p.ablate & 8))
 #pragma unroll
-        for (int i = 0; i < FM; ++i) acc[i][j] = smfmac16<BF>(af[i], bf, acc[i][j], idx[i]);
+      for (int i = 0; i < FM; ++i) acc[i][j] = smfmac16<BF>(af[i], bf, acc[i][j], idx[i]);
     }
   }
   __syncthreads();  // nothing is in flight: the last iteration issued no DMA
@@ -321,10 +313,9 @@ static int conv_spmma16(const void* X, const void* B, void* C, size_t N, size_t 
   }
   // 16-byte patch DMAs (round 4) where rows are whole 16-byte pieces: W % 8 == 0, a 16-byte aligned X, the border rounded up to
   // 8 halves and the stage's plan within 16 instructions; when only those tighter limits fail (narrow images: W = 8 gains little
-  // per instruction and pays the wider border) the 4-byte form takes the layer as it did before round 4.  SM_CONV_V16 = 0 (tuning)
-  // keeps the 4-byte form everywhere.
+  // per instruction and pays the wider border) the 4-byte form takes the layer as it did before round 4.
   ConvArgs a = {};
-  bool v16 = W % 8 == 0 && aligned16(X) && tuning_int("SM_CONV_V16", 1) != 0;
+  bool v16 = W % 8 == 0 && aligned16(X);
   const size_t bn = n_out <= 64 ? 64 : 128;
   const char* why = v16 ? conv_geometry_plan(N, Cin, H, W, kh, kw, stride, pad, dil, true, bn, a) : "";
   if (why) {
@@ -339,13 +330,12 @@ static int conv_spmma16(const void* X, const void* B, void* C, size_t N, size_t 
   a.X = (const half_t*)X; a.B = (const half_t*)B; a.C = (half_t*)C;
   a.Nout = (int)n_out;
   a.alpha = alpha; a.beta = beta;
-  a.ablate = tuning_int("SM_CONV_ABLATE", 0);
   hipStream_t st = (hipStream_t)stream;
   // (256-column tiles for n_out > 128 -- the patch gathered once per 256 output channels -- were built and measured in round 4:
   //  n = 256 unchanged (73.8 vs 74.1 us), n = 512 slower (134 vs 103 us: 223 registers, two workgroups per CU, half the tiles);
   //  profiles/conv_levers_r04k.txt.  Not kept.)
   if (v16) return n_out <= 64 ? launch_conv<64, BF, true>(a, st) : launch_conv<128, BF, true>(a, st);
-  if (a.a_n <= 16 && tuning_int("SM_CONV_SMALL", 1) != 0) return n_out <= 64 ? launch_conv<64, BF, false, true>(a, st) : launch_conv<128, BF, false, true>(a, st);
+  if (a.a_n <= 16) return n_out <= 64 ? launch_conv<64, BF, false, true>(a, st) : launch_conv<128, BF, false, true>(a, st);
   if (n_out <= 64) return launch_conv<64, BF>(a, st);
   return launch_conv<128, BF>(a, st);
 }

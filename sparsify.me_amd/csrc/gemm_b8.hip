@@ -17,9 +17,6 @@ bool out_ok(int o) { return o == SM_OUT_F32 || o == SM_OUT_F16 || o == SM_OUT_BF
 // the fused 1-byte form's tiles: 128 x 64 over 4 x 1 waves for n <= 64, otherwise 128 x 128 over 4 x 2
 template <class MM>
 int gemm_b8_launch(const Spmma8Args& a, size_t n, hipStream_t st, const char* what) {
-  static const int cfg = tuning_int("SM_GEMM_B8_CFG", 0);  // tuning aid
-  if (cfg == 1) return launch_spmma_b8<MM, 64, 4, 1>(a, st, what);
-  if (cfg == 2) return launch_spmma_b8<MM, 128, 2, 4>(a, st, what);
   return n <= 64 ? launch_spmma_b8<MM, 64, 4, 1>(a, st, what) : launch_spmma_b8<MM, 128, 4, 2>(a, st, what);
 }
 

@@ -530,14 +530,11 @@ static int launch_gemm_f16(const GemmArgs& a, hipStream_t st, bool ta = false, b
     if (tb) return launch_cfg<128, 128, 2, 2, false, true>(a, vec, st);
   }
   // (round 4) the dense twin: ragged k and n > 128 run through the fused 2:4 kernels' pipelines with dense MFMA (spmma_f16_fused.hip:
-  // gemm_dense_twin) where those are the better pipelines; SM_GEMM_TWIN (tuning): 0 = never, 2 = wherever supported
+  // gemm_dense_twin) where those are the better pipelines
   if (a.ldb == a.N && a.ldc == a.N && a.M > 0) {
-    const int twin_mode = tuning_int("SM_GEMM_TWIN", 1);
-    if (twin_mode > 0) {
-      DenseTwinCall c = {a.A, a.B, a.C, a.Ap, a.Bp, a.Cp, a.sA, a.sB, a.sC, a.M, a.N, a.K, a.lda, a.batch, a.alpha, a.beta, BF, twin_mode, workspace, workspace_bytes};
-      const int rc = gemm_dense_twin(c, st);
-      if (rc != SM_STATUS_NOT_SUPPORTED) return rc;
-    }
+    DenseTwinCall c = {a.A, a.B, a.C, a.Ap, a.Bp, a.Cp, a.sA, a.sB, a.sC, a.M, a.N, a.K, a.lda, a.batch, a.alpha, a.beta, BF, workspace, workspace_bytes};
+    const int rc = gemm_dense_twin(c, st);
+    if (rc != SM_STATUS_NOT_SUPPORTED) return rc;
   }
   // pointer-array batches: per-batch base alignment is the caller's (hipMalloc gives 256 B);
   // DMA fast path: whole 64-deep K stages, N a multiple of 4 (a half-valid last chunk is served from columns
@@ -575,22 +572,6 @@ int gemm_f16_f32out(const void* A, const void* B2, float* C, size_t M, size_t N,
   a.alpha_dev = alpha_dev;
   a.skip_flag = skip_flag;
   if (N <= 64) return launch_dma<128, 64, 4, 1, 2, false, true>(a, st);
-#ifdef SM_TUNING
-  switch (tuning_int("SM_COOFAST_TILE", 0)) {  // A/B of the tile shape of this compute-bound product
-    case 1: return launch_dma<256, 128, 4, 2, 2, false, true>(a, st);
-    case 2: return launch_dma<128, 256, 2, 4, 2, false, true>(a, st);
-    case 3: return launch_dma<256, 128, 4, 2, 3, false, true>(a, st);
-    case 4: return launch_dma<128, 128, 2, 2, 3, false, true>(a, st);
-    case 5: return launch_dma<256, 256, 4, 4, 2, false, true>(a, st);
-    case 6: return launch_dma<64, 128, 1, 4, 2, false, true>(a, st);
-    case 7: return launch_dma<128, 64, 4, 1, 2, false, true>(a, st);
-    case 8: return launch_dma<64, 128, 1, 4, 3, false, true>(a, st);
-    case 9: return launch_dma<256, 256, 2, 4, 2, false, true>(a, st);
-    case 10: return launch_dma<256, 128, 2, 2, 2, false, true>(a, st);
-    case 11: return launch_dma<128, 256, 2, 2, 2, false, true>(a, st);
-    default: break;
-  }
-#endif
   // 256 x 256 tiles (16 waves, one workgroup per CU) halve the LDS bytes per flop of this compute-bound product; taken when they
   // still give most CUs a tile and pad N no worse than 128-wide tiles do (profiles/coo_fast_tiles_r03p.txt: 137 vs 157 us on
   // (2048 x 12544 x 1152), 101 vs 109 on (4096 x 3136 x 2304); 276 vs 199 and 148 vs 116 where the conditions fail)

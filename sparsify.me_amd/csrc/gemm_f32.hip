@@ -12,7 +12,6 @@
 // 256 threads = 4 waves; the operands of the MFMA are swapped so a lane ends with four consecutive
 // columns of one row and stores them as one 16-byte access.
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 
 #include "mma_tile.h"
@@ -598,46 +597,22 @@ static int launch_spmma32_dma(const Gemm32Args& a0, hipStream_t st) {
 // --dtype f32).  128 x 64 takes over once a CU gets >= 32 of the small tiles.
 template <int MODE>
 static int dispatch32(const Gemm32Args& a, hipStream_t st) {
-  struct Cand { int bm, bn; };
-  static const Cand cands[4] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
-  static const int force = tuning_int("SM_GEMM32_CFG", -1);  // tuning aid: candidate index
-  const double cus = (double)device_cu_count();
-  const double small_tiles = (double)((a.M + 63) / 64) * (double)((a.N + 63) / 64) * a.batch;
-  int best = small_tiles / cus >= 32.0 ? 1 : 3;
-  if (force >= 0 && force < 4) best = force;
   if constexpr (MODE == 0 || MODE == 2) {
     // LDS-DMA pipeline when whole 16-byte chunks can be moved: K % 32 == 0, aligned rows (pointer-array batches: the
-    // caller's bases, hipMalloc gives 256 B); SM_GEMM32_DMA=0 (tuning aid) keeps the register-staged kernel
-    static const int dma_env = tuning_int("SM_GEMM32_DMA", 1);
+    // caller's bases, hipMalloc gives 256 B)
     const bool a_ok = (a.lda % 4 == 0) && (a.sA % 4 == 0) && (a.Ap || (reinterpret_cast<uintptr_t>(a.A) & 15u) == 0);
     const bool b_ok = (a.ldb % 4 == 0) && (a.sB % 4 == 0) && (a.Bp || (reinterpret_cast<uintptr_t>(a.B) & 15u) == 0);
-    if (dma_env && a.K % 32 == 0 && a.K >= 32 && a_ok && b_ok && (MODE == 2 || (a.N % 4 == 0 && a.N >= 4))) {
+    if (a.K % 32 == 0 && a.K >= 32 && a_ok && b_ok && (MODE == 2 || (a.N % 4 == 0 && a.N >= 4))) {
       constexpr bool BKM = MODE == 2;
-      const int cfg = dma_env;  // 1: default choice; 2..: forced shapes for tuning
-      if (cfg == 2) return launch32_dma<64, 64, 2, 2, 2, BKM>(a, st);
-      if (cfg == 3) return launch32_dma<64, 64, 2, 2, 3, BKM>(a, st);
-      if (cfg == 4) return launch32_dma<128, 64, 4, 1, 2, BKM>(a, st);
-      if (cfg == 5) return launch32_dma<128, 128, 2, 2, 2, BKM>(a, st);
-      if (cfg == 6) return launch32_dma<128, 128, 2, 4, 2, BKM>(a, st);
-      if (cfg == 7) return launch32_dma<128, 64, 4, 1, 3, BKM>(a, st);
-      if (cfg == 8) return launch32_dma<128, 128, 2, 4, 3, BKM>(a, st);
-      if (cfg == 9) return launch32_dma<128, 128, 4, 4, 2, BKM>(a, st);
       // short operands get tiles as short as they are; narrow outputs 128 x 64 tiles (more of them); otherwise
-      // 128 x 128 over 16 waves (measured on the ResNet
-      // shapes and on 4096^3 / 8192^2 x 2048: tools/archive/f32_probe.py under SM_GEMM32_DMA=2..9)
-      if (cfg == 10) return launch32_dma<64, 128, 1, 4, 2, BKM>(a, st);
+      // 128 x 128 over 16 waves (measured on the ResNet shapes and on 4096^3 / 8192^2 x 2048: tools/archive/f32_probe.py)
       if (a.M <= 64) return a.N <= 64 ? launch32_dma<64, 64, 2, 2, 2, BKM>(a, st) : launch32_dma<64, 128, 1, 4, 2, BKM>(a, st);
       return a.N <= 128 ? launch32_dma<128, 64, 4, 1, 2, BKM>(a, st) : launch32_dma<128, 128, 4, 4, 2, BKM>(a, st);
     }
   }
-  static const bool verbose = tuning_env("SM_GEMM32_VERBOSE") != nullptr;  // tuning aid
-  if (verbose) fprintf(stderr, "gemm_f32 %d x %d x %d b=%d on %d CUs -> tile %d x %d\n", a.M, a.N, a.K, a.batch, (int)cus, cands[best].bm, cands[best].bn);
-  switch (best) {
-    case 1: return launch32<128, 64, 4, 1, MODE>(a, st);
-    case 2: return launch32<64, 128, 1, 4, MODE>(a, st);
-    case 3: return launch32<64, 64, 2, 2, MODE>(a, st);
-    default: return launch32<128, 128, 2, 2, MODE>(a, st);
-  }
+  const double cus = (double)device_cu_count();
+  const double small_tiles = (double)((a.M + 63) / 64) * (double)((a.N + 63) / 64) * a.batch;
+  return small_tiles / cus >= 32.0 ? launch32<128, 64, 4, 1, MODE>(a, st) : launch32<64, 64, 2, 2, MODE>(a, st);
 }
 
 // C^T[n x m] (row-major, ldc = m: i.e. column-major m x n C) = alpha * Bt[n x k] * Adense[m x k]^T + beta * C,
@@ -954,12 +929,9 @@ int sm_spmma_f32(const void* blob, const float* B, float* C, size_t m, size_t n,
     a.batch = 1;
   }
   // LDS-DMA pipeline: whole 64-k planes, row pairs (metadata moves as 16-byte pairs), whole 16-byte B chunks
-  static const int dma_env = tuning_int("SM_SPMMA32_DMA", 1);  // tuning aid: 0 = register-staged kernel
   const bool pairs = (a.batch == 1 ? (a.M % 2 == 0) : (m % 2 == 0));
-  if (dma_env && k % 64 == 0 && k >= 64 && pairs && n % 4 == 0 && n >= 4 && strideB % 4 == 0 &&
+  if (k % 64 == 0 && k >= 64 && pairs && n % 4 == 0 && n >= 4 && strideB % 4 == 0 &&
       (reinterpret_cast<uintptr_t>(B) & 15u) == 0) {
-    if (dma_env == 3) return launch_spmma32_dma<128, 2, 4>(a, (hipStream_t)stream);
-    if (dma_env == 5) return launch_spmma32_dma<64, 4, 2>(a, (hipStream_t)stream);
     // 128 x 64 tiles on every shape (two workgroups per CU; the 128 x 128 forms hold one and measured 25-40 % slower)
     return launch_spmma32_dma<64, 4, 1>(a, (hipStream_t)stream);
   }
@@ -992,14 +964,10 @@ int sm_gemm_batched_f64(const double* const* A_ptrs, const double* const* B_ptrs
   a.ta = tb == SM_OP_T; a.tb = ta == SM_OP_T;  // roles swap with the operands
   a.alpha = alpha; a.beta = beta;
   // matrix-core path: whole 16-k stages of 16-byte chunks (even leading dimensions; the pointer arrays live on the
-  // device, their bases are the caller's -- a 16-byte global access needs dword alignment only); SM_GEMM64_DMA=0
-  // (tuning aid) keeps the FMA kernel
-  static const int dma_env = tuning_int("SM_GEMM64_DMA", 1);
-  if (dma_env && !a.ta && !a.tb && a.K % 16 == 0 && a.K >= 16 && a.N % 2 == 0 && a.N >= 2 && a.lda % 2 == 0 && a.ldb % 2 == 0 &&
+  // device, their bases are the caller's -- a 16-byte global access needs dword alignment only)
+  if (!a.ta && !a.tb && a.K % 16 == 0 && a.K >= 16 && a.N % 2 == 0 && a.N >= 2 && a.lda % 2 == 0 && a.ldb % 2 == 0 &&
       ceil_div((size_t)a.M, (size_t)64) <= 65535) {
-    if (dma_env == 2) return launch64_dma<64, 64, 2, 2>(a, batch, (hipStream_t)stream);
-    if (dma_env == 5) return launch64_dma<128, 128, 4, 4>(a, batch, (hipStream_t)stream);
-    // 128 x 128 tiles over 16 waves once they fill 3/4 of the CUs, 64 x 64 otherwise (tools/archive/f64_probe.py under SM_GEMM64_DMA=2..5)
+    // 128 x 128 tiles over 16 waves once they fill 3/4 of the CUs, 64 x 64 otherwise (tools/archive/f64_probe.py)
     const size_t big_tiles = ceil_div((size_t)a.M, (size_t)128) * ceil_div((size_t)a.N, (size_t)128) * batch;
     if (a.M > 64 && a.N > 64 && 4 * big_tiles >= 3 * (size_t)device_cu_count())
       return launch64_dma<128, 128, 4, 4>(a, batch, (hipStream_t)stream);

@@ -717,15 +717,13 @@ static int launch_compress(const void* A, size_t m, size_t k, size_t ld, size_t 
   const size_t items = L.M * (L.kc / 8);
   const size_t nunits = ceil_div(L.M, (size_t)8) * (L.kc / 64);
   if (vec_ok && L.kc == k && ld == k && (batch == 1 || strideA == m * ld) && nunits < 0xfffffff0ull) {
-    static const bool nt = tuning_int("SM_COMPRESS_NT", 1) != 0;
     // two loads per lane (8 units per block) measured best on the ResNet-50 table (1.72 ms against 1.85 with 4,
     // 2.00 with 8, 1.84 with 1: profiles/sweep_r01_i_compress.txt)
     constexpr int NLD = 2;
     const unsigned nstage = (unsigned)(L.kc / 64), grid = (unsigned)ceil_div(nunits, (size_t)(4 * NLD));
     T* v = (T*)blob;
     unsigned char* mt = (unsigned char*)blob + L.meta_off;
-    if (nt) compress_flat_kernel<T, true, NLD><<<grid, 256, 0, st>>>((const T*)A, L.M, k, nstage, (unsigned)nunits, v, mt);
-    else compress_flat_kernel<T, false, NLD><<<grid, 256, 0, st>>>((const T*)A, L.M, k, nstage, (unsigned)nunits, v, mt);
+    compress_flat_kernel<T, true, NLD><<<grid, 256, 0, st>>>((const T*)A, L.M, k, nstage, (unsigned)nunits, v, mt);
     return check_launch("compress_flat_kernel");
   }
   if constexpr (sizeof(T) == 2) {

@@ -45,17 +45,6 @@ int ensure_dyn_lds(LdsOptIn& s, const void* fn, size_t bytes, const char* what);
 // Compute units of the current device, queried once per device ordinal (hipGetDeviceProperties costs tens of
 // microseconds; launchers that size a grid by the CU count call this on every launch).
 int device_cu_count();
-// Tuning hooks of tools/ (SM_* environment variables) exist only in -DSM_TUNING builds; the product library
-// never reads the environment.
-#ifdef SM_TUNING
-inline const char* tuning_env(const char* name) { return getenv(name); }
-#else
-inline const char* tuning_env(const char*) { return nullptr; }
-#endif
-inline int tuning_int(const char* name, int dflt) {
-  const char* v = tuning_env(name);
-  return v ? atoi(v) : dflt;
-}
 
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline size_t ceil_div(size_t x, size_t y) { return (x + y - 1) / y; }
@@ -87,8 +76,7 @@ inline BlobLayout blob_layout(size_t m, size_t k, size_t elt, size_t batch) {
 // operand 176 -> 155 us, 231 MB 85 -> 80; the check, compress, TILE and one-pass kernels do not move, profiles/prune_ab_r05as.txt).
 inline unsigned stream_grid(size_t work_items, unsigned block, bool uncapped = false) {
   size_t g = ceil_div(work_items, block);
-  const size_t cap = (size_t)tuning_int("SM_STREAM_GRID_CAP", uncapped ? 0 : 256 * 16);  // tuning aid (A/B of the cap): 0 = none
-  if (cap && g > cap) g = cap;
+  if (!uncapped && g > 256 * 16) g = 256 * 16;
   if (g > 0x7fffffffull) g = 0x7fffffffull;
   if (g == 0) g = 1;
   return (unsigned)g;

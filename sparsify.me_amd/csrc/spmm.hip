@@ -379,11 +379,9 @@ static int launch_csr_and_fallback(size_t A_num_rows, size_t A_num_cols, size_t 
                                    float alpha, float beta, hipStream_t st, int gate) {
   const size_t count = A_num_rows * B_num_cols * num_batches;
   const size_t nv = B_num_cols * num_batches, col_bytes = A_num_cols * sizeof(float);
-  static const int lds_env = tuning_int("SM_SPMM_LDS", -1);  // tuning aid: 0 = off, 8/16/32 = J
   // as many vectors per workgroup as keep two workgroups on a CU (72 KB each): more FMAs per loaded non-zero
-  int J = col_bytes * 32 <= 72 * 1024 ? 32 : (col_bytes * 16 <= 144 * 1024 ? 16 : 8);
-  if (lds_env == 8 || lds_env == 16 || lds_env == 32) J = lds_env;
-  if (lds_env != 0 && col_bytes * J <= 144 * 1024 && ceil_div(nv, (size_t)J) <= 0x7fffffffull) {
+  const int J = col_bytes * 32 <= 72 * 1024 ? 32 : (col_bytes * 16 <= 144 * 1024 ? 16 : 8);
+  if (col_bytes * J <= 144 * 1024 && ceil_div(nv, (size_t)J) <= 0x7fffffffull) {
     int rc;
     if (J == 32) rc = launch_csr_lds<32>(A_num_rows, A_num_cols, nv, ws, cols, vals, B, C, alpha, beta, st, gate);
     else if (J == 16) rc = launch_csr_lds<16>(A_num_rows, A_num_cols, nv, ws, cols, vals, B, C, alpha, beta, st, gate);
@@ -956,8 +954,7 @@ extern "C" int sm_spmm_coo_fast_form(size_t A_num_rows, size_t A_num_cols, size_
   if (__builtin_mul_overflow(B_num_cols, num_batches, &nv) || nv == 0 || nv > 0x7fffffffull || A_num_rows == 0 ||
       sm_spmm_coo_fast_workspace_size(A_num_rows, A_num_cols, B_num_cols, num_batches, &need) != SM_STATUS_SUCCESS)
     return 0;
-  static const int smfmac_env = sm::tuning_int("SM_COO_SMFMAC", 1);  // (tuning builds only; the product never reads the environment)
-  if (smfmac_env && sm::coo_smfmac_takes(A_num_rows, A_num_cols, A_nnz, nv, nullptr, nullptr, beta)) return 2;
+  if (sm::coo_smfmac_takes(A_num_rows, A_num_cols, A_nnz, nv, nullptr, nullptr, beta)) return 2;
   return A_num_cols != 0 && A_num_cols % 64 == 0 && A_num_rows % 4 == 0 && A_num_rows >= 8 ? 1 : 0;
 }
 
@@ -975,8 +972,7 @@ extern "C" int sm_spmm_coo_f32_fast(size_t A_num_rows, size_t A_num_cols, size_t
   const int rs = sm_spmm_coo_fast_workspace_size(m, k, B_num_cols, num_batches, &need);
   // round 5: beta == 0 and a sparse enough A -> the product on the SPARSE matrix instruction (one prepared 2:4 image of A + the few entries
   // that do not fit it, the dense operand converted in the loader), any k
-  static const int smfmac_env = tuning_int("SM_COO_SMFMAC", 1);  // tuning aid: 0 = always the dense-MFMA pipeline
-  if (rs == SM_STATUS_SUCCESS && workspace_bytes >= need && nv <= 0x7fffffffull && smfmac_env && coo_smfmac_takes(m, k, A_nnz, nv, B, C, beta))
+  if (rs == SM_STATUS_SUCCESS && workspace_bytes >= need && nv <= 0x7fffffffull && coo_smfmac_takes(m, k, A_nnz, nv, B, C, beta))
     return coo_smfmac_product(m, k, A_nnz, nv, rows, cols, vals, B, C, alpha, workspace, (hipStream_t)stream);
   if (rs != SM_STATUS_SUCCESS || k == 0 || k % 64 != 0 || m % 4 != 0 || m < 8 || !aligned16(B) || !aligned16(C) || workspace_bytes < need || nv > 0x7fffffffull) {
     set_error("sm_spmm_coo_f32_fast: needs cols %% 64 == 0 (cols > 0), rows %% 4 == 0, 16-byte aligned B and C and the workspace of sm_spmm_coo_fast_workspace_size "
@@ -1015,13 +1011,10 @@ int sm_spmm_coo_f32_packed(size_t A_num_rows, size_t A_num_cols, size_t A_nnz, s
                            float beta, void* workspace, size_t workspace_bytes, sm_stream_t stream) {
   const PkPlan p = pk_plan(A_num_rows, A_nnz);
   const size_t nv = B_num_cols * num_batches, row_bytes_max = (A_num_cols + 1) * sizeof(float);
-  // as many vectors per workgroup as the slab (columns + a zero row) leaves room for: 32 while two workgroups share a CU
-  int J = row_bytes_max * 32 <= 80 * 1024 ? 32 : (row_bytes_max * 16 <= 160 * 1024 ? 16 : 8);
-  static const int pk_j_env = tuning_int("SM_SPMM_PK_J", 0);  // tuning aid: 8 / 16 / 32 vectors per workgroup
-  const bool forced = pk_j_env == 8 || pk_j_env == 16 || pk_j_env == 32;
-  if (forced) J = pk_j_env;
+  // as many vectors per workgroup as the slab (columns + a zero row) leaves room for: 32 while two workgroups share a CU, else
+  // 16 (8 vectors per workgroup: measured slower than the row-pointer form, 445 vs 339 us)
+  const int J = row_bytes_max * 32 <= 80 * 1024 ? 32 : 16;
   const bool can = workspace && workspace_bytes >= p.total_ints * sizeof(int) && A_nnz > 0 && aligned16(workspace) &&
-                   (J >= 16 || forced) /* 8 vectors per workgroup: measured slower than the row-pointer form (445 vs 339 us) */ &&
                    row_bytes_max * J <= 160 * 1024 && A_nnz + PK_PAD * (A_num_rows + 2) <= 0x7fffffffull &&
                    A_num_rows <= 0x7ffffff0ull && ceil_div(nv, (size_t)J) <= 0x7fffffffull;
   if (!can) {
@@ -1044,10 +1037,8 @@ int sm_spmm_coo_f32_packed(size_t A_num_rows, size_t A_num_cols, size_t A_nnz, s
   pk_pack_kernel<<<(unsigned)ceil_div(A_num_rows, (size_t)4), 256, 0, st>>>(ws, cols, vals, A_num_rows, A_num_cols, (unsigned)(J * sizeof(float)),
                                                                             ws + p.o_prow, reinterpret_cast<u2*>(ws + p.o_ent));
   if (check_launch("sm_spmm_coo_f32_packed: re-ordering") != SM_STATUS_SUCCESS) return SM_STATUS_LAUNCH_FAILED;
-  int rc;
-  if (J == 32) rc = launch_csr_packed<32>(A_num_rows, A_num_cols, nv, ws, p, B, C, alpha, beta, st);
-  else if (J == 16) rc = launch_csr_packed<16>(A_num_rows, A_num_cols, nv, ws, p, B, C, alpha, beta, st);
-  else rc = launch_csr_packed<8>(A_num_rows, A_num_cols, nv, ws, p, B, C, alpha, beta, st);
+  const int rc = J == 32 ? launch_csr_packed<32>(A_num_rows, A_num_cols, nv, ws, p, B, C, alpha, beta, st)
+                         : launch_csr_packed<16>(A_num_rows, A_num_cols, nv, ws, p, B, C, alpha, beta, st);
   if (rc != SM_STATUS_SUCCESS) return rc;
   // rows not sorted (flag odd): the atomic kernels
   scale_if_unsorted_kernel<<<(unsigned)(ceil_div(count, (size_t)256) < 1024 ? ceil_div(count, (size_t)256) : 1024), 256, 0, st>>>(ws, C, count, beta);

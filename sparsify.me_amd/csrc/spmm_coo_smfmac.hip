@@ -35,11 +35,6 @@ namespace sm {
 constexpr int CS_SEG = 64;   // bucket slots per (32 rows x 64 k) block of A
 constexpr int CS_CAP = 4 * CS_SEG;
 constexpr unsigned CS_EMPTY = 0xffffffffu;
-#ifdef SM_TUNING
-#define SM_COO_ABL(bit) ((p.ablate & (bit)) != 0)
-#else
-#define SM_COO_ABL(bit) false
-#endif
 
 struct CooSmArgs {
   const float* A32;       // dense fp32 scatter of A, [m][kc] (zero padded to whole stages)
@@ -53,7 +48,6 @@ struct CooSmArgs {
   int m, k, kc, nst, tiles_m, tiles_nv, slice_w;
   long long nv;
   float alpha;
-  int ablate;  // diagnostic timing builds (-DSM_TUNING, SM_COO_ABLATE): 1 no bucket entries, 2 no loads of B, 4 no SMFMAC; 0 in the product
 };
 
 __global__ __launch_bounds__(256) void coo_scatter_rows_kernel(const int* __restrict__ rows, const int* __restrict__ cols, const float* __restrict__ vals, size_t nnz,
@@ -189,7 +183,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void spmm_coo_smfmac_kernel(const 
   }
   f4 breg[BL];
   auto load_b = [&](int s) {
-    const int kk = SM_COO_ABL(2) ? p.k : s * 64 + 4 * (int)piece;
+    const int kk = s * 64 + 4 * (int)piece;
 #pragma unroll
     for (int i = 0; i < BL; ++i) {
       f4 v = {0.f, 0.f, 0.f, 0.f};
@@ -266,7 +260,6 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void spmm_coo_smfmac_kernel(const 
       load_r(s + 1, cur ^ 1);
     }
     const char* Bs = smem + cur * SB;
-    if (!SM_COO_ABL(4))
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const unsigned col = 16u * j + r16;
@@ -284,7 +277,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void spmm_coo_smfmac_kernel(const 
     //      (entries come out of the prefetched lane registers with v_readlane: no memory access inside the loop)
     {
       const u2 my = rent[cur];
-      const int ne = SM_COO_ABL(1) ? 0 : (int)__builtin_popcountll(__ballot(my[0] != CS_EMPTY));  // the valid slots are a prefix of the segment
+      const int ne = (int)__builtin_popcountll(__ballot(my[0] != CS_EMPTY));  // the valid slots are a prefix of the segment
       for (int e = 0; e < ne; ++e) {
         const unsigned pos = (unsigned)__builtin_amdgcn_readlane((int)my[0], e);
         const int vbits = __builtin_amdgcn_readlane((int)my[1], e);
@@ -385,7 +378,7 @@ __global__ __launch_bounds__(512, 2) void spmm_coo_smfmac_pc_kernel(const CooSmA
     const char* const zero = reinterpret_cast<const char*>(sm_coo_zero_page) + 16u * piece;
     auto dma = [&](int s) {  // always eight instructions (stages past the end and masked lanes read the zero page): vmcnt counts whole stages
       char* dst = stg + (s % RS) * SSTG + pw * 8192u;
-      const bool kin = s < nst && s * 64 + 4 * (int)piece < p.k && !SM_COO_ABL(2);
+      const bool kin = s < nst && s * 64 + 4 * (int)piece < p.k;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const char* src = kin && bsrc[i] ? bsrc[i] + (size_t)s * 256 : zero;
@@ -461,7 +454,6 @@ __global__ __launch_bounds__(512, 2) void spmm_coo_smfmac_pc_kernel(const CooSmA
                    : "+v"(ah[slot][0]), "+v"(ah[slot][1]), "+v"(al[slot][0]), "+v"(al[slot][1]), "+v"(am[slot][0]), "+v"(am[slot][1]), "+v"(re)
                    :: "memory");
       const char* Bs = smem + (s & 1) * SB;
-      if (!SM_COO_ABL(4))
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         const unsigned col = 16u * j + r16;
@@ -477,7 +469,7 @@ __global__ __launch_bounds__(512, 2) void spmm_coo_smfmac_pc_kernel(const CooSmA
       }
       {
         const u2 my = rent[slot];
-        const int ne = SM_COO_ABL(1) ? 0 : (int)__builtin_popcountll(__ballot(my[0] != CS_EMPTY));  // the valid slots are a prefix of the segment
+        const int ne = (int)__builtin_popcountll(__ballot(my[0] != CS_EMPTY));  // the valid slots are a prefix of the segment
         for (int e = 0; e < ne; ++e) {
           const unsigned pos = (unsigned)__builtin_amdgcn_readlane((int)my[0], e);
           const int vbits = __builtin_amdgcn_readlane((int)my[1], e);
@@ -579,9 +571,7 @@ bool coo_smfmac_takes(size_t m, size_t k, size_t nnz, size_t nv, const float* B,
   // L2-to-CU rate, not the matrix pipe, sets the pace (everything but the loads switched off: still 100 of 130 us, coo_ablate_r05al.txt) -- and the pipeline's
   // 256 x 256 tiles on fp16 operands win (3136 x 128 x 1152 106 vs 154, 784 x 256 x 2304 111 vs 148, 12544 x 64 x 576 141 vs 173).
   const bool dense_form_applies = k % 64 == 0 && m >= 8;
-  static const int rule_env = tuning_int("SM_COO_SMFMAC", 1);  // tuning aid: 2 = wherever this form can run (the caller handles 0 = never)
-  if (rule_env != 2 && dense_form_applies && !(nst <= 2 || m <= 256)) return false;
-  return true;
+  return !dense_form_applies || nst <= 2 || m <= 256;
 }
 
 int coo_smfmac_product(size_t m, size_t k, size_t nnz, size_t nv, const int* rows, const int* cols, const float* vals, const float* B, float* C, float alpha,
@@ -601,15 +591,11 @@ int coo_smfmac_product(size_t m, size_t k, size_t nnz, size_t nv, const int* row
   a.nv = (long long)nv;
   a.alpha = alpha;
   {  // column tiles per slice: the slice's part of B (fp32) inside ~2.5 MB of an XCD's 4 MiB L2
-    static const int slice_env = tuning_int("SM_COO_SLICE", 0);
     const size_t tile_b = (size_t)128 * k * 4;
     size_t w = tile_b ? ((size_t)5 << 19) / tile_b : 1;
     w = w < 1 ? 1 : w;
-    if (slice_env > 0) w = (size_t)slice_env;
     a.slice_w = (int)(w > (size_t)a.tiles_nv ? (size_t)a.tiles_nv : w);
   }
-  static const int ablate_env = tuning_int("SM_COO_ABLATE", 0);
-  a.ablate = ablate_env;
   if (hipMemsetAsync(ws, 0, COO_FAST_HDR_BYTES + m * (size_t)a.kc * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");  // header and the scatter target
   coo_fast_scan(vals, nnz, B, nv * k, a.hdr, st);
   if (nnz) coo_scatter_rows_kernel<<<stream_grid(nnz, 256), 256, 0, st>>>(rows, cols, vals, nnz, m, k, (size_t)a.kc, A32);
@@ -618,27 +604,22 @@ int coo_smfmac_product(size_t m, size_t k, size_t nnz, size_t nv, const int* row
   constexpr size_t lds = 128 * (128 * 4 + 16);  // the epilogue image; the two B stages (32 KiB) live inside it
   const unsigned grid = (unsigned)((size_t)a.tiles_m * a.tiles_nv);
   // the producer / consumer kernel (one workgroup per CU) where B is the traffic: few row tiles, several stages; the one-role kernel (two per CU) elsewhere
-  static const int pc_env = tuning_int("SM_COO_PC", 1);  // tuning aid: 0 = the one-role kernel everywhere, 2 = this one wherever k % 4 == 0
-  if (k % 4 == 0 && pc_env && (pc_env == 2 || (a.tiles_m <= 2 && a.nst >= 3))) {
+  if (k % 4 == 0 && a.tiles_m <= 2 && a.nst >= 3) {
     constexpr size_t lds_pc = 2 * 128 * 128 + 3 * 128 * 256;  // two images + the staging ring (the epilogue image fits inside)
     static LdsOptIn lds_optin_pc;
     if (const int rc = ensure_dyn_lds(lds_optin_pc, reinterpret_cast<const void*>(&spmm_coo_smfmac_pc_kernel), lds_pc, "spmm_coo_smfmac_pc_kernel")) return rc;
     spmm_coo_smfmac_pc_kernel<<<grid, 512, lds_pc, st>>>(a);
     return check_launch("spmm_coo_smfmac_pc_kernel");
   }
-  static const int nw_env = tuning_int("SM_COO_WAVES", 4);  // tuning aid: 8 = eight waves of 16 rows (measured the same to 5 % slower on long K, profiles/coo_waves_r05af.txt)
-  static LdsOptIn lds_optin[4];
-#define SM_COO_LAUNCH(I, KV, W)                                                                                                                          \
-  {                                                                                                                                                      \
-    if (const int rc = ensure_dyn_lds(lds_optin[I], reinterpret_cast<const void*>(&spmm_coo_smfmac_kernel<KV, W>), lds, "spmm_coo_smfmac_kernel")) return rc; \
-    spmm_coo_smfmac_kernel<KV, W><<<grid, 64 * W, lds, st>>>(a);                                                                                         \
-  }
-  if (nw_env != 8) {
-    if (k % 4 == 0) SM_COO_LAUNCH(0, true, 4) else SM_COO_LAUNCH(1, false, 4)
+  // (four waves of 32 rows; eight of 16 measured the same to 5 % slower on long K, profiles/coo_waves_r05af.txt)
+  static LdsOptIn lds_optin[2];
+  if (k % 4 == 0) {
+    if (const int rc = ensure_dyn_lds(lds_optin[0], reinterpret_cast<const void*>(&spmm_coo_smfmac_kernel<true, 4>), lds, "spmm_coo_smfmac_kernel")) return rc;
+    spmm_coo_smfmac_kernel<true, 4><<<grid, 256, lds, st>>>(a);
   } else {
-    if (k % 4 == 0) SM_COO_LAUNCH(2, true, 8) else SM_COO_LAUNCH(3, false, 8)
+    if (const int rc = ensure_dyn_lds(lds_optin[1], reinterpret_cast<const void*>(&spmm_coo_smfmac_kernel<false, 4>), lds, "spmm_coo_smfmac_kernel")) return rc;
+    spmm_coo_smfmac_kernel<false, 4><<<grid, 256, lds, st>>>(a);
   }
-#undef SM_COO_LAUNCH
   return check_launch("spmm_coo_smfmac_kernel");
 }
 

@@ -22,11 +22,7 @@ struct SpmmaArgs {
   int batch;          // grid batches (1 when stacked)
   int tiles_m, tiles_n;
   float alpha, beta;
-#ifdef SM_STAMP
-  unsigned long long* dbg;  // diagnostic build only: per-wave cycle sums (never in the product library)
-#endif
 };
-
 
 // The dense twin (spmma_f16_fused.hip): C = alpha * A * B + beta * C, row-major, dense, through the pipelines of the fused 2:4
 // kernels (direct / big / span) with dense MFMA in place of selection + SMFMAC -- so that the dense GEMM the 2:4 path is measured
@@ -39,7 +35,6 @@ struct DenseTwinCall {
   int M, N, K, lda, batch;
   float alpha, beta;
   bool bf;
-  int mode;  // 1: where the rule says the twin wins; 2: wherever it is supported (tuning)
   void* workspace;         // sm_gemm_*_ws: the stream-K form may run (sm_spmma_fused_workspace_size bytes, zero flag page); else null
   size_t workspace_bytes;
 };
@@ -54,17 +49,5 @@ int spmma_fused_thin(bool bf, int ngroup, const void* const* A, const void* cons
 // sm_compress24 + sm_spmma; the thin form is excluded)?  Asked by the prune-in-place + multiply entry points before they touch A.
 bool spmma_fused16_takes_exact(const void* A, const void* B, const void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t strideA, size_t strideB,
                                size_t strideC);
-
-#ifdef SM_STAMP
-__device__ __forceinline__ unsigned long long sm_stamp() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define SM_T(...) __VA_ARGS__
-#else
-#define SM_T(...)
-#endif
-
 
 }  // namespace sm

@@ -10,15 +10,7 @@
 // Global -> registers -> swizzled LDS images (mma_tile.h) with the next stage's loads in flight
 // during the current stage's SMFMACs.  The sparse operand must be srcA, so a lane ends with four
 // consecutive ROWS of one column; the epilogue transposes through LDS and stores 16-byte row pieces.
-#include <stdlib.h>
-
-#include <vector>
-
 #include "spmma_args.h"
-
-#ifndef SM_NT_A
-#define SM_NT_A 0
-#endif
 
 namespace sm {
 
@@ -244,7 +236,6 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const Spmma
   constexpr int SL = (W + NW - 1) / NW;  // slots per wave
   constexpr int LPS = W / NW;            // least DMA instructions any wave issues per stage (vmcnt unit)
   static_assert(LPS >= 1, "every wave must issue at least one DMA per stage");
-  constexpr int NT_A = SM_NT_A;  // cache policy bits of the A-side DMA (2 = nt)
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const unsigned tid = threadIdx.x, lane = tid & 63u;
@@ -312,12 +303,7 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const Spmma
         const unsigned kr = 8u * ((t - (unsigned)(A_N + M_N)) & 7u) + (lane >> 3);
         if (kt * 64 + (int)kr >= p.K) g = (gptr_t*)(sm_zero_page + 16u * (lane & 7u));
       }
-      // A values and metadata are read exactly once (non-temporal: keep them from evicting B, which
-      // every workgroup re-reads from L2); B uses the default policy.
-      if (t < (unsigned)(A_N + M_N))
-        __builtin_amdgcn_global_load_lds(g, l, 16, 0, NT_A);
-      else
-        __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
     }
   };
 
@@ -335,35 +321,22 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const Spmma
   for (int s = 0; s < NS - 1; ++s)
     if (s < nkt) stage(s, s);
   int cur = 0, fill = NS - 1;  // buffer of stage kt, buffer of stage kt+NS-1
-  SM_T(unsigned long long tw = 0, ti = 0, tc = 0; unsigned long long st0 = sm_stamp(); const unsigned long long tstart = st0;)
   for (int kt = 0; kt < nkt; ++kt) {
     const int ahead = (nkt - 1 - kt) < (NS - 2) ? (nkt - 1 - kt) : (NS - 2);
     if (NS >= 4 && ahead == 2) wait_dma_and_barrier<2 * LPS>();
     else if (NS >= 3 && ahead == 1) wait_dma_and_barrier<LPS>();
     else wait_dma_and_barrier<0>();
-    SM_T(unsigned long long st1 = sm_stamp(); tw += st1 - st0;)
     if (kt + NS - 1 < nkt) stage(kt + NS - 1, fill);
-    SM_T(unsigned long long st2 = sm_stamp(); ti += st2 - st1;)
     const char* As = smem + cur * STAGE;
     const char* Ms = As + SA;
     const char* Bs = Ms + SM_;
     smfmac_stage<FM, FN, BF>(As, Ms, Bs, wm * TM, wn * TN, lane, acc);
     cur = cur + 1 == NS ? 0 : cur + 1;
     fill = fill + 1 == NS ? 0 : fill + 1;
-    SM_T(__builtin_amdgcn_sched_barrier(0); st0 = sm_stamp(); tc += st0 - st2;)
   }
   __syncthreads();  // nothing is in flight here: the last NS-1 iterations issued no DMA
-  SM_T(const unsigned long long tloop = sm_stamp();)
 
   store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
-#ifdef SM_STAMP
-  if (p.dbg && lane == 0) {
-    const unsigned long long tend = sm_stamp();
-    unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8;
-    d[0] = tw; d[1] = ti; d[2] = tc; d[3] = tloop - tstart; d[4] = tend - tloop; d[5] = tstart; d[6] = tend;
-    d[7] = __builtin_amdgcn_s_getreg(GETREG_IMMED(4 - 1, 0, 20 /*HW_REG_XCC_ID*/));
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -464,11 +437,6 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const
           const unsigned kr = 8u * ((t - (unsigned)(A_N + M_N)) & 7u) + (lane >> 3);
           if (kt * 64 + (int)kr >= p.K) gp = (gptr_t*)(sm_zero_page + 16u * (lane & 7u));
         }
-#ifdef SM_ABLATE  /* diagnostic timing builds only: 1 = no metadata DMA, 2 = no A DMA, 4 = no B DMA */
-        if ((SM_ABLATE & 1) && t >= (unsigned)A_N && t < (unsigned)(A_N + M_N)) continue;
-        if ((SM_ABLATE & 2) && t < (unsigned)A_N) continue;
-        if ((SM_ABLATE & 4) && t >= (unsigned)(A_N + M_N)) continue;
-#endif
         __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
       }
     };
@@ -476,43 +444,27 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const
     for (int s = 0; s < NS - 1; ++s)
       if (s < nkt) stage(s, s);
     int fill = NS - 1;
-    SM_T(unsigned long long tw = 0, tb = 0, ti = 0; unsigned long long s0 = sm_stamp();)
     for (int kt = 0; kt < nkt; ++kt) {
       const int ahead = (nkt - 1 - kt) < (NS - 2) ? (nkt - 1 - kt) : (NS - 2);
-#ifdef SM_STAMP
-      if (NS >= 4 && ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPS) : "memory");
-      else if (NS >= 3 && ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      unsigned long long s1 = sm_stamp(); tw += s1 - s0;
-      asm volatile("s_barrier" ::: "memory");
-      unsigned long long s2 = sm_stamp(); tb += s2 - s1;
-#else
       if (NS >= 6 && ahead == 4) wait_dma_and_barrier<4 * LPS>();
       else if (NS >= 5 && ahead == 3) wait_dma_and_barrier<3 * LPS>();
       else if (NS >= 4 && ahead == 2) wait_dma_and_barrier<2 * LPS>();
       else if (NS >= 3 && ahead == 1) wait_dma_and_barrier<LPS>();
       else wait_dma_and_barrier<0>();
-#endif
       if (kt + NS - 1 < nkt) stage(kt + NS - 1, fill);
       fill = fill + 1 == NS ? 0 : fill + 1;
-      SM_T(s0 = sm_stamp(); ti += s0 - s2;)
     }
-    SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8; d[0] = tw; d[1] = tb; d[2] = ti; d[3] = 1; })
   } else {
     // ------------------------------------------------------------------ consumer wave
     int cur = 0;
-    SM_T(unsigned long long tb = 0, tc = 0; unsigned long long s0 = sm_stamp();)
     for (int kt = 0; kt < nkt; ++kt) {
       wait_dma_and_barrier<0>();  // a consumer has no DMA of its own: this is the stage barrier
-      SM_T(unsigned long long s1 = sm_stamp(); tb += s1 - s0;)
       const char* As = smem + cur * STAGE;
       const char* Ms = As + SA;
       const char* Bs = Ms + SM_;
       smfmac_stage<FM, FN, BF>(As, Ms, Bs, wm * TM, wn * TN, lane, acc);
       cur = cur + 1 == NS ? 0 : cur + 1;
-      SM_T(__builtin_amdgcn_sched_barrier(0); s0 = sm_stamp(); tc += s0 - s1;)
     }
-    SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8; d[0] = 0; d[1] = tb; d[2] = tc; d[3] = 0; })
   }
   __syncthreads();  // both roles; nothing is in flight (the last NS-1 loader iterations issued no DMA)
 
@@ -546,30 +498,6 @@ static int launch_pc(const SpmmaArgs& a0, hipStream_t st) {
   if (lds > 64 * 1024) {
     if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF>), lds, "spmma_f16_pc_kernel")) return rc;
   }
-#ifdef SM_STAMP
-  {
-    static unsigned long long* dbg = nullptr;
-    constexpr int NWV = WM * WN + NL;
-    const size_t cnt = nwg * (size_t)NWV * 8;
-    static size_t cap = 0;
-    if (cnt > cap) { if (dbg) (void)hipFree(dbg); (void)hipMalloc((void**)&dbg, cnt * 8); cap = cnt; }
-    a.dbg = dbg;
-    spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF><<<dim3((unsigned)nwg), dim3(64 * NWV), lds_launch, st>>>(a);
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(cnt);
-    (void)hipMemcpy(h.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-    double L[3] = {0, 0, 0}, Cn[2] = {0, 0};
-    double nl = 0, nc = 0;
-    for (size_t i = 0; i < cnt / 8; ++i) {
-      if (h[i * 8 + 3] == 1) { L[0] += h[i * 8]; L[1] += h[i * 8 + 1]; L[2] += h[i * 8 + 2]; nl += 1; }
-      else { Cn[0] += h[i * 8 + 1]; Cn[1] += h[i * 8 + 2]; nc += 1; }
-    }
-    const double nk = (double)(a.kc / 64);
-    fprintf(stderr, "STAMP-PC %dx%dx%d NL=%d NS=%d tiles=%zu nkt=%d | loader per stage: vmcnt-wait %.0f barrier %.0f issue %.0f | consumer per stage: barrier %.0f compute %.0f\n",
-            a.Mrows, a.N, a.K, NL, NS, nwg, a.kc / 64, L[0] / nl / nk, L[1] / nl / nk, L[2] / nl / nk, Cn[0] / nc / nk, Cn[1] / nc / nk);
-    return check_launch("spmma_f16_pc_kernel");
-  }
-#endif
   spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + NL)), lds_launch, st>>>(a);
   return check_launch("spmma_f16_pc_kernel");
 }
@@ -595,31 +523,6 @@ static int launch_dma(const SpmmaArgs& a0, hipStream_t st) {
   if (lds > 64 * 1024) {
     if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF>), lds, "spmma_f16_dma_kernel")) return rc;
   }
-#ifdef SM_STAMP
-  {
-    static unsigned long long* dbg = nullptr;
-    const size_t cnt = nwg * (size_t)(WM * WN) * 8;
-    static size_t cap = 0;
-    if (cnt > cap) { if (dbg) (void)hipFree(dbg); (void)hipMalloc((void**)&dbg, cnt * 8); cap = cnt; }
-    a.dbg = dbg;
-    spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds_launch, st>>>(a);
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(cnt);
-    (void)hipMemcpy(h.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-    double s[5] = {0, 0, 0, 0, 0};
-    unsigned long long t_min = ~0ull, t_max = 0;
-    for (size_t i = 0; i < cnt / 8; ++i) {
-      for (int j = 0; j < 5; ++j) s[j] += (double)h[i * 8 + j];
-      if (h[i * 8 + 5] < t_min) t_min = h[i * 8 + 5];
-      if (h[i * 8 + 6] > t_max) t_max = h[i * 8 + 6];
-    }
-    const double nwv = (double)(cnt / 8), nk = (double)(a.kc / 64);
-    fprintf(stderr, "STAMP %dx%dx%d nw=%d ns=%d tiles=%zu nkt=%d | per wave per stage: wait %.0f issue %.0f compute %.0f | loop %.0f epilogue %.0f cycles | kernel span %.0f cycles (100MHz ticks? no: shader clk)\n",
-            a.Mrows, a.N, a.K, WM * WN, NS, nwg, a.kc / 64, s[0] / nwv / nk, s[1] / nwv / nk, s[2] / nwv / nk, s[3] / nwv, s[4] / nwv,
-            (double)(t_max - t_min));
-    return check_launch("spmma_f16_dma_kernel");
-  }
-#endif
   spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds_launch, st>>>(a);
   return check_launch("spmma_f16_dma_kernel");
 }
@@ -694,66 +597,22 @@ static int spmma16(size_t ng, const void* const* blobs, const void* const* Bs, v
   if (fast) {
     // Workgroup shape by how many tiles exist: with thousands of tiles 4 waves per tile and several
     // tiles per CU overlap each other's latencies; with about one tile per CU the same tile is spread
-    // over 8 or 16 waves so that every SIMD still holds several waves.  SM_SPMMA_CFG (tuning aid):
-    // "<waves>x<ring>" forces a configuration.
+    // over 8 or 16 waves so that every SIMD still holds several waves.
     // 256 x 128 tiles (B lines amortised over twice the rows) pay with a long K and enough rows for >= 64 such
     // tiles per n-tile (profiles/sweep_r01_*.txt: 784x256x{1024,2304}, 3136x128x1152 at b=32)
-    if (!tuning_env("SM_SPMMA_PC") && !tuning_env("SM_SPMMA_CFG") && n >= 128 && n <= 256 && k >= 1024 &&
-        (size_t)a.Mrows * ng >= 16384)
-      return launch_pc<256, 128, 4, 2, 4, 3, BF>(a, st);
-#ifdef SM_TUNING
-    {  // A/B: 256 x 256 tiles, eight waves of 32 rows x 256 columns, all waves issue the DMA (ring of 3 / 2): SM_SPMMA_BIG = 3 / 2
-      const int big = tuning_int("SM_SPMMA_BIG", 0);
-      if (big && n > 128 && k > 64) return big == 2 ? launch_dma<256, 256, 8, 1, 2, BF>(a, st) : launch_dma<256, 256, 8, 1, 3, BF>(a, st);
-    }
-#endif
-    static const char* pc_env = tuning_env("SM_SPMMA_PC");  // tuning aid: "<loaders>x<ring>", "0" = previous kernel
-    // default: long K -> producer/consumer kernel (4 loader waves, ring of 3); short K -> the kernel
-    // above with more tiles per CU (measured per shape on the ResNet tables, profiles/sweep_r01_*.txt)
+    if (n >= 128 && n <= 256 && k >= 1024 && (size_t)a.Mrows * ng >= 16384) return launch_pc<256, 128, 4, 2, 4, 3, BF>(a, st);
+    // long K -> producer/consumer kernel (4 loader waves, ring of 3); short K -> the kernel below with more tiles per CU
+    // (measured per shape on the ResNet tables, profiles/sweep_r01_*.txt)
     // (n <= 64 is HBM-bound at every K: the plain DMA kernel with more tiles per CU wins there)
-    int nl = (k >= 512 && n > 64) ? 4 : 0, pns = 3;
-    if (pc_env) sscanf(pc_env, "%dx%d", &nl, &pns);
-    if (nl == 256 && n > 64) {  // tuning aid: 256 x 128 tiles, 8 consumer waves (64 x 64) + 4 loaders, 64-deep stages
-      return pns >= 4 ? launch_pc<256, 128, 4, 2, 4, 4, BF>(a, st) : (pns == 3 ? launch_pc<256, 128, 4, 2, 4, 3, BF>(a, st) : launch_pc<256, 128, 4, 2, 4, 2, BF>(a, st));
-    }
-#ifdef SM_TUNING
-    if (pc_env && n > 64) {  // deep rings / more loaders / 8 consumer waves on 128 x 128 tiles: "<nl>x<ns>x<c>", c = 4 or 8 consumers
-      int cw = 4;
-      sscanf(pc_env, "%*dx%*dx%d", &cw);
-      if (cw == 8) {
-        if (nl == 8) return pns >= 5 ? launch_pc<128, 128, 2, 4, 8, 5, BF>(a, st) : (pns == 4 ? launch_pc<128, 128, 2, 4, 8, 4, BF>(a, st) : launch_pc<128, 128, 2, 4, 8, 3, BF>(a, st));
-        return pns >= 5 ? launch_pc<128, 128, 2, 4, 4, 5, BF>(a, st) : (pns == 4 ? launch_pc<128, 128, 2, 4, 4, 4, BF>(a, st) : launch_pc<128, 128, 2, 4, 4, 3, BF>(a, st));
-      }
-      if (nl == 8) return pns >= 6 ? launch_pc<128, 128, 2, 2, 8, 6, BF>(a, st) : (pns == 5 ? launch_pc<128, 128, 2, 2, 8, 5, BF>(a, st) : (pns == 4 ? launch_pc<128, 128, 2, 2, 8, 4, BF>(a, st) : launch_pc<128, 128, 2, 2, 8, 3, BF>(a, st)));
-      if (nl == 4 && pns >= 5) return pns >= 6 ? launch_pc<128, 128, 2, 2, 4, 6, BF>(a, st) : launch_pc<128, 128, 2, 2, 4, 5, BF>(a, st);
-    }
-#endif
-    if (nl > 0) {
-      if (n <= 64) {
-        if (nl == 2) return pns >= 3 ? launch_pc<128, 64, 4, 1, 2, 3, BF>(a, st) : launch_pc<128, 64, 4, 1, 2, 2, BF>(a, st);
-        return pns >= 4 ? launch_pc<128, 64, 4, 1, 4, 4, BF>(a, st) : (pns == 3 ? launch_pc<128, 64, 4, 1, 4, 3, BF>(a, st) : launch_pc<128, 64, 4, 1, 4, 2, BF>(a, st));
-      }
-      if (nl == 2) return pns >= 3 ? launch_pc<128, 128, 2, 2, 2, 3, BF>(a, st) : launch_pc<128, 128, 2, 2, 2, 2, BF>(a, st);
-      return pns >= 4 ? launch_pc<128, 128, 2, 2, 4, 4, BF>(a, st) : (pns == 3 ? launch_pc<128, 128, 2, 2, 4, 3, BF>(a, st) : launch_pc<128, 128, 2, 2, 4, 2, BF>(a, st));
-    }
-    static const char* cfg_env = tuning_env("SM_SPMMA_CFG");
+    if (k >= 512 && n > 64) return launch_pc<128, 128, 2, 2, 4, 3, BF>(a, st);
     const size_t Mr = (size_t)a.Mrows;
-    int nw, ns;
     if (n <= 64) {
       const size_t tiles = ceil_div(Mr, 128) * a.batch * ng;
-      nw = tiles >= 1024 ? 4 : 8;
-      ns = 2;
-      if (cfg_env) sscanf(cfg_env, "%dx%d", &nw, &ns);
-      if (nw >= 8) return ns >= 3 ? launch_dma<128, 64, 4, 2, 3, BF>(a, st) : launch_dma<128, 64, 4, 2, 2, BF>(a, st);
-      return ns >= 3 ? launch_dma<128, 64, 4, 1, 3, BF>(a, st) : launch_dma<128, 64, 4, 1, 2, BF>(a, st);
+      return tiles >= 1024 ? launch_dma<128, 64, 4, 1, 2, BF>(a, st) : launch_dma<128, 64, 4, 2, 2, BF>(a, st);
     }
     const size_t tiles = ceil_div(Mr, 128) * ceil_div(n, 128) * a.batch * ng;
-    nw = tiles >= 1024 ? 4 : (tiles >= 512 ? 8 : 16);
-    ns = (tiles < 512 && k >= 1024) ? 3 : 2;
-    if (cfg_env) sscanf(cfg_env, "%dx%d", &nw, &ns);
-    if (nw >= 16) return ns >= 3 ? launch_dma<128, 128, 4, 4, 3, BF>(a, st) : launch_dma<128, 128, 4, 4, 2, BF>(a, st);
-    if (nw >= 8) return ns >= 3 ? launch_dma<128, 128, 2, 4, 3, BF>(a, st) : launch_dma<128, 128, 2, 4, 2, BF>(a, st);
-    return ns >= 3 ? launch_dma<128, 128, 2, 2, 3, BF>(a, st) : launch_dma<128, 128, 2, 2, 2, BF>(a, st);
+    if (tiles >= 1024) return launch_dma<128, 128, 2, 2, 2, BF>(a, st);
+    return tiles >= 512 ? launch_dma<128, 128, 2, 4, 2, BF>(a, st) : launch_dma<128, 128, 4, 4, 2, BF>(a, st);
   }
   if (n <= 64) return launch_cfg<128, 64, 4, 1, BF>(a, st);
   return launch_cfg<128, 128, 2, 2, BF>(a, st);

@@ -16,9 +16,6 @@
 //   consumer waves: unchanged (ds_read_b128 + ds_read_u16 + ds_read_b64_tr_b16 + v_smfmac).
 // The result is bit-identical to sm_spmma_f16(sm_compress24_f16(A), B): same kept values, same codes, same
 // instruction sequence on the same operands (tests/test_gpu_parity.py::test_fused_equals_staged).
-#include <cstdio>
-#include <vector>
-
 #include "select24.h"
 #include "spmma_args.h"
 
@@ -41,12 +38,6 @@ struct FusedArgs {
   const half_t* const* dAp;
   const half_t* const* dBp;
   half_t* const* dCp;
-#ifdef SM_STAMP
-  unsigned long long* dbg;  // diagnostic build only: per-wave cycle sums (never in the product library)
-#endif
-#ifdef SM_TUNING
-  int ablate;  // tuning builds only (direct kernel): 1 = no C store, 2 = no stage compute, 4 = no A / B loads (timing only: C is wrong)
-#endif
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -59,15 +50,9 @@ struct FusedArgs {
 // (round 5) the 128-column form is asked to fit four waves per SIMD (<= 128 registers; left alone it takes 129 = three): a single-stage
 // problem (k = 64) allocates 34 KiB of LDS, so a fourth workgroup then shares the CU -- with no K loop to pipeline, the workgroups
 // per CU are all that overlaps one tile's load latency with another's stores (12544 x 256 x 64)
-// (measured indifferent: profiles/direct_ablate_occ4_r05p.txt -- kept, it costs nothing.  Tuning builds, whose ablation switches push the kernel past 128 registers,
-// keep the default bound: with the hint they spill 204 bytes per lane and run 3 x slower, profiles/ab_bm192_r05s.txt)
-#ifdef SM_TUNING
-#define SM_DIRECT_MIN_WAVES(BN, NWV, BM) 1
-#else
-#define SM_DIRECT_MIN_WAVES(BN, NWV, BM) (((BN) == 128 && (NWV) == 4 && (BM) == 128) ? 4 : 1)
-#endif
+// (measured indifferent: profiles/direct_ablate_occ4_r05p.txt -- kept, it costs nothing)
 template <int BN, int NS, bool BF = false, int BM = 128, int NWV = 4, bool ANT = true, bool DENSE = false>
-__global__ __launch_bounds__(64 * NWV, SM_DIRECT_MIN_WAVES(BN, NWV, BM)) void spmma_f16_fused_direct_kernel(const FusedArgs p) {
+__global__ __launch_bounds__(64 * NWV, (BN == 128 && NWV == 4 && BM == 128) ? 4 : 1) void spmma_f16_fused_direct_kernel(const FusedArgs p) {
   static_assert(BM == 128 || BM == 64, "row tile");
   static_assert(NWV == 4 || (NWV == 8 && BM == 128), "waves per workgroup");
   constexpr int NW = NWV, TM = BM / NW, FM = TM / 16, FN = BN / 16;
@@ -80,11 +65,7 @@ __global__ __launch_bounds__(64 * NWV, SM_DIRECT_MIN_WAVES(BN, NWV, BM)) void sp
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned tiles = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
-#ifdef SM_TUNING
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, !(p.ablate & 16));  // (tuning: SM_DIRECT_ABLATE bit 4 = the XCD ranges of rounds 1-4)
-#else
   const unsigned lid = tile_order(blockIdx.x, gridDim.x, true);  // dispatch order: mma_tile.h
-#endif
   const unsigned gb = lid / tiles, trem = lid - gb * tiles;
   const unsigned grp = gb / (unsigned)p.batch, b = gb - grp * (unsigned)p.batch;
   const unsigned tile_m = trem / (unsigned)p.tiles_n, tile_n = trem - tile_m * (unsigned)p.tiles_n;
@@ -94,7 +75,7 @@ __global__ __launch_bounds__(64 * NWV, SM_DIRECT_MIN_WAVES(BN, NWV, BM)) void sp
   const half_t* B = p.dBp ? p.dBp[gb] : p.B[grp] + (size_t)b * p.sB;
   half_t* C = p.dCp ? p.dCp[gb] : p.C[grp] + (size_t)b * p.sC;
   const int mlast = p.Mrows - 1;
-  // (Round 5: the ablation of this kernel -- tools/direct_ablate.py, profiles/direct_ablate_r05n.txt -- reads "whole launch = launch without
+  // (Round 5: the ablation of this kernel -- profiles/direct_ablate_r05n.txt -- reads "whole launch = launch without
   //  the C store + the C store alone" on every shape (12544 x 256 x 64 x 3: 220 = 105 + 113 us): loads and stores do not overlap.  Starting the
   //  workgroups that share a CU a third of a tile's lifetime apart, so that one stores while the others load, changed nothing
   //  (profiles/direct_stagger_r05o.txt): it is not a phase alignment of the resident workgroups.  Removed again.)
@@ -124,9 +105,6 @@ __global__ __launch_bounds__(64 * NWV, SM_DIRECT_MIN_WAVES(BN, NWV, BM)) void sp
   }
   auto stage = [&](int kt, int buf) {
     char* base = smem + buf * STAGE;
-#ifdef SM_TUNING
-    if (p.ablate & 4) return;
-#endif
     // A is read exactly once by the whole grid: its DMA carries the non-temporal hint (aux = 2, `nt`); B is re-read by
     // every row tile and keeps the default policy.  Instruction i of a wave is an A piece iff NW * i < A_N (A_N % NW == 0).
     static_assert(A_N % NW == 0, "A / B split of the DMA instructions is per instruction index");
@@ -149,55 +127,25 @@ __global__ __launch_bounds__(64 * NWV, SM_DIRECT_MIN_WAVES(BN, NWV, BM)) void sp
   for (int s = 0; s < NS - 1; ++s)
     if (s < nkt) stage(s, s);
   int cur = 0, fill = NS - 1;
-  SM_T(unsigned long long tv = 0, tb = 0, ti = 0, tc = 0; unsigned long long s0 = sm_stamp(); const unsigned long long sstart = s0;)
   for (int kt = 0; kt < nkt; ++kt) {
     const int ahead = (nkt - 1 - kt) < (NS - 2) ? (nkt - 1 - kt) : (NS - 2);
-#ifdef SM_STAMP
-    if (NS >= 4 && ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SL) : "memory");
-    else if (NS >= 3 && ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SL) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long sv = sm_stamp(); tv += sv - s0;
-    asm volatile("s_barrier" ::: "memory");
-    const unsigned long long sb = sm_stamp(); tb += sb - sv;
-#else
     if (NS >= 4 && ahead == 2) wait_dma_and_barrier<2 * SL>();
     else if (NS >= 3 && ahead == 1) wait_dma_and_barrier<SL>();
     else wait_dma_and_barrier<0>();
-#endif
     if (kt + NS - 1 < nkt) stage(kt + NS - 1, fill);
-    SM_T(const unsigned long long si = sm_stamp(); ti += si - sb;)
     const char* As = smem + cur * STAGE;
-#ifdef SM_TUNING
-    if (!(p.ablate & 2)) {
-#endif
     if constexpr (DENSE) mfma_stage_dense_a<FM, FN, BF>(As, As + SA, wave * TM, 0, lane, acc);  // the dense twin: every element multiplied
     else smfmac_stage_dense_a<FM, FN, BF>(As, As + SA, wave * TM, 0, lane, acc);
-#ifdef SM_TUNING
-    }
-#endif
     cur = cur + 1 == NS ? 0 : cur + 1;
     fill = fill + 1 == NS ? 0 : fill + 1;
-    SM_T(__builtin_amdgcn_sched_barrier(0); s0 = sm_stamp(); tc += s0 - si;)
   }
   __syncthreads();
-  SM_T(const unsigned long long sloop = sm_stamp();)
-#ifdef SM_TUNING
-  if (p.ablate & 1) {  // no C store: one element per workgroup keeps the accumulators alive
-    if (tid == 0) C[(size_t)m0 * p.N + n0] = to_elt<BF>(acc[0][0][0] + acc[FM - 1][FN - 1][3]);
-    return;
-  }
-#endif
   store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
-  SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8; const unsigned long long se = sm_stamp();
-        d[0] = tv; d[1] = tb; d[2] = ti; d[3] = tc; d[4] = sloop - sstart; d[5] = se - sloop; })
 }
 
 template <int BN, int NS, bool BF = false, int BM = 128, int NWV = 4, bool ANT = true, bool DENSE = false>
 static int launch_fused_direct(const FusedArgs& a0, hipStream_t st) {
   FusedArgs a = a0;
-#ifdef SM_TUNING
-  a.ablate = tuning_int("SM_DIRECT_ABLATE", 0);
-#endif
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -217,27 +165,6 @@ static int launch_fused_direct(const FusedArgs& a0, hipStream_t st) {
   if (lds_max > 64 * 1024) {
     if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE>), lds_max, "spmma_f16_fused_direct_kernel")) return rc;
   }
-#ifdef SM_STAMP
-  {
-    static unsigned long long* dbg = nullptr;
-    static size_t cap = 0;
-    const size_t cnt = nwg * NWV * 8;
-    if (cnt > cap) { if (dbg) (void)hipFree(dbg); (void)hipMalloc((void**)&dbg, cnt * 8); cap = cnt; }
-    (void)hipMemset(dbg, 0, cnt * 8);
-    a.dbg = dbg;
-    spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE><<<dim3((unsigned)nwg), dim3(64 * NWV), lds, st>>>(a);
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(cnt);
-    (void)hipMemcpy(h.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-    double t[6] = {0, 0, 0, 0, 0, 0};
-    for (size_t i = 0; i < cnt / 8; ++i)
-      for (int j = 0; j < 6; ++j) t[j] += (double)h[i * 8 + j];
-    const double nwv = (double)(cnt / 8), nk = (double)(a.K / 64);
-    fprintf(stderr, "STAMP-FUSED-DIRECT %dx%dx%d NS=%d tiles=%zu nkt=%d | per wave per stage: vmcnt-wait %.0f barrier %.0f dma-issue %.0f compute %.0f | loop %.0f epilogue %.0f cycles per tile\n",
-            a.Mrows, a.N, a.K, NS, nwg, a.K / 64, t[0] / nwv / nk, t[1] / nwv / nk, t[2] / nwv / nk, t[3] / nwv / nk, t[4] / nwv, t[5] / nwv);
-    return check_launch("spmma_f16_fused_direct_kernel");
-  }
-#endif
   spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE><<<dim3((unsigned)nwg), dim3(64 * NWV), lds, st>>>(a);
   return check_launch("spmma_f16_fused_direct_kernel");
 }
@@ -280,11 +207,7 @@ __global__ __launch_bounds__(512) void spmma_f16_fused_big_kernel(const FusedArg
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned tiles = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
-#ifdef SM_TUNING
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, (p.ablate & 8) != 0);  // (tuning: SM_DIRECT_ABLATE bit 3 = dispatch order; measured 0-5 % slower here, mma_tile.h)
-#else
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
-#endif
   const unsigned gb = lid / tiles, trem = lid - gb * tiles;
   const unsigned grp = gb / (unsigned)p.batch, b = gb - grp * (unsigned)p.batch;
   const unsigned tile_m = trem / (unsigned)p.tiles_n, tile_n = trem - tile_m * (unsigned)p.tiles_n;
@@ -343,66 +266,26 @@ __global__ __launch_bounds__(512) void spmma_f16_fused_big_kernel(const FusedArg
     if (j + NSA - 1 < nkt) stage_a(j + NSA - 1, j + NSA - 1);
   }
   int ca = 0, cb = 0, fa = NSA - 1, fb = NSB - 1;  // current / next-to-fill slots of the two rings
-  SM_T(unsigned long long tv = 0, tb = 0, ti = 0, ts = 0, tc = 0; unsigned long long s0 = sm_stamp(); const unsigned long long sstart = s0;)
   for (int kt = 0; kt < nkt; ++kt) {
-#ifdef SM_STAMP
-    if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AHEAD) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long sv = sm_stamp(); tv += sv - s0;
-    asm volatile("s_barrier" ::: "memory");
-    const unsigned long long sb = sm_stamp(); tb += sb - sv;
-#else
     if (kt + 1 < nkt) wait_dma_and_barrier<AHEAD>();
     else wait_dma_and_barrier<0>();
-#endif
     if (kt + NSB - 1 < nkt) stage_b(kt + NSB - 1, fb);  // the slots stage kt - 1 occupied: every wave left them before this barrier
     if (kt + NSA - 1 < nkt) stage_a(kt + NSA - 1, fa);
-#ifdef SM_STAMP
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long si = sm_stamp(); ti += si - sb;
-    {
-      const unsigned g = lane >> 4, r = lane & 15u;
-      const char* Araw = smem + ca * SA;
-      h8 af[FM];
-      int idx[FM];
-#pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        const unsigned row = wave * TM + i * 16 + r;
-        const u4 lo = *reinterpret_cast<const u4*>(Araw + a_off(row, 2u * g));
-        const u4 hi = *reinterpret_cast<const u4*>(Araw + a_off(row, 2u * g + 1u));
-        dense16_to_operand(lo, hi, af[i], idx[i]);
-      }
-#pragma unroll
-      for (int i = 0; i < FM; ++i) asm volatile("" : "+v"(af[i]), "+v"(idx[i]));
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long ss = sm_stamp(); ts += ss - si;
-      smfmac_b_sweep<FM, FN, BF>(af, idx, smem + BRING + cb * SB, 0, lane, acc);
-      __builtin_amdgcn_sched_barrier(0);
-      s0 = sm_stamp(); tc += s0 - ss;
-    }
-#else
     if constexpr (DENSE) mfma_stage_dense_a<FM, FN, BF>(smem + ca * SA, smem + BRING + cb * SB, wave * TM, 0, lane, acc);
     else smfmac_stage_dense_a<FM, FN, BF>(smem + ca * SA, smem + BRING + cb * SB, wave * TM, 0, lane, acc);
-#endif
     ca = ca + 1 == NSA ? 0 : ca + 1;
     fa = fa + 1 == NSA ? 0 : fa + 1;
     cb = cb + 1 == NSB ? 0 : cb + 1;
     fb = fb + 1 == NSB ? 0 : fb + 1;
   }
   __syncthreads();
-  SM_T(const unsigned long long sloop = sm_stamp();)
   store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
-  SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8; const unsigned long long se = sm_stamp();
-        d[0] = tv; d[1] = tb; d[2] = ti; d[3] = ts; d[4] = tc; d[5] = sloop - sstart; d[6] = se - sloop; })
 }
 
 template <int BN, bool BF = false, int NSA = 3, int NSB = 2, bool ANT = true, bool DENSE = false>
 static int launch_fused_big(const FusedArgs& a0, hipStream_t st) {
   constexpr int BM = 256;
   FusedArgs a = a0;
-#ifdef SM_TUNING
-  if (!a.ablate) a.ablate = tuning_int("SM_DIRECT_ABLATE", 0) & 24;
-#endif
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -417,27 +300,6 @@ static int launch_fused_big(const FusedArgs& a0, hipStream_t st) {
   static_assert(lds <= 160 * 1024, "LDS budget of the big direct kernel");
   static LdsOptIn lds_optin;
   if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE>), lds, "spmma_f16_fused_big_kernel")) return rc;
-#ifdef SM_STAMP
-  {
-    static unsigned long long* dbg = nullptr;
-    static size_t cap = 0;
-    const size_t cnt = nwg * 8 * 8;
-    if (cnt > cap) { if (dbg) (void)hipFree(dbg); (void)hipMalloc((void**)&dbg, cnt * 8); cap = cnt; }
-    (void)hipMemset(dbg, 0, cnt * 8);
-    a.dbg = dbg;
-    spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a);
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(cnt);
-    (void)hipMemcpy(h.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-    double t[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (size_t i = 0; i < cnt / 8; ++i)
-      for (int j = 0; j < 7; ++j) t[j] += (double)h[i * 8 + j];
-    const double nwv = (double)(cnt / 8), nk = (double)(a.K / 64);
-    fprintf(stderr, "STAMP-FUSED-BIG %dx%dx%d BN=%d NSA=%d NSB=%d tiles=%zu nkt=%d | per wave per stage: vmcnt-wait %.0f barrier %.0f dma-issue %.0f select %.0f b-sweep %.0f | loop %.0f epilogue %.0f cycles per tile\n",
-            a.Mrows, a.N, a.K, BN, NSA, NSB, nwg, a.K / 64, t[0] / nwv / nk, t[1] / nwv / nk, t[2] / nwv / nk, t[3] / nwv / nk, t[4] / nwv / nk, t[5] / nwv, t[6] / nwv);
-    return check_launch("spmma_f16_fused_big_kernel");
-  }
-#endif
   spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a);
   return check_launch("spmma_f16_fused_big_kernel");
 }
@@ -496,9 +358,6 @@ struct SkArgs {
   // tg * nkt); the last group: tgl panels, wgl slots, cutl[]
   unsigned panels, slots, tg, wg, groups_full, tgl, wgl;
   unsigned cut[9], cutl[9];
-#ifdef SM_TUNING
-  int ablate;              // tuning builds only: 1 = no partial stores, 2 = no fix-up loads / waits (results wrong; timing only)
-#endif
 };
 // entry r of a 9-entry table held in the kernel arguments, by compares (a runtime index into a by-value argument array would
 // send the whole block through scratch memory)
@@ -538,11 +397,7 @@ __global__ __launch_bounds__(512) void spmma_f16_fused_sk_kernel(const FusedArgs
 
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef SM_TUNING
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, (p.ablate & 8) != 0);  // (tuning: SM_DIRECT_ABLATE bit 3 = dispatch order; measured 0-5 % slower here, mma_tile.h)
-#else
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
-#endif
   const unsigned tn = (unsigned)p.tiles_n;
   const unsigned slot = lid / tn, tile_n = lid - slot * tn;  // the tiles_n workgroups of a slot are neighbours: one XCD, one A stream
   const unsigned nkt = (unsigned)(p.K / 64);
@@ -653,9 +508,6 @@ __global__ __launch_bounds__(512) void spmma_f16_fused_sk_kernel(const FusedArgs
       float* dst = s.part + (size_t)lid * slot_floats + lane_off;
       asm volatile("" : "+v"(dst));  // (keeps the 32 store addresses from being computed ahead of the segment loop and spilled)
       bool publish = true;
-#ifdef SM_TUNING
-      publish = !(s.ablate & 1);
-#endif
       if (publish) {
 #pragma unroll
         for (int i = 0; i < FM; ++i)
@@ -674,9 +526,6 @@ __global__ __launch_bounds__(512) void spmma_f16_fused_sk_kernel(const FusedArgs
         // ---- the tile's first stages, and others hold the rest: add their partials in ascending k (= ascending logical id)
         const unsigned long long tile_end = (unsigned long long)(t + 1u) * nkt;
         unsigned c_end = s.slots;
-#ifdef SM_TUNING
-        if (s.ablate & 2) c_end = 0;
-#endif
         for (unsigned cs = slot + 1u; cs < c_end && sk_slot_start(s, cs, nkt) < tile_end; ++cs) {
           const unsigned c = cs * tn + tile_n;  // the workgroup of slot cs that holds this column tile
           if (tid == 0) {
@@ -785,13 +634,12 @@ static SkPlan sk_plan(size_t panels, size_t nkt, size_t tn, size_t cus) {
   SkPlan best = {};
   const size_t max_slots = cus / tn;
   if (max_slots == 0 || panels == 0 || nkt == 0 || nkt > 0xffffu) return best;
-  const unsigned lead = (unsigned)tuning_int("SM_SK_LEAD", (int)SK_LEAD);
   for (unsigned wg = 1; wg <= 8; ++wg)
     for (unsigned tg = 1; tg <= 16; ++tg) {
       if (wg > 1 && (size_t)tg * nkt < 2 * (size_t)wg) continue;  // at least two stages per range
       const size_t gf = panels / tg, tgl = panels % tg, wgl = tgl ? (tgl * wg + tg - 1) / tg : 0;
       if (gf * wg + wgl == 0 || gf * wg + wgl > max_slots) continue;
-      const SkPlan pl = sk_plan_for(panels, nkt, tg, wg, lead);
+      const SkPlan pl = sk_plan_for(panels, nkt, tg, wg, SK_LEAD);
       if (best.slots == 0 || pl.units < best.units) best = pl;
     }
   return best;
@@ -801,9 +649,6 @@ template <int BN, bool BF = false, bool ANT = true, bool DENSE = false>
 static int launch_fused_sk(const FusedArgs& a0, void* workspace, size_t workspace_bytes, hipStream_t st) {
   constexpr int BM = 256;
   FusedArgs a = a0;
-#ifdef SM_TUNING
-  if (!a.ablate) a.ablate = tuning_int("SM_DIRECT_ABLATE", 0) & 24;
-#endif
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t panels = (size_t)a.tiles_m * a.batch * a.ngroup;
@@ -819,12 +664,6 @@ static int launch_fused_sk(const FusedArgs& a0, void* workspace, size_t workspac
   }
   const int cus = device_cu_count();
   SkPlan pl = sk_plan(panels, nkt, (size_t)a.tiles_n, (size_t)cus);
-#ifdef SM_TUNING
-  if (const int wg_env = tuning_int("SM_SK_WG", 0)) {  // tuning: force the group shape (SM_SK_TG panels cut into SM_SK_WG ranges)
-    const unsigned tg = (unsigned)tuning_int("SM_SK_TG", 1), wg = (unsigned)(wg_env > 8 ? 8 : wg_env);
-    pl = sk_plan_for(panels, nkt, tg ? tg : 1, wg, (unsigned)tuning_int("SM_SK_LEAD", (int)SK_LEAD));
-  }
-#endif
   const size_t nwg = (size_t)pl.slots * a.tiles_n;
   if (pl.slots == 0 || nwg > (size_t)cus || nwg > 1023) {
     set_error("sm_spmma_fused_*_ws: the shape has more column tiles than the stream-K form has compute units for");
@@ -839,9 +678,6 @@ static int launch_fused_sk(const FusedArgs& a0, void* workspace, size_t workspac
   s.part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + 4096);
   s.panels = (unsigned)panels; s.slots = pl.slots; s.tg = pl.tg; s.wg = pl.wg; s.groups_full = pl.groups_full; s.tgl = pl.tgl; s.wgl = pl.wgl;
   for (int i = 0; i < 9; ++i) { s.cut[i] = pl.cut[i]; s.cutl[i] = pl.cutl[i]; }
-#ifdef SM_TUNING
-  s.ablate = tuning_int("SM_SK_ABLATE", 0);
-#endif
   constexpr size_t lds_main = (size_t)3 * BM * 128 + (size_t)2 * 64 * BN * 2;
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
@@ -857,16 +693,14 @@ static int launch_fused_sk(const FusedArgs& a0, void* workspace, size_t workspac
 // its one or two 256 KiB partial tiles at the end of the launch, 40-100 MB at the chip's memory rate all at once: profiles/
 // sk_probe_r05d.txt); the big form = rounds x stages; a 128 x 256 tile's stage (wide kernel) takes ~0.6 of a 256 x 256 one
 // (profiles/stamp_r04b_big_wide_direct.txt).  The A-stationary shapes (n > 256, k <= 512, plain store) keep their kernel: few
-// stages per tile, nothing for a K split to balance.  SM_FUSED_SK (tuning): 0 = never, 2 = wherever the kernel takes the shape.
+// stages per tile, nothing for a K split to balance.
 static bool sk_takes(size_t rows, size_t problems, size_t n, size_t k, bool astat_shape, SkPlan& pl) {
-  const int sk_rule = tuning_int("SM_FUSED_SK", 1);
-  if (!sk_rule || n <= 128 || k < 128 || k % 64 != 0) return false;
+  if (n <= 128 || k < 128 || k % 64 != 0) return false;
   const size_t cus = (size_t)device_cu_count(), nkt = k / 64;
   const size_t panels = (rows + 255) / 256 * problems, tn = (n + 255) / 256;
   const size_t t_big = panels * tn, t_wide = (rows + 127) / 128 * tn * problems;
   pl = sk_plan(panels, nkt, tn, cus);
   if (!pl.slots) return false;
-  if (sk_rule == 2) return true;
   const double c_sk = (double)pl.units + (pl.wg > 1 ? 8.0 : 0.0);
   const double c_big = (double)((t_big + cus - 1) / cus * nkt), c_wide = 0.6 * (double)((t_wide + cus - 1) / cus * nkt);
   const double c_now = c_big < c_wide ? c_big : c_wide;
@@ -896,11 +730,7 @@ __global__ __launch_bounds__(256) void spmma_f16_fused_span_kernel(const FusedAr
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned tiles = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
-#ifdef SM_TUNING
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, (p.ablate & 8) != 0);  // (tuning: SM_DIRECT_ABLATE bit 3 = dispatch order; measured 0-5 % slower here, mma_tile.h)
-#else
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
-#endif
   const unsigned grp = lid / tiles, trem = lid - grp * tiles;  // batch == 1: the batches are stacked rows
   const unsigned tile_m = trem / (unsigned)p.tiles_n, tile_n = trem - tile_m * (unsigned)p.tiles_n;
   const int m0 = (int)tile_m * BM, n0 = (int)tile_n * BN;
@@ -1012,9 +842,6 @@ __global__ __launch_bounds__(256) void spmma_f16_fused_span_kernel(const FusedAr
 template <int BN, bool BF = false, bool DENSE = false>
 static int launch_fused_span(const FusedArgs& a0, hipStream_t st) {
   FusedArgs a = a0;
-#ifdef SM_TUNING
-  if (!a.ablate) a.ablate = tuning_int("SM_DIRECT_ABLATE", 0) & 24;
-#endif
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.ngroup;
@@ -1080,11 +907,7 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned tiles = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
-#ifdef SM_TUNING
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, (p.ablate & 8) != 0);  // (tuning: SM_DIRECT_ABLATE bit 3 = dispatch order; measured 0-5 % slower here, mma_tile.h)
-#else
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
-#endif
   const unsigned gb = lid / tiles, trem = lid - gb * tiles;
   const unsigned grp = gb / (unsigned)p.batch, b = gb - grp * (unsigned)p.batch;
   const unsigned tile_m = trem / (unsigned)p.tiles_n, tile_n = trem - tile_m * (unsigned)p.tiles_n;
@@ -1104,36 +927,21 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
     BTileDma<BN, NBW> bd;
     bd.setup(p.B[grp] + (size_t)b * p.sB, p.N, n0, wave - (NC + NLA), lane, BRING);
     auto issue = [&](int kt, int buf) {
-#if defined(SM_ABLATE) && (SM_ABLATE & 4)
-      return;  /* diagnostic timing builds only: 1 = no consumer compute, 2 = no selection, 4 = no B DMA, 8 = no A loads in the loop */
-#endif
       bd.issue(smem, kt, (unsigned)(buf * SB));
     };
 #pragma unroll
     for (int s = 0; s < NSB - 1; ++s)
       if (s < nkt) issue(s, s);
     int nb = NSB - 1;  // buffer of the next stage to issue
-    SM_T(unsigned long long tb = 0, ti = 0, tv = 0, nlong = 0; unsigned long long s0 = sm_stamp(); unsigned long long sprev = s0;)
     for (int kt = 0; kt < nkt; ++kt) {
       // stage kt has landed once at most the NSB-2 younger stages are still in flight (fewer exist at the tail)
-#ifdef SM_STAMP
-      if (kt + NSB - 2 < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSB - 2) * B_WI) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned long long sv = sm_stamp();
-      tv += sv - s0;
-      asm volatile("s_barrier" ::: "memory");
-#else
       if (kt + NSB - 2 < nkt) wait_dma_and_barrier<(NSB - 2) * B_WI>();
       else wait_dma_and_barrier<0>();
-#endif
-      SM_T(unsigned long long s1 = sm_stamp(); tb += s1 - s0;)
       if (kt + NSB - 1 < nkt) {
         issue(kt + NSB - 1, nb);  // the buffer stage kt-1 occupied: consumers left it before barrier kt
         nb = nb + 1 == NSB ? 0 : nb + 1;
       }
-      SM_T(s0 = sm_stamp(); ti += s0 - s1; { const unsigned long long busy = (s0 - s1) + (sv - sprev); nlong += busy > 2000 ? 1 : 0; sprev = s0; })
     }
-    SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8; d[0] = tb; d[1] = ti; d[2] = tv; d[3] = 2; d[6] = nlong; })
   } else if (wave >= (unsigned)NC) {
     // ------------------------------------------------------------------ A loader wave: load, select, ds_write
     // (round 4: raising these waves' priority -- their selection is the stage's critical path -- changed nothing: within 2 %
@@ -1173,35 +981,23 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         uint32_t k0, k1, n0, n1;
-#if defined(SM_ABLATE) && (SM_ABLATE & 2)
-        k0 = src[i][0]; k1 = src[i][2]; n0 = 4; n1 = 4;
-#else
         strip_select_f16(src[i][0], src[i][1], k0, n0);
         strip_select_f16(src[i][2], src[i][3], k1, n1);
-#endif
         *reinterpret_cast<u2*>(sb + a_val_off[i]) = u2{k0, k1};
         *reinterpret_cast<unsigned char*>(sb + a_meta_off[i]) = (unsigned char)(n0 | (n1 << 4));
       }
     };
-    SM_T(unsigned long long tb = 0, tw = 0, ti = 0, tv = 0, tmax = 0, nlong = 0; unsigned long long s0 = 0;)
     auto step = [&](int kt, u4 (&rr)[4], bool write, bool load) {
       // stage kt is complete in LDS once this wave's ds_writes have landed; loads stay in flight
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);   // keep the next stage's selection (and its vmcnt wait) below the barrier
-      SM_T(unsigned long long s1 = sm_stamp(); tb += s1 - s0;)
       if (write) {
-        SM_T(asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (PF - 1)) : "memory"); unsigned long long s1b = sm_stamp(); tv += s1b - s1;)
         write_stage(kt + 1, rr);  // buffer (kt+1)&1: consumers left it before barrier kt
       }
-      SM_T(__builtin_amdgcn_sched_barrier(0); unsigned long long s2 = sm_stamp(); tw += s2 - s1;)
-#if !(defined(SM_ABLATE) && (SM_ABLATE & 8))
       if (load) load_a(kt + 1 + PF, rr);
-#endif
       __builtin_amdgcn_sched_barrier(0);
-      SM_T(s0 = sm_stamp(); ti += s0 - s2; { const unsigned long long busy = s0 - s1; tmax = busy > tmax ? busy : tmax; nlong += busy > 2000 ? 1 : 0; })
     };
     int kt0 = 0;
-    SM_T(s0 = sm_stamp();)
     if (nkt > 2 * PF) {
 #pragma unroll
       for (int s = 0; s < PF; ++s) load_a(s, ra[s]);
@@ -1225,7 +1021,6 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
         if (kt < nkt) step(kt, ra[(u + 1) % PF], kt + 1 < nkt, kt + 1 + PF < nkt);
       }
     }
-    SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8; d[0] = tb; d[1] = tw; d[2] = ti; d[3] = 1; d[4] = tv; d[5] = tmax; d[6] = nlong; })
   } else {
     // ------------------------------------------------------------------ consumer wave (as spmma_f16_pc_kernel)
     int cb = 0;
@@ -1240,7 +1035,6 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
       for (int s = 0; s < NSB - 1; ++s)
         if (s < nkt) bd.issue(smem, s, (unsigned)(s * SB));
     }
-    SM_T(unsigned long long tb = 0, tc = 0, nlong = 0; unsigned long long s0 = sm_stamp();)
     for (int kt = 0; kt < nkt; ++kt) {
       if (NLB == 0) {
         if (kt + NSB - 2 < nkt) wait_dma_and_barrier<(NSB - 2) * B_WI>();
@@ -1252,19 +1046,12 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
       } else {
         wait_dma_and_barrier<0>();
       }
-      SM_T(unsigned long long s1 = sm_stamp(); tb += s1 - s0;)
-#if defined(SM_ABLATE) && (SM_ABLATE & 1)
-      cb = cb + 1 == NSB ? 0 : cb + 1;
-      continue;
-#endif
       const char* As = smem + (kt & 1) * ASTG;
       const char* Ms = As + SA;
       const char* Bs = smem + BRING + cb * SB;
       smfmac_stage<FM, FN, BF>(As, Ms, Bs, wm * TM, wn * TN, lane, acc);
       cb = cb + 1 == NSB ? 0 : cb + 1;
-      SM_T(__builtin_amdgcn_sched_barrier(0); s0 = sm_stamp(); tc += s0 - s1; nlong += (s0 - s1) > 2000 ? 1 : 0;)
     }
-    SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * NW + wave) * 8; d[0] = tb; d[1] = tc; d[2] = 0; d[3] = 0; d[6] = nlong; })
   }
   __syncthreads();
 
@@ -1274,9 +1061,6 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
 template <int BN, int WM, int WN, int NLB, int PF, int NSB, bool BF = false, bool ANT = true>
 static int launch_fused_wide(const FusedArgs& a0, hipStream_t st) {
   FusedArgs a = a0;
-#ifdef SM_TUNING
-  if (!a.ablate) a.ablate = tuning_int("SM_DIRECT_ABLATE", 0) & 24;
-#endif
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -1292,34 +1076,6 @@ static int launch_fused_wide(const FusedArgs& a0, hipStream_t st) {
   if (lds > 64 * 1024) {
     if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT>), lds, "spmma_f16_fused_wide_kernel")) return rc;
   }
-#ifdef SM_STAMP
-  {
-    constexpr int NWV = WM * WN + 4 + NLB;
-    static unsigned long long* dbg = nullptr;
-    static size_t cap = 0;
-    const size_t cnt = nwg * (size_t)NWV * 8;
-    if (cnt > cap) { if (dbg) (void)hipFree(dbg); (void)hipMalloc((void**)&dbg, cnt * 8); cap = cnt; }
-    (void)hipMemset(dbg, 0, cnt * 8);
-    a.dbg = dbg;
-    spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT><<<dim3((unsigned)nwg), dim3(64 * NWV), lds, st>>>(a);
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(cnt);
-    (void)hipMemcpy(h.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-    double LBl = 0, Cnl = 0, LA[6] = {0, 0, 0, 0, 0, 0}, LB[3] = {0, 0, 0}, Cn[2] = {0, 0}, na = 0, nbw = 0, nc = 0;
-    for (size_t i = 0; i < cnt / 8; ++i) {
-      const unsigned long long* d = &h[i * 8];
-      if (d[3] == 1) { LA[0] += d[0]; LA[1] += d[1]; LA[2] += d[2]; LA[3] += d[4]; LA[4] += d[5]; LA[5] += d[6]; na += 1; }
-      else if (d[3] == 2) { LB[0] += d[0]; LB[1] += d[1]; LB[2] += d[2]; LBl += d[6]; nbw += 1; }
-      else { Cn[0] += d[0]; Cn[1] += d[1]; Cnl += d[6]; nc += 1; }
-    }
-    const double nk = (double)(a.K / 64);
-    fprintf(stderr, "STAMP-FUSED-WIDE %dx%dx%d PF=%d NSB=%d tiles=%zu nkt=%d | A-loader per stage: barrier %.0f vmcnt-wait %.0f select+write(incl. wait) %.0f load-issue %.0f | B-loader: wait+barrier %.0f (vmcnt part %.0f) issue %.0f | consumer: barrier %.0f compute %.0f\n",
-            a.Mrows, a.N, a.K, PF, NSB, nwg, a.K / 64, LA[0] / na / nk, LA[3] / na / nk, LA[1] / na / nk, LA[2] / na / nk,
-            LB[0] / nbw / nk, LB[2] / nbw / nk, LB[1] / nbw / nk, Cn[0] / nc / nk, Cn[1] / nc / nk);
-    fprintf(stderr, "   A-loader busy per stage: mean of per-wave max %.0f, stages busier than 2000 cycles per wave %.1f of %d (B-loader %.1f, consumer %.1f)\n", LA[4] / na, LA[5] / na, a.K / 64, LBl / nbw, Cnl / nc);
-    return check_launch("spmma_f16_fused_wide_kernel");
-  }
-#endif
   spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + 4 + NLB)), lds, st>>>(a);
   return check_launch("spmma_f16_fused_wide_kernel");
 }
@@ -1559,9 +1315,6 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
 template <int BN, int WM, int WN, int NLB, int PF, int NSB, bool BF = false>
 static int launch_fused_widep(const FusedArgs& a0, hipStream_t st) {
   FusedArgs a = a0;
-#ifdef SM_TUNING
-  if (!a.ablate) a.ablate = tuning_int("SM_DIRECT_ABLATE", 0) & 24;
-#endif
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nt = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -1609,11 +1362,7 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nkt = p.K / 64;
   const unsigned per_batch = (unsigned)p.tiles_m * (unsigned)nsplit;
-#ifdef SM_TUNING
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, (p.ablate & 8) != 0);  // (tuning: SM_DIRECT_ABLATE bit 3 = dispatch order; measured 0-5 % slower here, mma_tile.h)
-#else
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
-#endif
   const unsigned gb = lid / per_batch, trem = lid - gb * per_batch;
   const unsigned grp = gb / (unsigned)p.batch, b = gb - grp * (unsigned)p.batch;
   const unsigned tile_m = trem / (unsigned)nsplit, split = trem - tile_m * (unsigned)nsplit;
@@ -1640,9 +1389,6 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
   const size_t row_bytes = (size_t)p.N * 2;
   int i_nt = nt0, i_kt = 0, i_buf = 0;  // the next B stage to issue
   auto issue_b = [&]() {
-#if defined(SM_ABLATE) && (SM_ABLATE & 4)
-    if (nkt > 0) { i_buf = i_buf + 1 == NSB ? 0 : i_buf + 1; if (++i_kt == nkt) { i_kt = 0; ++i_nt; } return; }
-#endif
 #pragma unroll
     for (int i = 0; i < B_WI; ++i) {
       int gc = i_nt * BN + (int)b_col[i];
@@ -1694,24 +1440,11 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
 
   if (is_b) {
     // ------------------------------------------------------------------ B loader wave
-    SM_T(unsigned long long tv = 0, tb = 0, ti = 0; unsigned long long s0 = sm_stamp();)
     for (int it = 0; it < T; ++it) {
-#ifdef SM_STAMP
-      if (it + NSB - 2 < T) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSB - 2) * B_WI) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned long long sv = sm_stamp();
-      tv += sv - s0;
-      asm volatile("s_barrier" ::: "memory");
-      const unsigned long long s1 = sm_stamp();
-      tb += s1 - sv;
-#else
       if (it + NSB - 2 < T) wait_dma_and_barrier<(NSB - 2) * B_WI>();
       else wait_dma_and_barrier<0>();
-#endif
       if (it + NSB - 1 < T) issue_b();
-      SM_T(s0 = sm_stamp(); ti += s0 - s1;)
     }
-    SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * 16 + wave) * 8; d[0] = tv; d[1] = tb; d[2] = ti; d[3] = 2; d[4] = (unsigned long long)T; })
   } else {
     // ------------------------------------------------------------------ consumer wave
     const unsigned g = lane >> 4, r = lane & 15u;
@@ -1723,23 +1456,13 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
 #pragma unroll
       for (int j = 0; j < FN; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
     int cb = 0, kt = 0, nt = nt0;
-    SM_T(unsigned long long tb = 0, tc = 0, te = 0; unsigned long long s0 = sm_stamp();)
     for (int it = 0; it < T; ++it) {
       asm volatile("s_barrier" ::: "memory");  // (no vmcnt: this wave's C stores of the previous tile may still be in flight)
-      SM_T(unsigned long long s1 = sm_stamp(); tb += s1 - s0;)
-#if defined(SM_ABLATE) && (SM_ABLATE & 1)
-      if (nkt > 0) { cb = cb + 1 == NSB ? 0 : cb + 1; if (++kt == nkt) { kt = 0; ++nt; } continue; }
-#endif
       const char* As = smem + kt * ASTG;
       const char* Ms = As + SA;
       const char* Bs = Bring + cb * SB;
       smfmac_stage<FM, FN, BF>(As, Ms, Bs, wm * TM, wn * TN, lane, acc);
       cb = cb + 1 == NSB ? 0 : cb + 1;
-      SM_T(__builtin_amdgcn_sched_barrier(0); s0 = sm_stamp(); tc += s0 - s1;)
-#if defined(SM_ABLATE) && (SM_ABLATE & 16)
-      if (++kt == nkt) { kt = 0; ++nt; }
-      if (nkt > 0) continue;
-#endif
       if (++kt == nkt) {
         // ---- this column tile is done: C piece of this wave through its private LDS patch, 16-byte row pieces out
 #pragma unroll
@@ -1767,10 +1490,8 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
         }
         kt = 0;
         ++nt;
-        SM_T(__builtin_amdgcn_sched_barrier(0); { const unsigned long long s2 = sm_stamp(); te += s2 - s0; s0 = s2; })
       }
     }
-    SM_T(if (p.dbg && lane == 0) { unsigned long long* d = p.dbg + ((size_t)blockIdx.x * 16 + wave) * 8; d[0] = tb; d[1] = tc; d[2] = te; d[3] = 0; d[4] = (unsigned long long)T; })
   }
 }
 
@@ -1785,9 +1506,6 @@ static size_t astat_lds_bytes(int nkt, int nsb) { return (size_t)nkt * (128 * 72
 template <bool BF = false>
 static int launch_fused_astat(const FusedArgs& a0, hipStream_t st) {
   FusedArgs a = a0;
-#ifdef SM_TUNING
-  if (!a.ablate) a.ablate = tuning_int("SM_DIRECT_ABLATE", 0) & 24;
-#endif
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + 127) / 128;
   // split the column range of a row panel over several workgroups until 3/4 of the CUs have one (a split re-selects
@@ -1795,10 +1513,8 @@ static int launch_fused_astat(const FusedArgs& a0, hipStream_t st) {
   // per split
   const int cus = device_cu_count();
   const size_t panels = (size_t)a.tiles_m * a.batch * a.ngroup;
-  static const int nsplit_env = tuning_int("SM_FUSED_NSPLIT", 0);  // tuning aid
   int nsplit = 1;
-  while (!nsplit_env && panels * nsplit * 4 < (size_t)3 * cus && (a.tiles_n + 2 * nsplit - 1) / (2 * nsplit) >= 2) nsplit *= 2;
-  if (nsplit_env > 0) nsplit = nsplit_env < a.tiles_n ? nsplit_env : a.tiles_n;
+  while (panels * nsplit * 4 < (size_t)3 * cus && (a.tiles_n + 2 * nsplit - 1) / (2 * nsplit) >= 2) nsplit *= 2;
   int tps = (a.tiles_n + nsplit - 1) / nsplit;
   nsplit = (a.tiles_n + tps - 1) / tps;  // no empty splits
   const size_t nwg = panels * nsplit;
@@ -1912,22 +1628,18 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   }
   hipStream_t st = (hipStream_t)stream;
   // n <= 128 (and n <= 256 with a single stage): the direct kernel -- dense A by LDS-DMA, selection in the consumer's
-  // registers, ring of 2 so that three workgroups share a CU.  SM_FUSED_DIRECT=3 (tuning aid): ring of 3.
-  static const int direct_env = tuning_int("SM_FUSED_DIRECT", 2);
-  static const int wide_env = tuning_int("SM_FUSED_WIDE", 0);  // tuning aid: force the wide kernel
+  // registers, ring of 2 so that three workgroups share a CU.
   // (round 4) n > 128: the 256-row BIG form where its one-per-CU workgroups fill the chip's rounds at least as well as the
   // 128-row kernels' do (profiles/ab_big_r04a.txt: it then wins 3-10 %: 784 x 256 x 1024 x 5, 3136 x 256 x 512, 196 x 512 x 4608 x 3,
   // 784 x 512 x 1024; it loses where halving the tile count empties the last round: 784 x 256 x 2304 x 6 = 588 tiles = 2.3
   // rounds against 4.6, 196 x 512 x 2048 x 2 = 100 tiles against 196).  Against the A-stationary kernel (n > 256, k <= 512) it
-  // needs a clear margin (196 x 2048 x 512 x 3: 59 vs 68 us; 784 x 1024 x 256 x 6: 126 vs 111).  SM_FUSED_BIG (tuning): 0 = never.
-  const int big_rule = tuning_int("SM_FUSED_BIG", 8);
+  // needs a clear margin (196 x 2048 x 512 x 3: 59 vs 68 us; 784 x 1024 x 256 x 6: 126 vs 111).
   auto round_eff = [](size_t tiles, size_t cus) { const size_t r = (tiles + cus - 1) / cus; return r ? (double)tiles / (double)(r * cus) : 1.0; };
   // (round 5) with a workspace: the STREAM-K form where the rounds of whole tiles leave CUs idle.  Costs in stages of a 256 x 256
   // tile: stream-K = its share of the stage units + ~3 stages for the fix-up of the two tiles a range cuts; the big form = rounds x
   // stages; a 128 x 256 tile's stage (wide kernel) takes ~0.6 of a 256 x 256 one (profiles/stamp_r04b_big_wide_direct.txt).  The
   // A-stationary shapes (n > 256, k <= 512) keep their kernel: few stages per tile, nothing for a K split to balance.
-  // SM_FUSED_SK (tuning): 0 = never, 2 = wherever the kernel takes the shape.
-  if (workspace && !wide_env) {
+  if (workspace) {
     const bool astat_shape = n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0);
     SkPlan pl;
     if (sk_takes((size_t)a.Mrows, (size_t)a.batch * a.ngroup, n, k, astat_shape, pl) &&
@@ -1938,13 +1650,7 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
       if (rc != SM_STATUS_NOT_SUPPORTED) return rc;
     }
   }
-#ifdef SM_TUNING
-  // (round 6, the residency experiment VERDICT round 5 asked for -- tuning builds only: SM_FUSED_D256=1) the few-tile shapes on 128 x 256 DIRECT
-  // tiles: four waves, a ring of two 48 KiB stages = 96 KiB, so that a 48-64 KiB direct workgroup of ANOTHER launch fits on the same CU beside
-  // it (the big / wide / A-stationary workgroups hold the whole LDS or 16 waves).  Measured with tools/overlap_probe.py: DESIGN.md 4.2.
-  if (tuning_int("SM_FUSED_D256", 0) && n > 128 && k > 64) return launch_fused_direct<256, 2, BF, 128, 4, false>(a, st);
-#endif
-  if (big_rule == 8 && !wide_env && n > 128 && k > 64) {
+  if (n > 128 && k > 64) {
     const size_t cus = (size_t)device_cu_count(), nb = (size_t)a.batch * a.ngroup;
     const size_t t_big = ((size_t)a.Mrows + 255) / 256 * ((n + 255) / 256) * nb, t_wide = ((size_t)a.Mrows + 127) / 128 * ((n + 255) / 256) * nb;
     const bool astat_shape = n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0);
@@ -1958,49 +1664,20 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
     // (the hint on the big form's A loads, n <= 256: measured indifferent, profiles/nt_ab_r05q.txt)
     if (big) return n <= 256 ? launch_fused_big<256, BF, 3, 2, true>(a, st) : launch_fused_big<256, BF, 3, 2, false>(a, st);
   }
-#ifdef SM_TUNING
-  {  // A/B of the 256-row big form: bit 0 = n >= 256 (k > 64), bit 1 = 64 < n <= 128, bit 2 = n <= 256 with k <= 64; SM_FUSED_BIG_NSB = 2 / 3
-    const int big_env = tuning_int("SM_FUSED_BIG", 0), nsb = tuning_int("SM_FUSED_BIG_NSB", 2);
-    if (big_env < 8 && (big_env & 1) && n > 128 && k > 64) return n <= 256 ? launch_fused_big<256, BF, 3, 2, true>(a, st) : launch_fused_big<256, BF, 3, 2, false>(a, st);
-    if (big_env < 8 && (big_env & 4) && n > 128 && n <= 256 && k <= 64) return launch_fused_big<256, BF, 3, 2, true>(a, st);
-    if (big_env < 8 && (big_env & 2) && n > 64 && n <= 128) return nsb == 3 ? launch_fused_big<128, BF, 3, 3, true>(a, st) : launch_fused_big<128, BF, 3, 2, true>(a, st);
-  }
-#endif
   // (round 5: 128-column direct tiles at ANY n -- every column tile re-reading its A rows through L2, as 12544 x 256 x 64 does at 0.89 of its roofline -- measured on
   //  the shapes the A-stationary and wide kernels serve: slower on all of them, 3136 x 512 x 128 x 4 147 vs 129 us, 784 x 1024 x 256 x 6 164 vs 114, 784 x 256 x 2304 x 6
   //  303 vs 195, 196 x 512 x 2048 x 2 55 vs 32 (profiles/ab_direct_any_r05an.txt; the rows whose two columns agree went to the big form before the hook).  Removed.)
-  if (!wide_env && (n <= 128 || (n <= 256 && k <= 64))) {
-#ifdef SM_TUNING
-    if (tuning_int("SM_FUSED_NW", 4) == 8) {  // eight waves of 16 rows per workgroup: the same LDS, twice the waves per SIMD
-      if (n <= 64) return launch_fused_direct<64, 2, BF, 128, 8>(a, st);
-      return launch_fused_direct<128, 2, BF, 128, 8>(a, st);
-    }
-    if (tuning_int("SM_FUSED_BM", 128) == 64) {  // 64-row tiles: 32 KiB (n = 64) of LDS per workgroup, five workgroups per CU
-      if (n <= 64) return launch_fused_direct<64, 2, BF, 64>(a, st);
-      return launch_fused_direct<128, 2, BF, 64>(a, st);
-    }
-    // (round 5: 192-row tiles at 128 columns -- four waves of 48 rows, a third less B re-read per A byte, 80 KiB: still two workgroups per CU -- bit-identical and
-    //  no faster than the 128-row tiles on any n = 128 shape: 3136 x 128 x 1152 x 4 193.5 us against 194, 3136 x 128 x 512 x 3 83.7 against 80, 12544 x 128 x 256 61 against 60
-    //  (profiles/ab_bm192_r05s.txt: its "bm128" column is the spilling tuning build, compare with profiles/sweep_r05y_f16_resnet50.txt).  So the B tile re-read through
-    //  the CU's L2 port is NOT what holds the 128-column shapes at 4.5 TB/s.  Removed.)
-#endif
-#ifdef SM_TUNING
-    if (tuning_int("SM_DIRECT_NT", 1) == 0) {  // A/B of the non-temporal hint on the A DMA
-      if (n <= 64) return launch_fused_direct<64, 2, BF, 128, 4, false>(a, st);
-      return launch_fused_direct<128, 2, BF, 128, 4, false>(a, st);
-    }
-#endif
-    if (n <= 64) return direct_env >= 3 ? launch_fused_direct<64, 3, BF>(a, st) : launch_fused_direct<64, 2, BF>(a, st);
+  if (n <= 128 || (n <= 256 && k <= 64)) {
+    if (n <= 64) return launch_fused_direct<64, 2, BF>(a, st);
     // (round 5) the non-temporal hint on the A loads only where A really is read once and streams long: with two column tiles (n = 256,
     // k = 64) the second tile's read of the same rows then misses L2 -- 12544 x 256 x 64 x 3: 200 -> 166 us without the hint -- and the
     // short-K 128-column layer is 5 % faster without it too (12544 x 128 x 256: 68.7 -> 64.8 us); 3136 x 128 x 512 / 1152 and every
     // 64-column shape keep it (1-6 % faster with it; profiles/nt_ab_r05q.txt).  Same C either way.
-    if (direct_env < 3 && (n > 128 || k < 512)) return launch_fused_direct<128, 2, BF, 128, 4, false>(a, st);
-    return direct_env >= 3 ? launch_fused_direct<128, 3, BF>(a, st) : launch_fused_direct<128, 2, BF>(a, st);
+    if (n > 128 || k < 512) return launch_fused_direct<128, 2, BF, 128, 4, false>(a, st);
+    return launch_fused_direct<128, 2, BF>(a, st);
   }
   // n > 256, short K, plain store: A-stationary (the 2:4 image of a row panel stays in LDS across column tiles)
-  static const int astat_env = tuning_int("SM_FUSED_ASTAT", 1);  // tuning aid: 0 = off
-  if (astat_env && n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0) &&
+  if (n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0) &&
       astat_lds_bytes((int)(k / 64), 3) <= 160 * 1024) {
     return launch_fused_astat<BF>(a, st);
   }
@@ -2011,9 +1688,8 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   // The persistent form pays off where a tile is short (its fill / drain is a large share of it): 3136 x 256 x 512, b = 32:
   // 39.5 vs 43.9 us per instance, 784 x 256 x 1024: 19.6 vs 20.3; on 36- and 72-stage tiles the statically assigned tiles
   // lose to the hardware's dynamic dispatch (784 x 256 x 2304: 40.5 vs 39.1, 196 x 512 x 4608: 41.0 vs 35.3;
-  // profiles/widep_r03g.txt), so those keep one workgroup per tile.  SM_FUSED_WIDEP (tuning aid): 0 = never, 2 = always.
-  static const int widep_env = tuning_int("SM_FUSED_WIDEP", 1);
-  if (widep_env == 2 || (widep_env == 1 && k <= 1024)) return launch_fused_widep<256, 4, 2, 4, 2, 3, BF>(a, st);
+  // profiles/widep_r03g.txt), so those keep one workgroup per tile.
+  if (k <= 1024) return launch_fused_widep<256, 4, 2, 4, 2, 3, BF>(a, st);
   if (n > 256) return launch_fused_wide<256, 4, 2, 4, 2, 3, BF, false>(a, st);  // several column tiles read the same A rows: no non-temporal hint
   return launch_fused_wide<256, 4, 2, 4, 2, 3, BF>(a, st);
 }
@@ -2111,26 +1787,21 @@ static int dense_twin16(const DenseTwinCall& c, hipStream_t st) {
   // (round 5) with a workspace: the stream-K form -- only on the shapes where this pipeline is the dense GEMM's better one at all
   // (n <= 256 with k >= 2048, below): elsewhere gemm_f16.hip's 128 x 128 tiles at two workgroups per CU beat it by more than a K split
   // returns (196 x 512 x 4608 x 3: 163 us against 110, profiles/ab_streamk_r05e.txt)
-  if (c.workspace && c.mode < 2 && n > 128 && n <= 256 && k >= 2048) {
+  if (c.workspace && n > 128 && n <= 256 && k >= 2048) {
     SkPlan pl;
     if (sk_takes((size_t)c.M, (size_t)c.batch, n, k, false, pl) && c.workspace_bytes >= sk_workspace_bytes((size_t)pl.slots * ((n + 255) / 256), 256) &&
         aligned16(c.workspace))
-      return n <= 256 ? launch_fused_sk<256, BF, true, true>(a, c.workspace, c.workspace_bytes, st) : launch_fused_sk<256, BF, false, true>(a, c.workspace, c.workspace_bytes, st);
+      return launch_fused_sk<256, BF, true, true>(a, c.workspace, c.workspace_bytes, st);
   }
-  if (n <= 128) {  // gemm_f16.hip's 128 x 64 / 128 x 128 tiles are the direct pipeline already (A/B in tuning builds only)
-#ifdef SM_TUNING
-    if (c.mode >= 2) return n <= 64 ? launch_fused_direct<64, 2, BF, 128, 4, true, true>(a, st) : launch_fused_direct<128, 2, BF, 128, 4, true, true>(a, st);
-#endif
-    return SM_STATUS_NOT_SUPPORTED;
-  }
+  if (n <= 128) return SM_STATUS_NOT_SUPPORTED;  // gemm_f16.hip's 128 x 64 / 128 x 128 tiles are the direct pipeline already
   if (k <= 64) return SM_STATUS_NOT_SUPPORTED;
-  if (c.mode < 2 && ((size_t)c.M + 255) / 256 * 256 * 100 > (size_t)c.M * 115) return SM_STATUS_NOT_SUPPORTED;  // > 15 % of the 256-row tiles would be padding
+  if (((size_t)c.M + 255) / 256 * 256 * 100 > (size_t)c.M * 115) return SM_STATUS_NOT_SUPPORTED;  // > 15 % of the 256-row tiles would be padding
   // n > 128: 256 x 256 tiles (A streamed once per 256 columns instead of once per 128).  Measured per ResNet-50 shape against
   // gemm_f16.hip's 128 x 128 tiles, two workgroups per CU (profiles/ab_dense_r04r2.txt): they win only on the long-K 256-column
   // shape (784 x 256 x 2304 x 6: 40.1 -> 35.6 us per instance) and lose 5-17 % on 3136 x 256 x 512, 3136 x 512 x 128,
   // 196 x 2048 x 512, 196 x 512 x 4608 -- the rule is that one case.
-  if (c.mode < 2 && !(n <= 256 && k >= 2048)) return SM_STATUS_NOT_SUPPORTED;
-  return n <= 256 ? launch_fused_big<256, BF, 3, 2, true, true>(a, st) : launch_fused_big<256, BF, 3, 2, false, true>(a, st);
+  if (!(n <= 256 && k >= 2048)) return SM_STATUS_NOT_SUPPORTED;
+  return launch_fused_big<256, BF, 3, 2, true, true>(a, st);
 }
 
 int sm::gemm_dense_twin(const DenseTwinCall& c, hipStream_t st) { return c.bf ? dense_twin16<true>(c, st) : dense_twin16<false>(c, st); }

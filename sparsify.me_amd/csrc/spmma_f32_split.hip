@@ -36,7 +36,6 @@ struct SplitArgs {
   int Mrows, N, K, lda;
   int batch, tiles_m, tiles_n;
   float alpha, beta;
-  int xcd_ranges;  // tuning builds (SM_SPLIT_XCD=1): the XCD ranges of round 4 instead of the dispatch order for single-column-tile launches
 };
 
 __device__ __forceinline__ float as_f32(uint32_t x) { return __builtin_bit_cast(float, x); }
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(64 * NW) void spmma_f32_split_kernel(const SplitArg
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned tiles = (unsigned)p.tiles_m * (unsigned)p.tiles_n;
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, p.tiles_n == 1 && !p.xcd_ranges);  // (mma_tile.h)
+  const unsigned lid = tile_order(blockIdx.x, gridDim.x, p.tiles_n == 1);  // (mma_tile.h)
   const unsigned b = lid / tiles, trem = lid - b * tiles;
   const unsigned tile_m = trem / (unsigned)p.tiles_n, tile_n = trem - tile_m * (unsigned)p.tiles_n;
   const int m0 = (int)tile_m * BM, n0 = (int)tile_n * BN;
@@ -597,7 +596,7 @@ __global__ __launch_bounds__(512) void spmma_f32_split_span_kernel(const SplitAr
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const unsigned lid = tile_order(blockIdx.x, gridDim.x, p.tiles_n == 1 && !p.xcd_ranges);  // (mma_tile.h)
+  const unsigned lid = tile_order(blockIdx.x, gridDim.x, p.tiles_n == 1);  // (mma_tile.h)
   const unsigned tile_m = lid / (unsigned)p.tiles_n, tile_n = lid - tile_m * (unsigned)p.tiles_n;
   const int m0 = (int)tile_m * BM, n0 = (int)tile_n * BN;
   const int nkt = (p.K + 63) / 64;
@@ -795,7 +794,6 @@ static int f32_split_product(bool dense, const float* A, const float* B, float* 
     if (const int rc = check_launch("split_planes_kernel")) return rc;
   }
   SplitArgs a = {};
-  a.xcd_ranges = tuning_int("SM_SPLIT_XCD", 0);
   a.A = A; a.Bp = P; a.C = C;
   a.sA = strideA; a.sBp = strideB ? k * n : 0; a.plane = plane; a.sC = strideC;
   a.Mrows = (int)m; a.N = (int)n; a.K = (int)k; a.lda = (int)lda; a.batch = (int)batch;
@@ -820,7 +818,7 @@ static int f32_split_product(bool dense, const float* A, const float* B, float* 
   // (its per-lane DMA sources are 32-bit offsets from two uniform bases: the last plane's last stage row and a tile's last A row must
   // stay below 4 GiB, or the call takes the 128-column tiles below, whose addresses are 64-bit)
   const bool cols_offsets_fit = (size_t)(planes - 1) * plane * 2 + (size_t)64 * n * 2 < ((size_t)1 << 32) && (size_t)128 * lda * 4 < ((size_t)1 << 32);
-  if (n > 128 && n <= 256 && cols_offsets_fit && tuning_int("SM_F32_SPLIT_COLS", 1)) {
+  if (n > 128 && n <= 256 && cols_offsets_fit) {
     if (dense) return planes == 3 ? launch_split_cols<2, 3, true>(a, st) : launch_split_cols<2, 2, true>(a, st);
     return planes == 3 ? launch_split_cols<2, 3, false>(a, st) : launch_split_cols<2, 2, false>(a, st);
   }
@@ -828,12 +826,6 @@ static int f32_split_product(bool dense, const float* A, const float* B, float* 
     if (planes == 3) return n <= 64 ? launch_split<64, 3, 8, true>(a, st) : launch_split<128, 3, 8, true>(a, st);
     return n <= 64 ? launch_split<64, 2, 8, true>(a, st) : launch_split<128, 2, 8, true>(a, st);
   }
-#ifdef SM_TUNING
-  if (tuning_int("SM_F32_SPLIT_NW", 8) == 4) {  // A/B: four waves of 32 rows (one per SIMD) instead of eight of 16
-    if (planes == 3) return n <= 64 ? launch_split<64, 3, 4>(a, st) : launch_split<128, 3, 4>(a, st);
-    return n <= 64 ? launch_split<64, 2, 4>(a, st) : launch_split<128, 2, 4>(a, st);
-  }
-#endif
   if (planes == 3) return n <= 64 ? launch_split<64, 3, 8>(a, st) : launch_split<128, 3, 8>(a, st);
   return n <= 64 ? launch_split<64, 2, 8>(a, st) : launch_split<128, 2, 8>(a, st);
 }

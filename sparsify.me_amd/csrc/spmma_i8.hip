@@ -120,11 +120,6 @@ static int spmma_i8_entry(const void* blob, const void* B, int32_t* C, int8_t* C
     a.batch = 1;
   }
   hipStream_t st = (hipStream_t)stream;
-  static const int cfg = tuning_int("SM_SPMMA_I8_CFG", 0);  // tuning aid
-  if (cfg == 1) return launch_spmma_b8<MmaI8, 64, 4, 1>(a, st, "sm_spmma_i8");
-  if (cfg == 2) return launch_spmma_b8<MmaI8, 128, 2, 2>(a, st, "sm_spmma_i8");
-  if (cfg == 3) return launch_spmma_b8<MmaI8, 128, 2, 4>(a, st, "sm_spmma_i8");
-  if (cfg == 4) return launch_spmma_b8<MmaI8, 128, 4, 4>(a, st, "sm_spmma_i8");
   // narrow outputs: 128 x 64 tiles over 4 waves (more tiles); otherwise 128 x 128 over 8 (tools/archive/i8_probe.py)
   return n <= 128 ? launch_spmma_b8<MmaI8, 64, 4, 1>(a, st, "sm_spmma_i8") : launch_spmma_b8<MmaI8, 128, 2, 4>(a, st, "sm_spmma_i8");
 }
@@ -156,10 +151,6 @@ static int spmma_fused_i8_entry(const void* A, const void* B, int32_t* C, int8_t
     a.batch = 1;
   }
   hipStream_t st = (hipStream_t)stream;
-  static const int cfg = tuning_int("SM_SPMMA_I8_FUSED_CFG", 0);  // tuning aid
-  if (cfg == 1) return launch_spmma_b8<MmaI8, 64, 4, 1, true>(a, st, "sm_spmma_fused_i8");
-  if (cfg == 2) return launch_spmma_b8<MmaI8, 128, 2, 4, true>(a, st, "sm_spmma_fused_i8");
-  if (cfg == 3) return launch_spmma_b8<MmaI8, 128, 4, 2, true>(a, st, "sm_spmma_fused_i8");
   return n <= 64 ? launch_spmma_b8<MmaI8, 64, 4, 1, true>(a, st, "sm_spmma_fused_i8") : launch_spmma_b8<MmaI8, 128, 4, 2, true>(a, st, "sm_spmma_fused_i8");
 }
 

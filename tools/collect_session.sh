@@ -1,5 +1,5 @@
 #!/bin/bash
-# copy what a final session (tools/sessions/gpu_r06z.sh + gpu_r06z2.sh <tag>) left under gpurun_out/ into profiles/ under the names profiles/README.md
+# copy the outputs of a final session (tools/gpu_final.sh <tag>) into profiles/ under the names profiles/README.md
 # lists, and make its counter files the *_latest.json that bench.py replays (they carry the hash of the library they were measured on)
 tag=$1; [ -n "$tag" ] || { echo "usage: $0 <tag>"; exit 1; }
 g=gpurun_out; p=profiles

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench.py's config-5 stage alone (sparsifyme::batched::strided_coo over the ResNet-50 shapes, b = 32, 10 % dense A): one line per shape,
-fast form (and which one) against the exact forms.  SM_COO_SMFMAC=0 with the tuning library gives the dense-MFMA pipeline for an A/B."""
+fast form (and which one) against the exact forms."""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """sm_spmm_coo_f32_fast a few times on chosen config-5 shapes, for `rocprofv3 --kernel-trace --stats -- python3 tools/coo_profile.py m,n,k ...`
-(per-kernel durations of the call's scan / scatter / image / matrix kernels); env COO_ABLATE -> SM_COO_ABLATE of the tuning library."""
+(per-kernel durations of the call's scan / scatter / image / matrix kernels)."""
 import ctypes, os, sys
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import numpy as np, torch

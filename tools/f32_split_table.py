@@ -24,8 +24,7 @@ def main():
     dev = torch.device("cuda", 0)
     rows = [tuple(int(x) for x in r[:4]) for r in list(csv.reader(open(os.path.join(ROOT, "datasets", a.table + ".csv"))))[1:] if r]
     cnt = collections.Counter(rows)
-    print(f"# {a.table}.csv: {len(rows)} layers, {len(cnt)} unique shapes, fp32; library {sm.version()}; us per layer, one launch at a time" +
-          (" [SM_F32_SPLIT_NW=%s]" % os.environ["SM_F32_SPLIT_NW"] if "SM_F32_SPLIT_NW" in os.environ else ""))
+    print(f"# {a.table}.csv: {len(rows)} layers, {len(cnt)} unique shapes, fp32; library {sm.version()}; us per layer, one launch at a time")
     print("%6s %5s %5s %3s %3s | %8s %8s | %8s %6s %8s %6s | %8s %8s | %7s" % ("m", "n", "k", "b", "cnt", "dense", "exact", "split3", "TB/s", "split2", "TB/s", "dense s3", "dense s2", "roof"))
     tot = collections.defaultdict(float)
     for (m, n, k, b), c in cnt.items():
