@@ -528,6 +528,43 @@ int sm_gemm_rowmajor_fp8(const void* A, const void* B, void* C, size_t m, size_t
                          size_t strideA, size_t strideB, size_t strideC, int fmt_a, int fmt_b, int out_type, float alpha,
                          float beta, const float* row_scale, sm_stream_t stream);
 
+/* ---- fp8 quantisation of 16-bit operands (extension): what produces the fp8 bytes and the row_scale of the entry points
+ *      above.  Per row i of a row-major fp16 / bf16 A (rows x k, lda), FMAX = 448 (SM_FP8_E4M3) / 57344 (SM_FP8_E5M2):
+ *        amax_i = max(max_j |a_ij| over the FINITE elements of the row, 2^-100)       exact
+ *        row_scale_i = amax_i / FMAX,  inv_i = FMAX / amax_i                           two correctly rounded fp32 divisions
+ *        q_ij = fp32(a_ij) * inv_i (one fp32 multiply) rounded to nearest even to fmt, subnormals of fmt included
+ *      |fp32(a_ij) * inv_i| <= FMAX (1 + 2^-23), which rounds to FMAX: a finite row never overflows and the largest
+ *      element of a non-zero row becomes 0x7e / 0x7b.  |a_ij - row_scale_i q_ij| <= R |a_ij| + S row_scale_i with
+ *      R = 2^-4, S = 2^-10 (e4m3), R = 2^-3, S = 2^-17 (e5m2).  An all-zero row gives 0x00 (-0: 0x80).  Non-finite
+ *      elements do not enter amax_i: NaN -> 0x7f (sign cleared), +-inf -> 0x7f (e4m3) / 0x7c | sign (e5m2).
+ *      sm_quantize_rows_fp8_*: Q (row-major rows x k bytes, ldq) and row_scale[rows]; any k.
+ *      sm_quantize_compress24_fp8_*: the same rule, then the STRIP selection on the quantised bytes, written as the blob
+ *      of sm_compress24_size(rows, k, 1, 1) bytes -- identical in every byte to sm_quantize_rows_fp8_* followed by
+ *      sm_compress24_fp8(Q, rows, k, k, 1, rows * k, blob, fmt) -- and the same row_scale; A is read once and no dense fp8
+ *      A exists.  The blob is stage-major over all rows, so rows = batch * m stacked matrices give the blob of
+ *      batch m x k matrices; with a shared B multiply them as ONE matrix, sm_spmma_fp8(blob, Bt, C, rows, n, k, 1, 0,
+ *      rows * n, ..., row_scale, ...): sm_spmma_fp8 indexes row_scale by row % m, so per-row scales of stacked rows reach
+ *      the epilogue only in that form (batch > 1 with a B per batch and per-row scales is not covered).
+ *      sm_quantize_transpose_fp8_*: the weight operand, row-major k x n 16-bit B (ldb) -> the [n][k] fp8 operand of the
+ *      1-byte kernels, q = rne_fmt(clamp(fp32(b) * inv_scale, -FMAX, FMAX)) with a per-tensor inv_scale given by the
+ *      caller (its reciprocal folds into alpha); the non-finite rule above.
+ *      A null operand, a bad fmt, lda < k, ldq < k, ldb < n or a blob that is not 16-byte aligned:
+ *      SM_STATUS_INVALID_VALUE.  Rows of A that are not 16-byte aligned (pointer, lda % 8), k % 64 != 0 for the compress
+ *      form, a dimension of 2^31 or more: SM_STATUS_NOT_SUPPORTED.  rows == 0 or k == 0 (n == 0): success.  All decided
+ *      before any device work; the entry points only enqueue on `stream` (no allocation, no synchronisation). */
+int sm_quantize_rows_fp8_f16(const void* A, size_t rows, size_t k, size_t lda, void* Q, size_t ldq, float* row_scale, int fmt,
+                             sm_stream_t stream);
+int sm_quantize_rows_fp8_bf16(const void* A, size_t rows, size_t k, size_t lda, void* Q, size_t ldq, float* row_scale, int fmt,
+                              sm_stream_t stream);
+int sm_quantize_compress24_fp8_f16(const void* A, size_t rows, size_t k, size_t lda, void* blob, float* row_scale, int fmt,
+                                   sm_stream_t stream);
+int sm_quantize_compress24_fp8_bf16(const void* A, size_t rows, size_t k, size_t lda, void* blob, float* row_scale, int fmt,
+                                    sm_stream_t stream);
+int sm_quantize_transpose_fp8_f16(const void* B, size_t k, size_t n, size_t ldb, float inv_scale, void* Bt, int fmt,
+                                  sm_stream_t stream);
+int sm_quantize_transpose_fp8_bf16(const void* B, size_t k, size_t n, size_t ldb, float inv_scale, void* Bt, int fmt,
+                                   sm_stream_t stream);
+
 /* ---- im2col front end (extension).  X: N x C x H x W activations (NCHW, contiguous).
  *      A: per image the row-major L x K operand of the layer's matmul, L = out_h * out_w rows (row oh * out_w + ow),
  *      K = C * kh * kw columns (column c * kh * kw + r * kw + u), images back to back -- the transpose of torch's

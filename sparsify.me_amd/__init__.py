@@ -149,6 +149,11 @@ _SIGS["sm_spmma_fused_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 8 + [_c_i, 
 _SIGS["sm_gemm_rowmajor_fp8"] = _SIGS["sm_spmma_fused_fp8"]
 _SIGS["sm_gemm_rowmajor_i8"] = _SIGS["sm_spmma_fused_i8"]
 _SIGS["sm_gemm_rowmajor_i8_q"] = _SIGS["sm_spmma_fused_i8_q"]
+# fp8 quantisation of 16-bit operands (quant_fp8.hip)
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_quantize_rows_fp8_" + _sfx16] = [_c_ptr, _c_size, _c_size, _c_size, _c_ptr, _c_size, _c_ptr, _c_i, _c_ptr]
+    _SIGS["sm_quantize_compress24_fp8_" + _sfx16] = [_c_ptr, _c_size, _c_size, _c_size, _c_ptr, _c_ptr, _c_i, _c_ptr]
+    _SIGS["sm_quantize_transpose_fp8_" + _sfx16] = [_c_ptr, _c_size, _c_size, _c_size, _c_f, _c_ptr, _c_i, _c_ptr]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -450,6 +455,47 @@ def gemm_rowmajor_fp8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB
     rs = _dev(row_scale) if row_scale is not None else None
     _check(lib().sm_gemm_rowmajor_fp8(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, fa, fb, ot, float(alpha),
                                       float(beta), rs, _stream()), "sm_gemm_rowmajor_fp8")
+
+
+def _quant_src_sfx(A, what):
+    torch = _t()
+    if A.dtype not in (torch.float16, torch.bfloat16):
+        raise SparsifymeError(f"{what}: the source is float16 or bfloat16, not {A.dtype}")
+    return _sfx(A)
+
+
+def _quant_row_scale(row_scale, what):
+    if row_scale.dtype != _t().float32:
+        raise SparsifymeError(f"{what}: row_scale is float32, not {row_scale.dtype}")
+    return _dev(row_scale)
+
+
+def quantize_rows_fp8(A, Q, row_scale, rows, k, lda=None, ldq=None):
+    """Per-row quantisation of a float16 / bfloat16 A (rows x k) to fp8 (the format of Q's dtype): Q rows x k bytes and
+    row_scale[rows] = amax / FMAX, what spmma_fp8 / gemm_rowmajor_fp8 take as row_scale."""
+    sfx = _quant_src_sfx(A, "quantize_rows_fp8")
+    fmt = fp8_format(Q.dtype)
+    rs = _quant_row_scale(row_scale, "quantize_rows_fp8")
+    fn = getattr(lib(), "sm_quantize_rows_fp8_" + sfx)
+    _check(fn(_dev(A), rows, k, k if lda is None else lda, _dev(Q), k if ldq is None else ldq, rs, fmt, _stream()), "sm_quantize_rows_fp8")
+
+
+def quantize_compress24_fp8(A, blob, row_scale, rows, k, fmt_dtype, lda=None):
+    """quantize_rows_fp8 + compress24_fp8 in one pass over A: blob of compress24_size(rows, k, 1, 1) bytes (fmt_dtype: the fp8
+    dtype, the blob does not carry it) and row_scale[rows]."""
+    sfx = _quant_src_sfx(A, "quantize_compress24_fp8")
+    fmt = fp8_format(fmt_dtype)
+    rs = _quant_row_scale(row_scale, "quantize_compress24_fp8")
+    fn = getattr(lib(), "sm_quantize_compress24_fp8_" + sfx)
+    _check(fn(_dev(A), rows, k, k if lda is None else lda, _dev(blob), rs, fmt, _stream()), "sm_quantize_compress24_fp8")
+
+
+def quantize_transpose_fp8(B, Bt, k, n, inv_scale, ldb=None):
+    """Row-major k x n float16 / bfloat16 B -> Bt [n][k] fp8 (the format of Bt's dtype), q = rne(clamp(b * inv_scale))."""
+    sfx = _quant_src_sfx(B, "quantize_transpose_fp8")
+    fmt = fp8_format(Bt.dtype)
+    fn = getattr(lib(), "sm_quantize_transpose_fp8_" + sfx)
+    _check(fn(_dev(B), k, n, n if ldb is None else ldb, float(inv_scale), _dev(Bt), fmt, _stream()), "sm_quantize_transpose_fp8")
 
 
 def gemm_rowmajor_i8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, accumulate=False):
