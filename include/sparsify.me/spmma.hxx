@@ -42,6 +42,14 @@ struct spmma_fns<float> {
   static int prune_mul(float*, float*, float*, std::size_t, std::size_t, std::size_t, std::size_t, int*, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // no one-kernel form for fp32 (no fp32 sparse matrix instruction: the 2:4 kernels expand)
   }
+  // the epilogue forms exist for the 16-bit types only (sm_spmma_*_ex)
+  static int fused_ex(float*, float*, float*, std::size_t, std::size_t, std::size_t, std::size_t, float, float, const sm_epilogue_t*, hipStream_t) {
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  static int mul_ex_on(const void*, float*, float*, std::size_t, std::size_t, std::size_t, std::size_t, std::size_t, float, float, const sm_epilogue_t*,
+                       hipStream_t) {
+    return SM_STATUS_NOT_SUPPORTED;
+  }
   // (round 4) the product on the sparse matrix instruction through exact bfloat16 splits (sm_spmma_fused_f32_split); ws: planes of B
   static int fused_split(float* A, float* B, float* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, int planes, void* ws,
                          std::size_t ws_bytes, float al, float be) {
@@ -89,6 +97,14 @@ struct spmma_fns_f16 {
   static int fused(void* A, void* B, void* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, float al, float be) {
     return sm_spmma_fused_f16(A, B, C, m, n, k, k, b, m * k, k * n, m * n, al, be, nullptr);
   }
+  static int fused_ex(void* A, void* B, void* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, float al, float be, const sm_epilogue_t* ep,
+                      hipStream_t st) {
+    return sm_spmma_fused_f16_ex(A, B, C, m, n, k, k, b, m * k, k * n, m * n, al, be, ep, st);
+  }
+  static int mul_ex_on(const void* blob, void* B, void* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, std::size_t sB, float al, float be,
+                       const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_spmma_f16_ex(blob, B, C, m, n, k, b, sB, m * n, al, be, ep, st);
+  }
   static int prune(void* A, std::size_t m, std::size_t k) { return sm_prune24_f16(A, A, m, k, k, SM_PRUNE_TILE, nullptr); }
   static int check(void* A, std::size_t m, std::size_t k, int* v) { return sm_prune24_check_f16(A, m, k, k, v, nullptr); }
   static int compress(void* A, std::size_t m, std::size_t k, std::size_t b, void* blob) { return sm_compress24_f16(A, m, k, k, b, m * k, blob, nullptr); }
@@ -121,6 +137,14 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
   }
   static int fused(void* A, void* B, void* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, float al, float be) {
     return sm_spmma_fused_bf16(A, B, C, m, n, k, k, b, m * k, k * n, m * n, al, be, nullptr);
+  }
+  static int fused_ex(void* A, void* B, void* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, float al, float be, const sm_epilogue_t* ep,
+                      hipStream_t st) {
+    return sm_spmma_fused_bf16_ex(A, B, C, m, n, k, k, b, m * k, k * n, m * n, al, be, ep, st);
+  }
+  static int mul_ex_on(const void* blob, void* B, void* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, std::size_t sB, float al, float be,
+                       const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_spmma_bf16_ex(blob, B, C, m, n, k, b, sB, m * n, al, be, ep, st);
   }
   static int prune(void* A, std::size_t m, std::size_t k) { return sm_prune24_bf16(A, A, m, k, k, SM_PRUNE_TILE, nullptr); }
   static int check(void* A, std::size_t m, std::size_t k, int* v) { return sm_prune24_check_bf16(A, m, k, k, v, nullptr); }
@@ -355,6 +379,49 @@ float spmma_fused(type_t* dA, type_t* dB, type_t* dC, std::size_t m, std::size_t
   return ms;
 }
 
+// Extension: the epilogue of the 16-bit 2:4 matmul (sm_epilogue_t, include/sparsifyme.h):
+//   D = act(alpha * A_2:4 . B + beta * residual + bias), fp32 until the one final rounding.
+// bias: fp32 device vector (bias_dim SM_BIAS_COL: n entries, SM_BIAS_ROW: m entries) or null; act: SM_ACT_*; residual: a device
+// matrix with D's layout (batches m * n apart), null: D itself when beta != 0 (what beta means without an epilogue).
+struct spmma_epilogue_t {
+  const float* bias = nullptr;
+  int bias_dim = SM_BIAS_COL;
+  int act = SM_ACT_NONE;
+  float act_arg = 0.0f;
+  const void* residual = nullptr;
+  sm_epilogue_t c_struct(const void* dC, std::size_t m, std::size_t n, float beta) const {
+    sm_epilogue_t e;
+    e.bias = bias; e.bias_dim = bias_dim; e.act = act; e.act_arg = act_arg;
+    e.R = residual ? residual : (beta != 0.0f ? dC : nullptr);
+    e.strideR = m * n;
+    return e;
+  }
+};
+
+// spmma_fused with an epilogue (fp16 / bfloat16).  As above a shape the fused kernels cannot take runs as sm_compress24 + sm_spmma_*_ex
+// with a temporary blob: the same D bit for bit.  Blocking; returns the elapsed milliseconds.
+template <typename type_t>
+float spmma_fused(type_t* dA, type_t* dB, type_t* dC, std::size_t m, std::size_t n, std::size_t k, std::size_t batch_size,
+                  const spmma_epilogue_t& epilogue, float alpha = 1.0f, float beta = 0.0f) {
+  using fns = detail::spmma_fns<type_t>;
+  if (batch_size == 0) batch_size = 1;
+  const sm_epilogue_t e = epilogue.c_struct(dC, m, n, beta);
+  util::timer_t timer;
+  timer.begin();
+  int rc = fns::fused_ex(dA, dB, dC, m, n, k, batch_size, alpha, beta, &e, nullptr);
+  if (rc == SM_STATUS_NOT_SUPPORTED && sizeof(type_t) == 2) {
+    std::size_t compressed_size = 0;
+    (void)sm_compress24_size(m, k, sizeof(type_t), batch_size, &compressed_size);
+    device_vector<unsigned char> compressed(compressed_size);
+    rc = fns::compress(dA, m, k, batch_size, compressed.data().get());
+    if (rc == SM_STATUS_SUCCESS) rc = fns::mul_ex_on(compressed.data().get(), dB, dC, m, n, k, batch_size, k * n, alpha, beta, &e, nullptr);
+    (void)hipStreamSynchronize(nullptr);  // the blob is released when this scope ends
+  }
+  const float ms = timer.end();
+  if (rc != SM_STATUS_SUCCESS) std::cerr << "sparsifyme::spmma_fused: " << sm_last_error() << std::endl;
+  return ms;
+}
+
 // Extension of this build ("cached-plan API"): the reference builds handle, descriptors, plan
 // and the compressed blob inside every spmma() call and times the allocation (spmma.hxx:51-80,101).  A plan owns the
 // blob for one (m, k, batch) operand: compress() once (optionally pruning A in place first, as spmma() does), then
@@ -391,6 +458,14 @@ class spmma_plan_t {
     using fns = detail::spmma_fns<type_t>;
     if (!ready_) return SM_STATUS_INVALID_VALUE;
     return fns::mul_on(blob_.data().get(), dB, dC, m_, n, k_, batch_, strideB < 0 ? k_ * n : (std::size_t)strideB, alpha, beta, stream);
+  }
+  // the same with an epilogue (fp16 / bfloat16): D_b = act(alpha * A_b(2:4) * B_b + beta * residual_b + bias)
+  int multiply(type_t* dB, type_t* dC, std::size_t n, const spmma_epilogue_t& epilogue, float alpha = 1.0f, float beta = 0.0f, hipStream_t stream = nullptr,
+               std::ptrdiff_t strideB = -1) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_) return SM_STATUS_INVALID_VALUE;
+    const sm_epilogue_t e = epilogue.c_struct(dC, m_, n, beta);
+    return fns::mul_ex_on(blob_.data().get(), dB, dC, m_, n, k_, batch_, strideB < 0 ? k_ * n : (std::size_t)strideB, alpha, beta, &e, stream);
   }
 
  private:

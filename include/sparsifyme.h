@@ -225,6 +225,64 @@ int sm_spmma_fused_bf16_grouped_ws(size_t count, const void* const* A, const voi
                                    size_t k, size_t lda, size_t batch, size_t strideA, size_t strideB, size_t strideC,
                                    float alpha, float beta, void* workspace, size_t workspace_bytes, sm_stream_t stream);
 
+/* ---- Epilogues of the 16-bit 2:4 matmul (extension): the layer  activation(conv(x) + bias [+ shortcut])  in the matmul's own
+ *      store instead of one or two more passes over the output.
+ *
+ *          D[i][j] = round_to_out( act( alpha * (A_2:4 . B)[i][j] + beta * R[i][j] + bias ) )
+ *
+ *      Everything between the fp32 accumulator and the final conversion is fp32 (alpha * acc + beta * R evaluated exactly as the
+ *      plain entry points evaluate alpha * acc + beta * C; the bias is a separate addition after it); ONE rounding, to nearest
+ *      even, to fp16 / bf16 at the end.
+ *      R      the shortcut: a 16-bit matrix with the shape, the leading dimension (n) and the batch rule of D, given by its own
+ *             pointer and batch stride (elements).  R == D (same pointer, same stride) is allowed: in place, what beta means in
+ *             the plain entry points; any other overlap of R and D is undefined.  Not read when beta == 0 (may then be NULL).
+ *      bias   fp32 device vector or NULL.  bias_dim = SM_BIAS_COL: n entries, one per output column (the output channel in this
+ *             project's layout: A the im2col operand, B the weights); SM_BIAS_ROW: m entries indexed by row % m when batches are
+ *             stacked (the rule row_scale follows in the fp8 product: the vendor orientation, sparse weights as A).
+ *      act    SM_ACT_NONE; SM_ACT_RELU max(x, 0); SM_ACT_CLIPPED_RELU min(max(x, 0), act_arg) (ReLU6: act_arg = 6);
+ *             SM_ACT_LEAKY_RELU x >= 0 ? x : act_arg * x; SM_ACT_HARDSWISH x * min(max(x + 3, 0), 6) * (1/6).  Plain fp32
+ *             arithmetic.  NaN in, NaN out for every activation; max(-0, 0) is +0 (ReLU, clipped ReLU and the inner clamp of
+ *             hardswish return +0 for every x <= 0 that is not NaN, -0 included; leaky ReLU returns -0 for -0).
+ *             GELU / SiLU / sigmoid are NOT offered: none of the layer tables this library is measured on uses them, and the
+ *             device exp / erf they need would bring an error bound that has to be measured rather than derived.
+ *      The struct is read during the call (host memory); a NULL struct pointer, or one that says "no bias, SM_ACT_NONE, R == D
+ *      (or beta == 0)", IS the plain entry point: same kernels, same bits.
+ *      Status, decided before any device work: unknown act / bias_dim, beta != 0 with R == NULL, a non-finite or negative
+ *      act_arg for the clipped form: SM_STATUS_INVALID_VALUE; a shape the plain entry point does not take: what it returns.
+ *      The calls only enqueue on `stream` (hipGraph-capturable).
+ *      sm_spmma_*_ex takes every shape sm_spmma_* takes.  sm_spmma_fused_*_ex takes the EXACT forms of sm_spmma_fused_* (the
+ *      shapes of the direct, big, wide, A-stationary and span kernels; with an epilogue the A-stationary and persistent-wide
+ *      shapes run the wide kernel, whose store is the shared one: same bits) and is bit-identical to sm_compress24 + sm_spmma_*_ex;
+ *      the span form additionally needs a 16-byte aligned R with strideR == m * n when it is read.  The THIN form (n < 8) with a
+ *      non-trivial epilogue: SM_STATUS_NOT_SUPPORTED.
+ *      Not covered yet (they share the routine and can follow): the grouped and _ws (stream-K) forms, sm_prune24_spmma_*,
+ *      sm_conv_spmma_*, fp32, int8 and fp8. */
+#define SM_BIAS_COL 0
+#define SM_BIAS_ROW 1
+#define SM_ACT_NONE 0
+#define SM_ACT_RELU 1
+#define SM_ACT_CLIPPED_RELU 2
+#define SM_ACT_LEAKY_RELU 3
+#define SM_ACT_HARDSWISH 4
+typedef struct {
+  const float* bias; /* device, fp32; NULL: none */
+  int bias_dim;      /* SM_BIAS_COL / SM_BIAS_ROW */
+  int act;           /* SM_ACT_* */
+  float act_arg;     /* upper clip (SM_ACT_CLIPPED_RELU) / negative slope (SM_ACT_LEAKY_RELU) */
+  const void* R;     /* device, the type of D; NULL allowed when beta == 0 */
+  size_t strideR;    /* batch stride of R (elements) */
+} sm_epilogue_t;
+int sm_spmma_f16_ex(const void* blob, const void* B, void* D, size_t m, size_t n, size_t k, size_t batch, size_t strideB,
+                    size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_spmma_bf16_ex(const void* blob, const void* B, void* D, size_t m, size_t n, size_t k, size_t batch, size_t strideB,
+                     size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_spmma_fused_f16_ex(const void* A, const void* B, void* D, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                          size_t strideA, size_t strideB, size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue,
+                          sm_stream_t stream);
+int sm_spmma_fused_bf16_ex(const void* A, const void* B, void* D, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                           size_t strideA, size_t strideB, size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue,
+                           sm_stream_t stream);
+
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +
  * sm_spmma_f32 to fp32 accumulation order.  Needs k % 32 == 0, n % 4 == 0, 16-byte aligned rows. */

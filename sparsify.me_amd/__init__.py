@@ -154,6 +154,10 @@ for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_quantize_rows_fp8_" + _sfx16] = [_c_ptr, _c_size, _c_size, _c_size, _c_ptr, _c_size, _c_ptr, _c_i, _c_ptr]
     _SIGS["sm_quantize_compress24_fp8_" + _sfx16] = [_c_ptr, _c_size, _c_size, _c_size, _c_ptr, _c_ptr, _c_i, _c_ptr]
     _SIGS["sm_quantize_transpose_fp8_" + _sfx16] = [_c_ptr, _c_size, _c_size, _c_size, _c_f, _c_ptr, _c_i, _c_ptr]
+# bias / activation / residual epilogues of the 16-bit 2:4 matmul: the plain signature with a `const sm_epilogue_t*` before the stream
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_spmma_%s_ex" % _sfx16] = _SIGS["sm_spmma_f16"][:-1] + [_c_ptr, _c_ptr]
+    _SIGS["sm_spmma_fused_%s_ex" % _sfx16] = _SIGS["sm_spmma_fused_f16"][:-1] + [_c_ptr, _c_ptr]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -334,10 +338,68 @@ def decompress24(blob, m, k, ld, batch, strideA, A):
     _check(fn(_dev(blob), m, k, ld, batch, strideA, _dev(A), _stream()), "sm_decompress24")
 
 
-def spmma(blob, B, C, m, n, k, batch=1, strideB=0, strideC=None, alpha=1.0, beta=0.0):
-    """The matmul step of sparsifyme::spmma (spmma.hxx:112-113) on a compressed blob."""
+BIAS_COL, BIAS_ROW = 0, 1
+ACT_NONE, ACT_RELU, ACT_CLIPPED_RELU, ACT_LEAKY_RELU, ACT_HARDSWISH = 0, 1, 2, 3, 4
+_BIAS_DIMS = {"col": BIAS_COL, "row": BIAS_ROW}
+_ACTS = {"none": ACT_NONE, "relu": ACT_RELU, "clipped_relu": ACT_CLIPPED_RELU, "relu6": ACT_CLIPPED_RELU, "leaky_relu": ACT_LEAKY_RELU,
+         "hardswish": ACT_HARDSWISH}
+
+
+class EpilogueStruct(ctypes.Structure):
+    """sm_epilogue_t (include/sparsifyme.h)"""
+    _fields_ = [("bias", _c_ptr), ("bias_dim", _c_i), ("act", _c_i), ("act_arg", _c_f), ("R", _c_ptr), ("strideR", _c_size)]
+
+
+class Epilogue:
+    """What spmma(..., epilogue=) / spmma_fused(..., epilogue=) apply in the matmul's store:
+    D = act(alpha * A.B + beta * residual + bias), fp32 until the one final rounding (sm_epilogue_t, include/sparsifyme.h).
+    bias: float32 device vector (bias_dim "col": n entries, "row": m entries) or None; act: "none", "relu", "clipped_relu"
+    ("relu6": clipped with act_arg 6), "leaky_relu", "hardswish", or an ACT_* number; residual: a device tensor of D's dtype with D's
+    layout (None: D itself when beta != 0, what beta means without an epilogue); stride_residual: its batch stride (default m * n)."""
+
+    def __init__(self, bias=None, bias_dim="col", act="none", act_arg=0.0, residual=None, stride_residual=None):
+        if bias is not None and bias.dtype != _t().float32:
+            raise SparsifymeError(f"Epilogue: bias is float32, not {bias.dtype}")
+        if isinstance(bias_dim, str):
+            if bias_dim not in _BIAS_DIMS:
+                raise SparsifymeError(f"Epilogue: bias_dim is 'col' or 'row', not {bias_dim!r}")
+            bias_dim = _BIAS_DIMS[bias_dim]
+        if isinstance(act, str):
+            if act not in _ACTS:
+                raise SparsifymeError(f"Epilogue: unknown activation {act!r} (one of {sorted(_ACTS)})")
+            if act == "relu6" and not act_arg:
+                act_arg = 6.0
+            act = _ACTS[act]
+        self.bias, self.bias_dim, self.act, self.act_arg = bias, int(bias_dim), int(act), float(act_arg)
+        self.residual, self.stride_residual = residual, stride_residual
+
+    def struct_for(self, D, strideD, beta):
+        """The C struct for a call that writes D (dtype checks first, then the pointers)."""
+        if self.residual is not None and self.residual.dtype != D.dtype:
+            raise SparsifymeError(f"Epilogue: residual is {self.residual.dtype}, the output is {D.dtype}")
+        st = EpilogueStruct()
+        st.bias = _dev(self.bias) if self.bias is not None else None
+        st.bias_dim, st.act, st.act_arg = self.bias_dim, self.act, self.act_arg
+        if self.residual is not None:
+            st.R = _dev(self.residual)
+            st.strideR = strideD if self.stride_residual is None else self.stride_residual
+        elif beta != 0.0:
+            st.R, st.strideR = _dev(D), strideD
+        else:
+            st.R, st.strideR = None, 0
+        return st
+
+
+def spmma(blob, B, C, m, n, k, batch=1, strideB=0, strideC=None, alpha=1.0, beta=0.0, epilogue=None):
+    """The matmul step of sparsifyme::spmma (spmma.hxx:112-113) on a compressed blob; epilogue: an Epilogue (sm_spmma_*_ex)."""
     if strideC is None:
         strideC = m * n
+    if epilogue is not None:
+        st = epilogue.struct_for(C, strideC, float(beta))
+        fn = getattr(lib(), "sm_spmma_%s_ex" % _sfx(B))
+        _check(fn(_dev(blob), _dev(B), _dev(C), m, n, k, batch, strideB, strideC, float(alpha), float(beta), ctypes.addressof(st), _stream()),
+               "sm_spmma_ex")
+        return
     fn = getattr(lib(), "sm_spmma_" + _sfx(B))
     _check(fn(_dev(blob), _dev(B), _dev(C), m, n, k, batch, strideB, strideC, float(alpha), float(beta), _stream()),
            "sm_spmma")
@@ -559,12 +621,22 @@ def spmma_fused_workspace():
     return _t().zeros(spmma_fused_workspace_size(), dtype=_t().uint8, device="cuda")
 
 
-def spmma_fused(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, alpha=1.0, beta=0.0, workspace=None):
+def spmma_fused(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, alpha=1.0, beta=0.0, workspace=None,
+                epilogue=None):
     """Fused prune(STRIP) + compress + 2:4 matmul straight from the dense A (no blob).  workspace (spmma_fused_workspace()): the
-    library may run the stream-K form where whole-tile rounds leave CUs idle."""
+    library may run the stream-K form where whole-tile rounds leave CUs idle.  epilogue: an Epilogue (sm_spmma_fused_*_ex; not with a
+    workspace)."""
     lda = k if lda is None else lda
     strideA = m * lda if strideA is None else strideA
     strideC = m * n if strideC is None else strideC
+    if epilogue is not None:
+        if workspace is not None:
+            raise SparsifymeError("spmma_fused: the workspace (stream-K) form takes no epilogue")
+        st = epilogue.struct_for(C, strideC, float(beta))
+        fn = getattr(lib(), "sm_spmma_fused_%s_ex" % _sfx(A))
+        _check(fn(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, float(alpha), float(beta), ctypes.addressof(st),
+                  _stream()), "sm_spmma_fused_ex")
+        return
     if workspace is not None:
         fn = getattr(lib(), "sm_spmma_fused_%s_ws" % _sfx(A))
         _check(fn(_dev(A), _dev(B), _dev(C), m, n, k, lda, batch, strideA, strideB, strideC, float(alpha), float(beta), _dev(workspace),

@@ -303,6 +303,178 @@ __device__ __forceinline__ void store_c_tile(char* smem, half_t* C, const f4 (&a
   }
 }
 
+// ---- the epilogue of the sm_spmma_*_ex entry points: D = act(alpha * acc + beta * R + bias), everything in fp32, one rounding.
+// Device-side image of sm_epilogue_t (include/sparsifyme.h); R and sR are always set by the host (R = D, sR = strideD when the
+// caller gave none and beta == 0: never read then).
+struct EpiArgs {
+  const float* bias;  // null: none
+  const half_t* R;    // the residual operand, read when beta != 0 (shape, leading dimension and batch rule of D)
+  size_t sR;          // its batch stride (elements)
+  int bias_dim;       // SM_BIAS_COL: bias[column]; SM_BIAS_ROW: bias[row % m]
+  int act;            // SM_ACT_*
+  float act_arg;
+  int m;              // rows per batch (the SM_BIAS_ROW index of stacked batches)
+};
+
+// The activation on the four accumulator rows a lane holds of one fragment column.  Comparisons are written so that a NaN falls
+// through every branch unchanged (v_max_f32 would return the other operand), and max(-0, 0) is +0.  No contraction: the same
+// operations in every kernel that calls it.
+__device__ __forceinline__ f4 epi_act4(f4 x, int act, float arg) {
+#pragma clang fp contract(off)
+  f4 y = x;
+  switch (act) {
+    case SM_ACT_RELU:
+#pragma unroll
+      for (int q = 0; q < 4; ++q) y[q] = x[q] > 0.0f ? x[q] : (x[q] == x[q] ? 0.0f : x[q]);
+      break;
+    case SM_ACT_CLIPPED_RELU:
+#pragma unroll
+      for (int q = 0; q < 4; ++q) y[q] = x[q] > 0.0f ? (x[q] < arg ? x[q] : arg) : (x[q] == x[q] ? 0.0f : x[q]);
+      break;
+    case SM_ACT_LEAKY_RELU:
+#pragma unroll
+      for (int q = 0; q < 4; ++q) y[q] = x[q] >= 0.0f ? x[q] : arg * x[q];
+      break;
+    case SM_ACT_HARDSWISH:
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float t = x[q] + 3.0f;
+        t = t > 0.0f ? (t < 6.0f ? t : 6.0f) : (t == t ? 0.0f : t);
+        y[q] = (x[q] * t) * (1.0f / 6.0f);
+      }
+      break;
+    default: break;
+  }
+  return y;
+}
+
+// The bias add as an addition of its own (never contracted into alpha * acc + beta * R), skipped when there is no bias so that
+// a -0 stays -0.
+__device__ __forceinline__ f4 epi_bias4(f4 v, bool bias_col, float bj, bool bias_row, f4 bi) {
+#pragma clang fp contract(off)
+  if (bias_col) v += bj;
+  if (bias_row) v += bi;
+  return v;
+}
+
+// store_c_tile with the epilogue above; same contract (every thread of the workgroup, after its last barrier; `smem` is the
+// BM x (2 BN + 16)-byte transpose buffer that aliases the stage buffers).  The 16-byte path is kept WITH a residual: whenever D
+// (and R, when it is read) are 16-byte aligned and N % 8 == 0, all NT threads bring the R tile into the transpose buffer with
+// 16-byte loads, and after a barrier each accumulator lane reads its own element from LDS, computes in fp32 and writes the
+// rounded result to the same address (one lane per address, so no further barrier between the read and the write); then the
+// rows leave as 16-byte non-temporal stores as in store_c_tile.  No LDS beyond what store_c_tile uses, so the workgroups per CU
+// are those of the plain kernels.  alpha * acc + beta * R is evaluated exactly as store_c_tile does (R == D, beta != 0 gives
+// its bits); bias is added after it, then the activation.  R may be D itself (a workgroup reads its R tile before it writes
+// its D tile, and tiles are disjoint); any other overlap of R and D is undefined.
+// The bias values an accumulator lane needs -- one per fragment column (SM_BIAS_COL) or four per fragment row (SM_BIAS_ROW), in
+// one array of max(FN, 4 FM) registers -- are fetched by epi_bias_prefetch BEFORE the K loop, so that their latency is hidden
+// under it (fetched at the top of the epilogue they cost a short-K tile an exposed memory round trip: 784 x 1024 x 256 ran 1.6 x
+// the plain call with bias + ReLU).  The plain loads are older than every LDS-DMA piece of the rings, so the kernels' counted
+// vmcnt waits cover them.
+template <int FM, int FN>
+struct EpiBias {
+  static constexpr int NV = FN > 4 * FM ? FN : 4 * FM;
+  float v[NV];
+};
+template <int FM, int FN>
+__device__ __forceinline__ EpiBias<FM, FN> epi_bias_prefetch(const EpiArgs& e, bool has_acc, unsigned row0, unsigned col0, int m0, int n0, int Mrows,
+                                                            int N, unsigned lane) {
+  EpiBias<FM, FN> eb;
+  const unsigned g = lane >> 4, r = lane & 15u;
+#pragma unroll
+  for (int t = 0; t < EpiBias<FM, FN>::NV; ++t) eb.v[t] = 0.0f;
+  if (has_acc && e.bias != nullptr) {
+    if (e.bias_dim == SM_BIAS_COL) {
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const int gc = n0 + (int)(col0 + j * 16 + r);
+        if (gc < N) eb.v[j] = e.bias[gc];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int gr = m0 + (int)(row0 + i * 16 + 4u * g) + q;
+          if (gr < Mrows) eb.v[4 * i + q] = e.bias[gr % e.m];
+        }
+    }
+  }
+  return eb;
+}
+
+template <int BM, int BN, int FM, int FN, int NT, bool BF = false>
+__device__ __forceinline__ void store_c_tile_epi(char* smem, half_t* C, const half_t* R, const EpiArgs& e, const EpiBias<FM, FN>& eb,
+                                                 const f4 (&acc)[FM][FN], bool has_acc, unsigned row0, unsigned col0, int m0, int n0,
+                                                 int Mrows, int N, float alpha, float beta, unsigned tid) {
+  constexpr int CPITCH = BN * 2 + 16;
+  const unsigned lane = tid & 63u, g = lane >> 4, r = lane & 15u;
+  const bool use_r = beta != 0.0f;
+  const bool c_vec = (reinterpret_cast<uintptr_t>(C) & 15u) == 0 && (N % 8 == 0) && (!use_r || (reinterpret_cast<uintptr_t>(R) & 15u) == 0);
+  const bool bias_col = e.bias != nullptr && e.bias_dim == SM_BIAS_COL, bias_row = e.bias != nullptr && e.bias_dim == SM_BIAS_ROW;
+  constexpr int NCH = BM * (BN / 8);
+  if (c_vec) {
+    if (use_r) {
+      for (unsigned q = tid; q < (unsigned)NCH; q += (unsigned)NT) {
+        const unsigned row = q / (BN / 8), cn = q % (BN / 8);
+        const int gr = m0 + (int)row, gc = n0 + 8 * (int)cn;
+        if (gr >= Mrows || gc >= N) continue;
+        // R is read once by the whole grid, like A: non-temporal
+        *reinterpret_cast<u4*>(smem + row * CPITCH + cn * 16) = __builtin_nontemporal_load(reinterpret_cast<const u4*>(R + (size_t)gr * N + gc));
+      }
+      __syncthreads();
+    }
+    if (has_acc) {
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          const unsigned row = row0 + i * 16 + 4u * g, col = col0 + j * 16 + r;
+          f4 v4;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            // (rows / columns past the matrix edge hold whatever the stage buffers left: computed, never stored)
+            float v = alpha * acc[i][j][q];
+            if (use_r) v += beta * to_f32<BF>(*reinterpret_cast<const half_t*>(smem + (row + q) * CPITCH + col * 2));
+            v4[q] = v;
+          }
+          v4 = epi_act4(epi_bias4(v4, bias_col, eb.v[j < EpiBias<FM, FN>::NV ? j : 0], bias_row, f4{eb.v[4 * i], eb.v[4 * i + 1], eb.v[4 * i + 2], eb.v[4 * i + 3]}), e.act, e.act_arg);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) *reinterpret_cast<half_t*>(smem + (row + q) * CPITCH + col * 2) = to_elt<BF>(v4[q]);
+        }
+    }
+    __syncthreads();
+    for (unsigned q = tid; q < (unsigned)NCH; q += (unsigned)NT) {
+      const unsigned row = q / (BN / 8), cn = q % (BN / 8);
+      const int gr = m0 + (int)row, gc = n0 + 8 * (int)cn;
+      if (gr >= Mrows || gc >= N) continue;  // N % 8 == 0: a chunk is all in or all out
+      __builtin_nontemporal_store(*reinterpret_cast<const u4*>(smem + row * CPITCH + cn * 16), reinterpret_cast<u4*>(C + (size_t)gr * N + gc));
+    }
+  } else if (has_acc) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const int gc = n0 + (int)(col0 + j * 16 + r);
+        if (gc >= N) continue;
+        f4 v4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int gr = m0 + (int)(row0 + i * 16 + 4u * g) + q;
+          float v = alpha * acc[i][j][q];
+          if (use_r && gr < Mrows) v += beta * to_f32<BF>(R[(size_t)gr * N + gc]);
+          v4[q] = v;
+        }
+        v4 = epi_act4(epi_bias4(v4, bias_col, eb.v[j < EpiBias<FM, FN>::NV ? j : 0], bias_row, f4{eb.v[4 * i], eb.v[4 * i + 1], eb.v[4 * i + 2], eb.v[4 * i + 3]}), e.act, e.act_arg);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int gr = m0 + (int)(row0 + i * 16 + 4u * g) + q;
+          if (gr < Mrows) C[(size_t)gr * N + gc] = to_elt<BF>(v4[q]);
+        }
+      }
+  }
+}
+
 // XCD-aware bijective remap of a linear workgroup id: blocks that share an XCD (ids equal mod 8)
 // receive a contiguous range of logical ids, so tiles that re-read the same operand panel sit on
 // one L2 (speed only; any placement is correct).

@@ -24,6 +24,44 @@ struct SpmmaArgs {
   float alpha, beta;
 };
 
+// The argument block of the kernels' epilogue instantiations (sm_spmma_*_ex): the plain block + the epilogue.  The plain
+// instantiations keep taking SpmmaArgs itself, so their code is what it was.
+struct SpmmaArgsEpi : SpmmaArgs {
+  EpiArgs e;
+};
+template <bool EPI> struct SpmmaArgsSel { typedef SpmmaArgs type; };
+template <> struct SpmmaArgsSel<true> { typedef SpmmaArgsEpi type; };
+
+// sm_epilogue_t -> EpiArgs for one problem (D, strideD, rows per batch m), with the argument checks of the _ex entry points
+// (include/sparsifyme.h).  *plain: the epilogue is the plain entry point's (no bias, no activation, R == D or not read).
+inline int epilogue_args(const sm_epilogue_t* ep, const void* D, size_t strideD, size_t m, float beta, EpiArgs& e, bool* plain, const char* who) {
+  e = EpiArgs{nullptr, (const half_t*)D, strideD, SM_BIAS_COL, SM_ACT_NONE, 0.0f, (int)(m ? m : 1)};
+  *plain = true;
+  if (!ep) return SM_STATUS_SUCCESS;
+  if (ep->act < SM_ACT_NONE || ep->act > SM_ACT_HARDSWISH || (ep->bias_dim != SM_BIAS_COL && ep->bias_dim != SM_BIAS_ROW)) {
+    set_error("%s: invalid epilogue (unknown act or bias_dim)", who);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  if (beta != 0.0f && !ep->R) {
+    set_error("%s: invalid epilogue (beta != 0 needs the residual operand R)", who);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  if (ep->act == SM_ACT_CLIPPED_RELU && !(ep->act_arg >= 0.0f && ep->act_arg <= 3.4028234663852886e38f)) {
+    set_error("%s: invalid epilogue (the clipped ReLU needs a finite act_arg >= 0)", who);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  e.bias = ep->bias;
+  e.bias_dim = ep->bias_dim;
+  e.act = ep->act;
+  e.act_arg = ep->act_arg;
+  if (beta != 0.0f) {
+    e.R = (const half_t*)ep->R;
+    e.sR = ep->strideR;
+  }
+  *plain = !ep->bias && ep->act == SM_ACT_NONE && (beta == 0.0f || (ep->R == D && ep->strideR == strideD));
+  return SM_STATUS_SUCCESS;
+}
+
 // The dense twin (spmma_f16_fused.hip): C = alpha * A * B + beta * C, row-major, dense, through the pipelines of the fused 2:4
 // kernels (direct / big / span) with dense MFMA in place of selection + SMFMAC -- so that the dense GEMM the 2:4 path is measured
 // against is not held back by a weaker pipeline on the shapes where those pipelines are the better ones (ragged k: the span form;

@@ -19,8 +19,10 @@ namespace sm {
 __device__ __attribute__((aligned(256))) const unsigned char sm_zero_page[256] = {0};
 
 
-template <int BM, int BN, int WM, int WN, bool BF = false>
-__global__ __launch_bounds__(256) void spmma_f16_kernel(const SpmmaArgs p) {
+// (EPI, here and below: the sm_spmma_*_ex instantiation -- the argument block carries the epilogue and the store is
+// store_c_tile_epi; the plain instantiations are untouched)
+template <int BM, int BN, int WM, int WN, bool BF = false, bool EPI = false>
+__global__ __launch_bounds__(256) void spmma_f16_kernel(const typename SpmmaArgsSel<EPI>::type p) {
   static_assert(WM * WN == 4, "4 waves");
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
   constexpr int A_CH = BM * 8 / 256;        // 16-byte value chunks per thread per stage
@@ -54,6 +56,8 @@ __global__ __launch_bounds__(256) void spmma_f16_kernel(const SpmmaArgs p) {
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
 
+  EpiBias<FM, FN> eb;  // (EPI: the lane's bias values, fetched ahead of the K loop)
+  if constexpr (EPI) eb = epi_bias_prefetch<FM, FN>(p.e, true, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, lane);
   u4 ra[A_CH], rb[B_CH];
   u2 rm[M_CH];
   const bool b_vec = (p.N % 8 == 0) && ((reinterpret_cast<uintptr_t>(B) & 15u) == 0);
@@ -158,6 +162,10 @@ __global__ __launch_bounds__(256) void spmma_f16_kernel(const SpmmaArgs p) {
     __syncthreads();
   }
 
+  if constexpr (EPI) {  // (the loop above ends with a barrier: every wave has left the stage images the transpose buffer aliases)
+    store_c_tile_epi<BM, BN, FM, FN, 256, BF>(smem, C, p.e.R + (size_t)b * p.e.sR, p.e, eb, acc, true, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+    return;
+  }
   // ---- epilogue: lane holds C[rows 4*(lane>>4) + r][col lane&15] of each fragment
   const bool c_vec = (p.N % 8 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15u) == 0);
   if (p.beta == 0.0f && c_vec) {
@@ -220,8 +228,8 @@ __global__ __launch_bounds__(256) void spmma_f16_kernel(const SpmmaArgs p) {
 // ---------------------------------------------------------------------------------------------
 
 
-template <int BM, int BN, int WM, int WN, int NS, bool BF = false>
-__global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const SpmmaArgs p) {
+template <int BM, int BN, int WM, int WN, int NS, bool BF = false, bool EPI = false>
+__global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const typename SpmmaArgsSel<EPI>::type p) {
   constexpr int NW = WM * WN;  // waves per workgroup: 4 for big grids, 8 / 16 when few tiles exist
   static_assert(NW == 4 || NW == 8 || NW == 16, "4, 8 or 16 waves");
   static_assert(NS >= 2 && NS <= 4, "ring depth");
@@ -254,6 +262,8 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const Spmma
   const half_t* B = p.B[grp] + (size_t)b * p.sB;
   half_t* C = p.C[grp] + (size_t)b * p.sC;
   const int mlast = p.Mrows - 1;
+  EpiBias<FM, FN> eb;  // (EPI: the lane's bias values, fetched ahead of the K loop)
+  if constexpr (EPI) eb = epi_bias_prefetch<FM, FN>(p.e, true, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, lane);
 
   // per-slot source address of stage 0 (advanced by `step` bytes per stage) and LDS offset in a stage
   const char* src[SL];
@@ -336,7 +346,8 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const Spmma
   }
   __syncthreads();  // nothing is in flight here: the last NS-1 iterations issued no DMA
 
-  store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  if constexpr (EPI) store_c_tile_epi<BM, BN, FM, FN, 64 * NW, BF>(smem, C, p.e.R + (size_t)b * p.e.sR, p.e, eb, acc, true, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  else store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -351,8 +362,8 @@ __global__ __launch_bounds__(64 * WM * WN) void spmma_f16_dma_kernel(const Spmma
 //   consumer:                                 barrier kt | compute stage kt
 // so the transfer of stages kt+1 .. kt+NS-1 runs under the compute of stage kt.
 // ---------------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, int NL, int NS, bool BF = false>
-__global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const SpmmaArgs p) {
+template <int BM, int BN, int WM, int WN, int NL, int NS, bool BF = false, bool EPI = false>
+__global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const typename SpmmaArgsSel<EPI>::type p) {
   constexpr int NC = WM * WN, NW = NC + NL;
   static_assert(NS >= 2 && NS <= 6, "ring depth");
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
@@ -384,6 +395,8 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
   const unsigned wm = wave / WN, wn = wave % WN;  // meaningful for consumer waves only
+  EpiBias<FM, FN> eb;  // (EPI: the lane's bias values, fetched ahead of the K loop)
+  if constexpr (EPI) eb = epi_bias_prefetch<FM, FN>(p.e, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, lane);
 
   if (wave >= (unsigned)NC) {
     // ------------------------------------------------------------------ loader wave
@@ -469,7 +482,8 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const
   __syncthreads();  // both roles; nothing is in flight (the last NS-1 loader iterations issued no DMA)
 
   // ---- epilogue: consumers stage their fragments, every wave (loaders too) stores 16-byte row pieces
-  store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  if constexpr (EPI) store_c_tile_epi<BM, BN, FM, FN, 64 * NW, BF>(smem, C, p.e.R + (size_t)b * p.e.sR, p.e, eb, acc, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  else store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
 }
 
 // (A variant of this kernel with the consumers' operand reads pipelined across stages -- ring of 4, the next stage's A
@@ -477,9 +491,9 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const
 // measured in round 2: bit-identical, and 1.4 x SLOWER on every few-tile shape (196x512x4608: 51 vs 37 us,
 // profiles/tune_pc2_r02i.txt), with or without the deeper look-ahead.  Exposed LDS latency in the consumers is therefore
 // not what bounds this kernel; the variant is in the git history, not in the library.)
-template <int BM, int BN, int WM, int WN, int NL, int NS, bool BF = false>
-static int launch_pc(const SpmmaArgs& a0, hipStream_t st) {
-  SpmmaArgs a = a0;
+template <int BM, int BN, int WM, int WN, int NL, int NS, bool BF = false, bool EPI = false>
+static int launch_pc(const typename SpmmaArgsSel<EPI>::type& a0, hipStream_t st) {
+  typename SpmmaArgsSel<EPI>::type a = a0;
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -496,15 +510,15 @@ static int launch_pc(const SpmmaArgs& a0, hipStream_t st) {
   const size_t lds_launch = used > lds_epi ? used : lds_epi;
   static LdsOptIn lds_optin;
   if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF>), lds, "spmma_f16_pc_kernel")) return rc;
+    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF, EPI>), lds, "spmma_f16_pc_kernel")) return rc;
   }
-  spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + NL)), lds_launch, st>>>(a);
+  spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF, EPI><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + NL)), lds_launch, st>>>(a);
   return check_launch("spmma_f16_pc_kernel");
 }
 
-template <int BM, int BN, int WM, int WN, int NS, bool BF = false>
-static int launch_dma(const SpmmaArgs& a0, hipStream_t st) {
-  SpmmaArgs a = a0;
+template <int BM, int BN, int WM, int WN, int NS, bool BF = false, bool EPI = false>
+static int launch_dma(const typename SpmmaArgsSel<EPI>::type& a0, hipStream_t st) {
+  typename SpmmaArgsSel<EPI>::type a = a0;
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -521,15 +535,15 @@ static int launch_dma(const SpmmaArgs& a0, hipStream_t st) {
   const size_t lds_launch = used > lds_epi ? used : lds_epi;
   static LdsOptIn lds_optin;
   if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF>), lds, "spmma_f16_dma_kernel")) return rc;
+    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF, EPI>), lds, "spmma_f16_dma_kernel")) return rc;
   }
-  spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds_launch, st>>>(a);
+  spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF, EPI><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds_launch, st>>>(a);
   return check_launch("spmma_f16_dma_kernel");
 }
 
-template <int BM, int BN, int WM, int WN, bool BF = false>
-static int launch_cfg(const SpmmaArgs& a0, hipStream_t st) {
-  SpmmaArgs a = a0;
+template <int BM, int BN, int WM, int WN, bool BF = false, bool EPI = false>
+static int launch_cfg(const typename SpmmaArgsSel<EPI>::type& a0, hipStream_t st) {
+  typename SpmmaArgsSel<EPI>::type a = a0;
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -541,7 +555,7 @@ static int launch_cfg(const SpmmaArgs& a0, hipStream_t st) {
   constexpr size_t lds_main = (size_t)BM * 144 + (size_t)(BN / 64) * 128 * 128;
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  spmma_f16_kernel<BM, BN, WM, WN, BF><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
+  spmma_f16_kernel<BM, BN, WM, WN, BF, EPI><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
   return check_launch("spmma_f16_kernel");
 }
 
@@ -553,7 +567,7 @@ using namespace sm;
 // ng <= SPMMA_MAXG same-shape problems (blob, B, C triples) as one grid; a plain call is a group of one.
 template <bool BF>
 static int spmma16(size_t ng, const void* const* blobs, const void* const* Bs, void* const* Cs, size_t m, size_t n, size_t k, size_t batch,
-                   size_t strideB, size_t strideC, float alpha, float beta, sm_stream_t stream) {
+                   size_t strideB, size_t strideC, float alpha, float beta, sm_stream_t stream, const EpiArgs* epi = nullptr) {
   if (ng == 0) return SM_STATUS_SUCCESS;
   if (!blobs || !Bs || !Cs || ng > (size_t)SPMMA_MAXG) {
     set_error("sm_spmma_{f16,bf16}: invalid argument");
@@ -586,12 +600,17 @@ static int spmma16(size_t ng, const void* const* blobs, const void* const* Bs, v
   a.sB = strideB; a.sC = strideC;
   a.m = (int)m; a.Mrows = (int)m; a.N = (int)n; a.K = (int)k; a.kc = (int)L.kc;
   a.batch = (int)batch; a.alpha = alpha; a.beta = beta;
-  // shared B + contiguous C: the batch is one tall matrix of batch*m blob rows
-  if (batch > 1 && strideB == 0 && strideC == m * n) {
+  // shared B + contiguous C (and R, when the epilogue reads one): the batch is one tall matrix of batch*m blob rows
+  if (batch > 1 && strideB == 0 && strideC == m * n && (!epi || beta == 0.0f || epi->sR == m * n)) {
     a.Mrows = (int)(m * batch);
     a.batch = 1;
   }
   hipStream_t st = (hipStream_t)stream;
+  // the same rules pick the kernel with and without an epilogue (epi: a single problem, sm_spmma_*_ex)
+  SpmmaArgsEpi ae = {};
+  static_cast<SpmmaArgs&>(ae) = a;
+  if (epi) ae.e = *epi;
+#define SM_LAUNCH(fn, ...) (epi ? fn<__VA_ARGS__, BF, true>(ae, st) : fn<__VA_ARGS__, BF, false>(a, st))
   // the metadata DMA moves 16-byte row pairs: batches and planes must start on even rows
   const bool fast = (n % 8 == 0) && n >= 8 && b_aligned && (strideB % 8 == 0) && (m % 2 == 0) && k >= 8;
   if (fast) {
@@ -600,22 +619,23 @@ static int spmma16(size_t ng, const void* const* blobs, const void* const* Bs, v
     // over 8 or 16 waves so that every SIMD still holds several waves.
     // 256 x 128 tiles (B lines amortised over twice the rows) pay with a long K and enough rows for >= 64 such
     // tiles per n-tile (profiles/sweep_r01_*.txt: 784x256x{1024,2304}, 3136x128x1152 at b=32)
-    if (n >= 128 && n <= 256 && k >= 1024 && (size_t)a.Mrows * ng >= 16384) return launch_pc<256, 128, 4, 2, 4, 3, BF>(a, st);
+    if (n >= 128 && n <= 256 && k >= 1024 && (size_t)a.Mrows * ng >= 16384) return SM_LAUNCH(launch_pc, 256, 128, 4, 2, 4, 3);
     // long K -> producer/consumer kernel (4 loader waves, ring of 3); short K -> the kernel below with more tiles per CU
     // (measured per shape on the ResNet tables, profiles/sweep_r01_*.txt)
     // (n <= 64 is HBM-bound at every K: the plain DMA kernel with more tiles per CU wins there)
-    if (k >= 512 && n > 64) return launch_pc<128, 128, 2, 2, 4, 3, BF>(a, st);
+    if (k >= 512 && n > 64) return SM_LAUNCH(launch_pc, 128, 128, 2, 2, 4, 3);
     const size_t Mr = (size_t)a.Mrows;
     if (n <= 64) {
       const size_t tiles = ceil_div(Mr, 128) * a.batch * ng;
-      return tiles >= 1024 ? launch_dma<128, 64, 4, 1, 2, BF>(a, st) : launch_dma<128, 64, 4, 2, 2, BF>(a, st);
+      return tiles >= 1024 ? SM_LAUNCH(launch_dma, 128, 64, 4, 1, 2) : SM_LAUNCH(launch_dma, 128, 64, 4, 2, 2);
     }
     const size_t tiles = ceil_div(Mr, 128) * ceil_div(n, 128) * a.batch * ng;
-    if (tiles >= 1024) return launch_dma<128, 128, 2, 2, 2, BF>(a, st);
-    return tiles >= 512 ? launch_dma<128, 128, 2, 4, 2, BF>(a, st) : launch_dma<128, 128, 4, 4, 2, BF>(a, st);
+    if (tiles >= 1024) return SM_LAUNCH(launch_dma, 128, 128, 2, 2, 2);
+    return tiles >= 512 ? SM_LAUNCH(launch_dma, 128, 128, 2, 4, 2) : SM_LAUNCH(launch_dma, 128, 128, 4, 4, 2);
   }
-  if (n <= 64) return launch_cfg<128, 64, 4, 1, BF>(a, st);
-  return launch_cfg<128, 128, 2, 2, BF>(a, st);
+  if (n <= 64) return SM_LAUNCH(launch_cfg, 128, 64, 4, 1);
+  return SM_LAUNCH(launch_cfg, 128, 128, 2, 2);
+#undef SM_LAUNCH
 }
 
 extern "C" int sm_spmma_f16(const void* blob, const void* B, void* C, size_t m, size_t n, size_t k, size_t batch,
@@ -625,6 +645,24 @@ extern "C" int sm_spmma_f16(const void* blob, const void* B, void* C, size_t m, 
 extern "C" int sm_spmma_bf16(const void* blob, const void* B, void* C, size_t m, size_t n, size_t k, size_t batch,
                              size_t strideB, size_t strideC, float alpha, float beta, sm_stream_t stream) {
   return spmma16<true>(1, &blob, &B, &C, m, n, k, batch, strideB, strideC, alpha, beta, stream);
+}
+
+// The same product with an epilogue (include/sparsifyme.h: sm_epilogue_t); a plain epilogue IS the call above.
+template <bool BF>
+static int spmma16_ex(const void* blob, const void* B, void* D, size_t m, size_t n, size_t k, size_t batch, size_t strideB, size_t strideD,
+                      float alpha, float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
+  EpiArgs e;
+  bool plain;
+  if (const int rc = epilogue_args(ep, D, strideD, m, beta, e, &plain, "sm_spmma_{f16,bf16}_ex")) return rc;
+  return spmma16<BF>(1, &blob, &B, &D, m, n, k, batch, strideB, strideD, alpha, beta, stream, plain ? nullptr : &e);
+}
+extern "C" int sm_spmma_f16_ex(const void* blob, const void* B, void* D, size_t m, size_t n, size_t k, size_t batch, size_t strideB,
+                               size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return spmma16_ex<false>(blob, B, D, m, n, k, batch, strideB, strideD, alpha, beta, epilogue, stream);
+}
+extern "C" int sm_spmma_bf16_ex(const void* blob, const void* B, void* D, size_t m, size_t n, size_t k, size_t batch, size_t strideB,
+                                size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return spmma16_ex<true>(blob, B, D, m, n, k, batch, strideB, strideD, alpha, beta, epilogue, stream);
 }
 
 // `count` same-shape problems in as few grids as possible (SPMMA_MAXG per launch): same kernels, same C bit for bit

@@ -40,6 +40,16 @@ struct FusedArgs {
   half_t* const* dCp;
 };
 
+// The argument block of the epilogue instantiations (sm_spmma_fused_*_ex: `bool EPI` of the kernels below -- the store is
+// store_c_tile_epi, mma_tile.h): the plain block + the epilogue.  The plain instantiations keep taking FusedArgs itself, so
+// their code is what it was.  Only the combinations the dispatch of sm_spmma_fused_*_ex can select are instantiated (not the
+// dense twin, not the stream-K, persistent-wide or A-stationary kernels, whose stores are their own).
+struct FusedArgsEpi : FusedArgs {
+  EpiArgs e;
+};
+template <bool EPI> struct FusedArgsSel { typedef FusedArgs type; };
+template <> struct FusedArgsSel<true> { typedef FusedArgsEpi type; };
+
 // ---------------------------------------------------------------------------------------------
 // n <= 128, DIRECT form: no loader waves and no compressed image at all.  The dense A tile (128 rows x 128 B per 64-k
 // stage) and the B tile reach LDS by LDS-DMA issued by the four compute waves themselves (ring of NS stages, counted
@@ -51,8 +61,8 @@ struct FusedArgs {
 // problem (k = 64) allocates 34 KiB of LDS, so a fourth workgroup then shares the CU -- with no K loop to pipeline, the workgroups
 // per CU are all that overlaps one tile's load latency with another's stores (12544 x 256 x 64)
 // (measured indifferent: profiles/direct_ablate_occ4_r05p.txt -- kept, it costs nothing)
-template <int BN, int NS, bool BF = false, int BM = 128, int NWV = 4, bool ANT = true, bool DENSE = false>
-__global__ __launch_bounds__(64 * NWV, (BN == 128 && NWV == 4 && BM == 128) ? 4 : 1) void spmma_f16_fused_direct_kernel(const FusedArgs p) {
+template <int BN, int NS, bool BF = false, int BM = 128, int NWV = 4, bool ANT = true, bool DENSE = false, bool EPI = false>
+__global__ __launch_bounds__(64 * NWV, (BN == 128 && NWV == 4 && BM == 128) ? 4 : 1) void spmma_f16_fused_direct_kernel(const typename FusedArgsSel<EPI>::type p) {
   static_assert(BM == 128 || BM == 64, "row tile");
   static_assert(NWV == 4 || (NWV == 8 && BM == 128), "waves per workgroup");
   constexpr int NW = NWV, TM = BM / NW, FM = TM / 16, FN = BN / 16;
@@ -75,6 +85,8 @@ __global__ __launch_bounds__(64 * NWV, (BN == 128 && NWV == 4 && BM == 128) ? 4 
   const half_t* B = p.dBp ? p.dBp[gb] : p.B[grp] + (size_t)b * p.sB;
   half_t* C = p.dCp ? p.dCp[gb] : p.C[grp] + (size_t)b * p.sC;
   const int mlast = p.Mrows - 1;
+  EpiBias<FM, FN> eb;  // (EPI: the lane's bias values, fetched ahead of the K loop)
+  if constexpr (EPI) eb = epi_bias_prefetch<FM, FN>(p.e, true, wave * TM, 0, m0, n0, p.Mrows, p.N, lane);
   // (Round 5: the ablation of this kernel -- profiles/direct_ablate_r05n.txt -- reads "whole launch = launch without
   //  the C store + the C store alone" on every shape (12544 x 256 x 64 x 3: 220 = 105 + 113 us): loads and stores do not overlap.  Starting the
   //  workgroups that share a CU a third of a tile's lifetime apart, so that one stores while the others load, changed nothing
@@ -140,12 +152,13 @@ __global__ __launch_bounds__(64 * NWV, (BN == 128 && NWV == 4 && BM == 128) ? 4 
     fill = fill + 1 == NS ? 0 : fill + 1;
   }
   __syncthreads();
-  store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  if constexpr (EPI) store_c_tile_epi<BM, BN, FM, FN, 64 * NW, BF>(smem, C, p.e.R + (size_t)b * p.e.sR, p.e, eb, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  else store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
 }
 
-template <int BN, int NS, bool BF = false, int BM = 128, int NWV = 4, bool ANT = true, bool DENSE = false>
-static int launch_fused_direct(const FusedArgs& a0, hipStream_t st) {
-  FusedArgs a = a0;
+template <int BN, int NS, bool BF = false, int BM = 128, int NWV = 4, bool ANT = true, bool DENSE = false, bool EPI = false>
+static int launch_fused_direct(const typename FusedArgsSel<EPI>::type& a0, hipStream_t st) {
+  typename FusedArgsSel<EPI>::type a = a0;
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -163,9 +176,9 @@ static int launch_fused_direct(const FusedArgs& a0, hipStream_t st) {
   constexpr size_t lds_max = NS * stage_bytes > lds_epi ? NS * stage_bytes : lds_epi;
   static LdsOptIn lds_optin;
   if (lds_max > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE>), lds_max, "spmma_f16_fused_direct_kernel")) return rc;
+    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE, EPI>), lds_max, "spmma_f16_fused_direct_kernel")) return rc;
   }
-  spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE><<<dim3((unsigned)nwg), dim3(64 * NWV), lds, st>>>(a);
+  spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE, EPI><<<dim3((unsigned)nwg), dim3(64 * NWV), lds, st>>>(a);
   return check_launch("spmma_f16_fused_direct_kernel");
 }
 
@@ -192,8 +205,8 @@ static int launch_fused_direct(const FusedArgs& a0, hipStream_t st) {
 // barrier (profiles/ab_ilv_r04n.txt: -3 .. +3 % over seven shapes, A pieces only: -3 .. 0 %: the 800 cycles the burst spends in
 // issue are not won back by hiding them, so they are not what bounds the stage).
 // ---------------------------------------------------------------------------------------------
-template <int BN, bool BF = false, int NSA = 3, int NSB = 2, bool ANT = true, bool DENSE = false>
-__global__ __launch_bounds__(512) void spmma_f16_fused_big_kernel(const FusedArgs p) {
+template <int BN, bool BF = false, int NSA = 3, int NSB = 2, bool ANT = true, bool DENSE = false, bool EPI = false>
+__global__ __launch_bounds__(512) void spmma_f16_fused_big_kernel(const typename FusedArgsSel<EPI>::type p) {
   constexpr int BM = 256, NW = 8, TM = BM / NW, FM = TM / 16, FN = BN / 16;
   constexpr int SA = BM * 128, SB = 64 * BN * 2;
   constexpr int A_N = BM / 8, B_N = BN / 8;  // 1 KiB DMA wave-instructions per stage
@@ -217,6 +230,8 @@ __global__ __launch_bounds__(512) void spmma_f16_fused_big_kernel(const FusedArg
   const half_t* B = p.dBp ? p.dBp[gb] : p.B[grp] + (size_t)b * p.sB;
   half_t* C = p.dCp ? p.dCp[gb] : p.C[grp] + (size_t)b * p.sC;
   const int mlast = p.Mrows - 1;
+  EpiBias<FM, FN> eb;  // (EPI: the lane's bias values, fetched ahead of the K loop)
+  if constexpr (EPI) eb = epi_bias_prefetch<FM, FN>(p.e, true, wave * TM, 0, m0, n0, p.Mrows, p.N, lane);
 
   const char* asrc[SLA];
   const char* bsrc[SLB];
@@ -279,13 +294,14 @@ __global__ __launch_bounds__(512) void spmma_f16_fused_big_kernel(const FusedArg
     fb = fb + 1 == NSB ? 0 : fb + 1;
   }
   __syncthreads();
-  store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  if constexpr (EPI) store_c_tile_epi<BM, BN, FM, FN, 64 * NW, BF>(smem, C, p.e.R + (size_t)b * p.e.sR, p.e, eb, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  else store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
 }
 
-template <int BN, bool BF = false, int NSA = 3, int NSB = 2, bool ANT = true, bool DENSE = false>
-static int launch_fused_big(const FusedArgs& a0, hipStream_t st) {
+template <int BN, bool BF = false, int NSA = 3, int NSB = 2, bool ANT = true, bool DENSE = false, bool EPI = false>
+static int launch_fused_big(const typename FusedArgsSel<EPI>::type& a0, hipStream_t st) {
   constexpr int BM = 256;
-  FusedArgs a = a0;
+  typename FusedArgsSel<EPI>::type a = a0;
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -299,8 +315,8 @@ static int launch_fused_big(const FusedArgs& a0, hipStream_t st) {
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static_assert(lds <= 160 * 1024, "LDS budget of the big direct kernel");
   static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE>), lds, "spmma_f16_fused_big_kernel")) return rc;
-  spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a);
+  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE, EPI>), lds, "spmma_f16_fused_big_kernel")) return rc;
+  spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE, EPI><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a);
   return check_launch("spmma_f16_fused_big_kernel");
 }
 
@@ -721,8 +737,8 @@ static bool sk_takes(size_t rows, size_t problems, size_t n, size_t k, bool asta
 // ---------------------------------------------------------------------------------------------
 __device__ __attribute__((aligned(256))) const unsigned char sm_fused_zero_page[256] = {0};
 
-template <int BN, bool BF = false, bool DENSE = false>
-__global__ __launch_bounds__(256) void spmma_f16_fused_span_kernel(const FusedArgs p, const unsigned span_lds /*bytes reserved for the A span*/,
+template <int BN, bool BF = false, bool DENSE = false, bool EPI = false>
+__global__ __launch_bounds__(256) void spmma_f16_fused_span_kernel(const typename FusedArgsSel<EPI>::type p, const unsigned span_lds /*bytes reserved for the A span*/,
                                                                    const size_t a_bytes /*bytes of one problem's A*/) {
   constexpr int BM = 128, NW = 4, TM = BM / NW, FM = TM / 16, FN = BN / 16;
   constexpr int SB = 64 * BN * 2;
@@ -740,6 +756,8 @@ __global__ __launch_bounds__(256) void spmma_f16_fused_span_kernel(const FusedAr
   half_t* C = p.dCp ? p.dCp[grp] : p.C[grp];
   const unsigned rowbytes = (unsigned)p.K * 2u;
   const int rows = p.Mrows - m0 < BM ? p.Mrows - m0 : BM;  // valid rows of this tile (>= 1)
+  EpiBias<FM, FN> eb;  // (EPI: the lane's bias values, fetched ahead of the span's DMA)
+  if constexpr (EPI) eb = epi_bias_prefetch<FM, FN>(p.e, true, wave * TM, 0, m0, n0, p.Mrows, p.N, lane);
 
   // ---- A span: bytes [m0 * rowbytes, (m0 + rows) * rowbytes) of the operand, in 1 KiB pieces
   {
@@ -836,12 +854,13 @@ __global__ __launch_bounds__(256) void spmma_f16_fused_span_kernel(const FusedAr
     smfmac_b_sweep<FM, FN, BF>(af, idx, Bimg + kt * SB, 0, lane, acc);
   }
   __syncthreads();
-  store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  if constexpr (EPI) store_c_tile_epi<BM, BN, FM, FN, 64 * NW, BF>(smem, C, p.e.R, p.e, eb, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);  // (batches stacked)
+  else store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, true, wave * TM, 0, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
 }
 
-template <int BN, bool BF = false, bool DENSE = false>
-static int launch_fused_span(const FusedArgs& a0, hipStream_t st) {
-  FusedArgs a = a0;
+template <int BN, bool BF = false, bool DENSE = false, bool EPI = false>
+static int launch_fused_span(const typename FusedArgsSel<EPI>::type& a0, hipStream_t st) {
+  typename FusedArgsSel<EPI>::type a = a0;
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.ngroup;
@@ -856,8 +875,8 @@ static int launch_fused_span(const FusedArgs& a0, hipStream_t st) {
     return SM_STATUS_NOT_SUPPORTED;
   }
   static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_span_kernel<BN, BF, DENSE>), 160 * 1024, "spmma_f16_fused_span_kernel")) return rc;
-  spmma_f16_fused_span_kernel<BN, BF, DENSE><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a, (unsigned)span_lds, (size_t)a.Mrows * a.K * 2);
+  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_span_kernel<BN, BF, DENSE, EPI>), 160 * 1024, "spmma_f16_fused_span_kernel")) return rc;
+  spmma_f16_fused_span_kernel<BN, BF, DENSE, EPI><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a, (unsigned)span_lds, (size_t)a.Mrows * a.K * 2);
   return check_launch("spmma_f16_fused_span_kernel");
 }
 
@@ -892,8 +911,8 @@ struct BTileDma {
 // PF stages ahead in registers, only B through LDS -- was built in round 2: bit-identical, 1.3x slower on every n <= 128 layer
 // (profiles/tune_rega_r02q.txt; 164 VGPRs, half-line wave loads).  Removed again; DESIGN.md 4.5, git history.)
 
-template <int BN, int WM, int WN, int NLB, int PF, int NSB, bool BF = false, bool ANT = true>
-__global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide_kernel(const FusedArgs p) {
+template <int BN, int WM, int WN, int NLB, int PF, int NSB, bool BF = false, bool ANT = true, bool EPI = false>
+__global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide_kernel(const typename FusedArgsSel<EPI>::type p) {
   constexpr int BM = 128, NLA = 4, NC = WM * WN, NW = NC + NLA + NLB;
   static_assert(PF >= 1 && PF <= 3 && NSB >= 2 && NSB <= 4, "pipeline depths");
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
@@ -921,6 +940,8 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
   const unsigned wm = wave / WN, wn = wave % WN;  // consumer waves only
+  EpiBias<FM, FN> eb;  // (EPI: the lane's bias values, fetched ahead of the K loop)
+  if constexpr (EPI) eb = epi_bias_prefetch<FM, FN>(p.e, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, lane);
 
   if (NLB > 0 && wave >= (unsigned)(NC + NLA)) {
     // ------------------------------------------------------------------ B loader wave: LDS-DMA only
@@ -1055,12 +1076,13 @@ __global__ __launch_bounds__(64 * (WM * WN + 4 + NLB)) void spmma_f16_fused_wide
   }
   __syncthreads();
 
-  store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  if constexpr (EPI) store_c_tile_epi<BM, BN, FM, FN, 64 * NW, BF>(smem, C, p.e.R + (size_t)b * p.e.sR, p.e, eb, acc, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
+  else store_c_tile<BM, BN, FM, FN, 64 * NW, BF>(smem, C, acc, wave < (unsigned)NC, wm * TM, wn * TN, m0, n0, p.Mrows, p.N, p.alpha, p.beta, tid);
 }
 
-template <int BN, int WM, int WN, int NLB, int PF, int NSB, bool BF = false, bool ANT = true>
-static int launch_fused_wide(const FusedArgs& a0, hipStream_t st) {
-  FusedArgs a = a0;
+template <int BN, int WM, int WN, int NLB, int PF, int NSB, bool BF = false, bool ANT = true, bool EPI = false>
+static int launch_fused_wide(const typename FusedArgsSel<EPI>::type& a0, hipStream_t st) {
+  typename FusedArgsSel<EPI>::type a = a0;
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
@@ -1074,9 +1096,9 @@ static int launch_fused_wide(const FusedArgs& a0, hipStream_t st) {
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   static LdsOptIn lds_optin;
   if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT>), lds, "spmma_f16_fused_wide_kernel")) return rc;
+    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT, EPI>), lds, "spmma_f16_fused_wide_kernel")) return rc;
   }
-  spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + 4 + NLB)), lds, st>>>(a);
+  spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT, EPI><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + 4 + NLB)), lds, st>>>(a);
   return check_launch("spmma_f16_fused_wide_kernel");
 }
 
@@ -1563,7 +1585,10 @@ bool sm::spmma_fused16_takes_exact(const void* A, const void* B, const void* C, 
 template <bool BF>
 static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const* Bg, void* const* Cg, size_t m, size_t n, size_t k, size_t lda,
                          size_t batch, size_t strideA, size_t strideB, size_t strideC, float alpha, float beta,
-                         sm_stream_t stream, void* workspace = nullptr, size_t workspace_bytes = 0) {
+                         sm_stream_t stream, void* workspace = nullptr, size_t workspace_bytes = 0, const EpiArgs* epi = nullptr) {
+  // epi: sm_spmma_fused_*_ex with an epilogue that is not the plain one (a single problem, no workspace).  The same rules pick
+  // the kernel; the forms whose stores are their own (thin, A-stationary, persistent wide) are not taken.
+#define SM_LAUNCH(fn, ...) (epi ? fn<__VA_ARGS__, true>(ae, st) : fn<__VA_ARGS__, false>(a, st))
   if (ngroup == 0) return SM_STATUS_SUCCESS;
   if (!Ag || !Bg || !Cg || lda < k || ngroup > (size_t)MAXG) {
     set_error("sm_spmma_fused_{f16,bf16}: invalid argument");
@@ -1582,12 +1607,18 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   // (round 5) thin problems -- n < 8, k <= 64, one tall contiguous A, shared B: the depthwise layers of the model zoo -- on the
   // vector ALUs (spmma_f16_thin.hip); result inside the tight bound of the exact product, not bit-identical to the staged pair
   if (n < 8 && k <= 64 && lda == k && (batch == 1 || (strideB == 0 && strideA == m * lda && strideC == m * n))) {
+    if (epi) {
+      set_error("sm_spmma_fused_{f16,bf16}_ex: the thin form (n < 8) takes no epilogue");
+      return SM_STATUS_NOT_SUPPORTED;
+    }
     const int rc = spmma_fused_thin(BF, (int)ngroup, Ag, Bg, Cg, m * batch, n, k, alpha, beta, (hipStream_t)stream);
     if (rc != SM_STATUS_NOT_SUPPORTED) return rc;
   }
   // rows that are not whole 64-deep stages of 16-byte pieces: the span form, when A is one tall contiguous matrix, n <= 128
   // and a 128-row span + the whole B fit the LDS (k = 147: the stem layer of every ResNet)
-  if (span_form_takes(m, n, k, lda, batch, strideA, strideB, strideC, all_aligned, c_aligned)) {
+  // (a residual that is read must follow D: 16-byte aligned, batches back to back)
+  const bool r_follows = !epi || beta == 0.0f || (aligned16(epi->R) && (batch == 1 || epi->sR == m * n));
+  if (span_form_takes(m, n, k, lda, batch, strideA, strideB, strideC, all_aligned, c_aligned && r_follows)) {
     FusedArgs a = {};
     for (size_t g = 0; g < (size_t)MAXG; ++g) {
       const size_t s_ = g < ngroup ? g : 0;
@@ -1597,7 +1628,10 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
     a.Mrows = (int)(m * batch); a.N = (int)n; a.K = (int)k; a.lda = (int)lda;
     a.batch = 1; a.alpha = alpha; a.beta = beta;
     hipStream_t st = (hipStream_t)stream;
-    return n <= 64 ? launch_fused_span<64, BF>(a, st) : launch_fused_span<128, BF>(a, st);
+    FusedArgsEpi ae = {};
+    static_cast<FusedArgs&>(ae) = a;
+    if (epi) ae.e = *epi;
+    return n <= 64 ? SM_LAUNCH(launch_fused_span, 64, BF, false) : SM_LAUNCH(launch_fused_span, 128, BF, false);
   }
   // whole 64-deep stages of 16-byte aligned rows only; anything else: sm_compress24_f16 + sm_spmma_f16
   if (!stage_forms_take(n, k, lda, strideA, strideB, all_aligned)) {
@@ -1622,11 +1656,14 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   a.sA = strideA; a.sB = strideB; a.sC = strideC;
   a.Mrows = (int)m; a.N = (int)n; a.K = (int)k; a.lda = (int)lda;
   a.batch = (int)batch; a.alpha = alpha; a.beta = beta;
-  if (batch > 1 && strideB == 0 && strideA == m * lda && strideC == m * n) {
+  if (batch > 1 && strideB == 0 && strideA == m * lda && strideC == m * n && (!epi || beta == 0.0f || epi->sR == m * n)) {
     a.Mrows = (int)(m * batch);
     a.batch = 1;
   }
   hipStream_t st = (hipStream_t)stream;
+  FusedArgsEpi ae = {};
+  static_cast<FusedArgs&>(ae) = a;
+  if (epi) ae.e = *epi;
   // n <= 128 (and n <= 256 with a single stage): the direct kernel -- dense A by LDS-DMA, selection in the consumer's
   // registers, ring of 2 so that three workgroups share a CU.
   // (round 4) n > 128: the 256-row BIG form where its one-per-CU workgroups fill the chip's rounds at least as well as the
@@ -1653,7 +1690,7 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   if (n > 128 && k > 64) {
     const size_t cus = (size_t)device_cu_count(), nb = (size_t)a.batch * a.ngroup;
     const size_t t_big = ((size_t)a.Mrows + 255) / 256 * ((n + 255) / 256) * nb, t_wide = ((size_t)a.Mrows + 127) / 128 * ((n + 255) / 256) * nb;
-    const bool astat_shape = n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0);
+    const bool astat_shape = !epi && n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0);
     bool big = round_eff(t_big, cus) >= round_eff(t_wide, cus);
     if (astat_shape) {
       const size_t panels = ((size_t)a.Mrows + 127) / 128 * nb;
@@ -1662,22 +1699,22 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
       big = round_eff(t_big, cus) > round_eff(panels * ns, cus) + 0.1;
     }
     // (the hint on the big form's A loads, n <= 256: measured indifferent, profiles/nt_ab_r05q.txt)
-    if (big) return n <= 256 ? launch_fused_big<256, BF, 3, 2, true>(a, st) : launch_fused_big<256, BF, 3, 2, false>(a, st);
+    if (big) return n <= 256 ? SM_LAUNCH(launch_fused_big, 256, BF, 3, 2, true, false) : SM_LAUNCH(launch_fused_big, 256, BF, 3, 2, false, false);
   }
   // (round 5: 128-column direct tiles at ANY n -- every column tile re-reading its A rows through L2, as 12544 x 256 x 64 does at 0.89 of its roofline -- measured on
   //  the shapes the A-stationary and wide kernels serve: slower on all of them, 3136 x 512 x 128 x 4 147 vs 129 us, 784 x 1024 x 256 x 6 164 vs 114, 784 x 256 x 2304 x 6
   //  303 vs 195, 196 x 512 x 2048 x 2 55 vs 32 (profiles/ab_direct_any_r05an.txt; the rows whose two columns agree went to the big form before the hook).  Removed.)
   if (n <= 128 || (n <= 256 && k <= 64)) {
-    if (n <= 64) return launch_fused_direct<64, 2, BF>(a, st);
+    if (n <= 64) return SM_LAUNCH(launch_fused_direct, 64, 2, BF, 128, 4, true, false);
     // (round 5) the non-temporal hint on the A loads only where A really is read once and streams long: with two column tiles (n = 256,
     // k = 64) the second tile's read of the same rows then misses L2 -- 12544 x 256 x 64 x 3: 200 -> 166 us without the hint -- and the
     // short-K 128-column layer is 5 % faster without it too (12544 x 128 x 256: 68.7 -> 64.8 us); 3136 x 128 x 512 / 1152 and every
     // 64-column shape keep it (1-6 % faster with it; profiles/nt_ab_r05q.txt).  Same C either way.
-    if (n > 128 || k < 512) return launch_fused_direct<128, 2, BF, 128, 4, false>(a, st);
-    return launch_fused_direct<128, 2, BF>(a, st);
+    if (n > 128 || k < 512) return SM_LAUNCH(launch_fused_direct, 128, 2, BF, 128, 4, false, false);
+    return SM_LAUNCH(launch_fused_direct, 128, 2, BF, 128, 4, true, false);
   }
   // n > 256, short K, plain store: A-stationary (the 2:4 image of a row panel stays in LDS across column tiles)
-  if (n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0) &&
+  if (!epi && n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0) &&
       astat_lds_bytes((int)(k / 64), 3) <= 160 * 1024) {
     return launch_fused_astat<BF>(a, st);
   }
@@ -1689,9 +1726,10 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   // 39.5 vs 43.9 us per instance, 784 x 256 x 1024: 19.6 vs 20.3; on 36- and 72-stage tiles the statically assigned tiles
   // lose to the hardware's dynamic dispatch (784 x 256 x 2304: 40.5 vs 39.1, 196 x 512 x 4608: 41.0 vs 35.3;
   // profiles/widep_r03g.txt), so those keep one workgroup per tile.
-  if (k <= 1024) return launch_fused_widep<256, 4, 2, 4, 2, 3, BF>(a, st);
-  if (n > 256) return launch_fused_wide<256, 4, 2, 4, 2, 3, BF, false>(a, st);  // several column tiles read the same A rows: no non-temporal hint
-  return launch_fused_wide<256, 4, 2, 4, 2, 3, BF>(a, st);
+  if (k <= 1024 && !epi) return launch_fused_widep<256, 4, 2, 4, 2, 3, BF>(a, st);
+  if (n > 256) return SM_LAUNCH(launch_fused_wide, 256, 4, 2, 4, 2, 3, BF, false);  // several column tiles read the same A rows: no non-temporal hint
+  return SM_LAUNCH(launch_fused_wide, 256, 4, 2, 4, 2, 3, BF, true);
+#undef SM_LAUNCH
 }
 
 extern "C" int sm_spmma_fused_f16(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda,
@@ -1703,6 +1741,26 @@ extern "C" int sm_spmma_fused_bf16(const void* A, const void* B, void* C, size_t
                                    size_t batch, size_t strideA, size_t strideB, size_t strideC, float alpha, float beta,
                                    sm_stream_t stream) {
   return spmma_fused16<true>(1, &A, &B, &C, m, n, k, lda, batch, strideA, strideB, strideC, alpha, beta, stream);
+}
+
+// With an epilogue (include/sparsifyme.h: sm_epilogue_t); a plain epilogue IS the call above.
+template <bool BF>
+static int spmma_fused16_ex(const void* A, const void* B, void* D, size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t strideA, size_t strideB,
+                            size_t strideD, float alpha, float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
+  EpiArgs e;
+  bool plain;
+  if (const int rc = epilogue_args(ep, D, strideD, m, beta, e, &plain, "sm_spmma_fused_{f16,bf16}_ex")) return rc;
+  return spmma_fused16<BF>(1, &A, &B, &D, m, n, k, lda, batch, strideA, strideB, strideD, alpha, beta, stream, nullptr, 0, plain ? nullptr : &e);
+}
+extern "C" int sm_spmma_fused_f16_ex(const void* A, const void* B, void* D, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                                     size_t strideA, size_t strideB, size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue,
+                                     sm_stream_t stream) {
+  return spmma_fused16_ex<false>(A, B, D, m, n, k, lda, batch, strideA, strideB, strideD, alpha, beta, epilogue, stream);
+}
+extern "C" int sm_spmma_fused_bf16_ex(const void* A, const void* B, void* D, size_t m, size_t n, size_t k, size_t lda, size_t batch,
+                                      size_t strideA, size_t strideB, size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue,
+                                      sm_stream_t stream) {
+  return spmma_fused16_ex<true>(A, B, D, m, n, k, lda, batch, strideA, strideB, strideD, alpha, beta, epilogue, stream);
 }
 
 // The same entry points with a workspace (round 5): the library may then run the stream-K form (spmma_f16_fused_sk_kernel) on the
