@@ -78,6 +78,10 @@ struct spmma_fns<float> {
   }
 };
 struct spmma_fns_f16 {
+  static int linear_on(const void* blob, const void* X, void* Y, std::size_t tokens, std::size_t out, std::size_t in, std::size_t ldx, std::size_t ldy,
+                       float al, float be, const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_linear24_f16(blob, X, Y, tokens, out, in, ldx, ldy, al, be, ep, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -119,6 +123,10 @@ struct spmma_fns_f16 {
   }
 };
 struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_f32_16x16x64_bf16
+  static int linear_on(const void* blob, const void* X, void* Y, std::size_t tokens, std::size_t out, std::size_t in, std::size_t ldx, std::size_t ldy,
+                       float al, float be, const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_linear24_bf16(blob, X, Y, tokens, out, in, ldx, ldy, al, be, ep, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
   }
@@ -466,6 +474,25 @@ class spmma_plan_t {
     if (!ready_) return SM_STATUS_INVALID_VALUE;
     const sm_epilogue_t e = epilogue.c_struct(dC, m_, n, beta);
     return fns::mul_ex_on(blob_.data().get(), dB, dC, m_, n, k_, batch_, strideB < 0 ? k_ * n : (std::size_t)strideB, alpha, beta, &e, stream);
+  }
+
+  // Extension (fp16 / bfloat16, a plan of batch_size 1): the operand as the WEIGHT of a linear layer, m = out features, k = in
+  // features -- Y[tokens][m] = alpha * X[tokens][k] . A_2:4^T + beta * Y, token-major in and out, one launch (sm_linear24_*).
+  // ldx / ldy: leading dimensions of X / Y in elements (0: k / m).
+  int linear(type_t* dX, type_t* dY, std::size_t tokens, float alpha = 1.0f, float beta = 0.0f, hipStream_t stream = nullptr, std::size_t ldx = 0,
+             std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1) return SM_STATUS_INVALID_VALUE;
+    return fns::linear_on(blob_.data().get(), dX, dY, tokens, m_, k_, ldx ? ldx : k_, ldy ? ldy : m_, alpha, beta, nullptr, stream);
+  }
+  // the same with an epilogue, read in Y's coordinates: bias_dim SM_BIAS_COL = one value per out feature, SM_BIAS_ROW = one per token;
+  // the residual has Y's shape and ldy
+  int linear(type_t* dX, type_t* dY, std::size_t tokens, const spmma_epilogue_t& epilogue, float alpha = 1.0f, float beta = 0.0f,
+             hipStream_t stream = nullptr, std::size_t ldx = 0, std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1) return SM_STATUS_INVALID_VALUE;
+    const sm_epilogue_t e = epilogue.c_struct(dY, tokens, m_, beta);
+    return fns::linear_on(blob_.data().get(), dX, dY, tokens, m_, k_, ldx ? ldx : k_, ldy ? ldy : m_, alpha, beta, &e, stream);
   }
 
  private:

@@ -283,6 +283,40 @@ int sm_spmma_fused_bf16_ex(const void* A, const void* B, void* D, size_t m, size
                            size_t strideA, size_t strideB, size_t strideD, float alpha, float beta, const sm_epilogue_t* epilogue,
                            sm_stream_t stream);
 
+/* ---- 2:4 WEIGHT-sparse linear layer, token-major (extension: the reference has no linear layer; this is the documented case of
+ *      the vendor libraries, torch.nn.functional.linear with W[out][in] pruned 2:4 along `in`).
+ *
+ *          Y[t][o] = round_to_out( act( alpha * sum_i W_2:4[o][i] * X[t][i] + beta * R[t][o] + bias ) )
+ *
+ *      blob   exactly what sm_compress24_{f16,bf16}(W, m = out_features, k = in_features, ld, batch = 1, ..) or
+ *             sm_prune24_compress24_* writes: the weight is compressed once, the activations are fresh on every call.
+ *      X      row-major tokens x in_features, leading dimension ldx >= in_features (elements); rows 16-byte aligned.
+ *      Y      row-major tokens x out_features, leading dimension ldy >= out_features (elements): a fused QKV or gate/up output
+ *             can be written as column slices of one buffer.  Columns at or beyond out_features are not touched.
+ *      fp32 accumulation and ONE rounding at the end, the arithmetic of sm_spmma_*_ex: alpha * acc + beta * R, then the bias as an
+ *      addition of its own, then the activation.
+ *      epilogue  the sm_epilogue_t above, NULL = none, read in Y's coordinates: SM_BIAS_COL = one fp32 per out feature (the
+ *             nn.Linear bias), SM_BIAS_ROW = one per token; R has Y's shape and ldy, R == Y is allowed (in place); strideR is ignored
+ *             (there is no batch).  With a NULL struct beta != 0 reads Y; with a struct, beta != 0 and R == NULL is invalid.  The
+ *             validity rules and the error text are those of sm_spmma_*_ex, checked before the shape.
+ *      Forms  tokens <= 16 and out_features <= 16384: the decode form (a pure weight stream: the blob goes straight to registers, the
+ *             waves of a workgroup split K and add their fp32 partial tiles in a fixed order); every other call: the tile form, which
+ *             walks K in the order of
+ *             sm_spmma_* and is bit-identical to sm_transpose(X) + sm_spmma_{f16,bf16}[_ex] + sm_transpose(C).  The decode form adds
+ *             its K slices in another order: it agrees within the arithmetic's bound (as the THIN form of sm_spmma_fused_f16), not
+ *             bit for bit.  Both forms give the same bits on every run (no atomics, no order that depends on arrival).
+ *      Status, decided before any device work: invalid epilogue, null operand, blob not 16-byte aligned, ldx < in_features,
+ *      ldy < out_features: SM_STATUS_INVALID_VALUE; in_features % 64 != 0, X rows not 16-byte aligned (pointer, ldx % 8), a
+ *      dimension >= 2^31: SM_STATUS_NOT_SUPPORTED; tokens == 0 or out_features == 0: success, nothing enqueued.  Every tokens >= 1
+ *      and out_features >= 1 is taken: Y (and R, when read) 8-byte aligned with out_features % 4 == 0 and ldy % 4 == 0 use 8-byte
+ *      stores, everything else per-element stores.
+ *      Enqueue only: no allocation, no synchronisation, no workspace, no memset node; capturable into a hipGraph.
+ *      Not covered: fp8 / int8 token-major output, a batch dimension, in_features % 64 != 0. */
+int sm_linear24_f16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
+                    size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_linear24_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
+                     size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +
  * sm_spmma_f32 to fp32 accumulation order.  Needs k % 32 == 0, n % 4 == 0, 16-byte aligned rows. */

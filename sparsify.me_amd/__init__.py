@@ -158,6 +158,9 @@ for _sfx16 in ("f16", "bf16"):
 for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_spmma_%s_ex" % _sfx16] = _SIGS["sm_spmma_f16"][:-1] + [_c_ptr, _c_ptr]
     _SIGS["sm_spmma_fused_%s_ex" % _sfx16] = _SIGS["sm_spmma_fused_f16"][:-1] + [_c_ptr, _c_ptr]
+# the token-major 2:4 weight-sparse linear layer (linear24_f16.hip)
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_linear24_" + _sfx16] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_f, _c_f, _c_ptr, _c_ptr]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -403,6 +406,21 @@ def spmma(blob, B, C, m, n, k, batch=1, strideB=0, strideC=None, alpha=1.0, beta
     fn = getattr(lib(), "sm_spmma_" + _sfx(B))
     _check(fn(_dev(blob), _dev(B), _dev(C), m, n, k, batch, strideB, strideC, float(alpha), float(beta), _stream()),
            "sm_spmma")
+
+
+def linear24(blob, X, Y, tokens, out_features, in_features, ldx=None, ldy=None, alpha=1.0, beta=0.0, epilogue=None):
+    """Y[tokens][out] = act(alpha * X[tokens][in] . W^T + beta * R + bias) with W[out][in] the 2:4 blob of
+    compress24(W, m=out_features, k=in_features) (sm_linear24_*): token-major in and out, one launch.  epilogue: an Epilogue read in
+    Y's coordinates (bias_dim "col": one value per out feature, "row": one per token; residual of Y's shape and ldy)."""
+    torch = _t()
+    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
+        raise SparsifymeError(f"linear24: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+    ldx = in_features if ldx is None else ldx
+    ldy = out_features if ldy is None else ldy
+    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
+    fn = getattr(lib(), "sm_linear24_" + _sfx(X))
+    _check(fn(_dev(blob), _dev(X), _dev(Y), tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta),
+              ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24")
 
 
 def spmma_fused_i8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, accumulate=False, scale=None):
