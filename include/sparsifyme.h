@@ -206,6 +206,41 @@ int sm_spmma_fused_workspace_state(const void* workspace, int* state, sm_stream_
  * Answered for beta == 0 and a 16-byte aligned C with strideC % 8 == 0 (what the dispatch's A-stationary exception for n > 256,
  * k <= 512 requires): with another beta / C alignment those shapes may run stream-K although *takes = 0 here.  plan: >= 25 unsigned. */
 int sm_spmma_fused_streamk_plan(size_t rows, size_t n, size_t k, size_t problems, int* takes, unsigned* plan);
+/* WHICH FORM of the fused kernel a launch runs: the dispatch rule of sm_spmma_fused_{f16,bf16} and their _grouped / _ws / _ex forms as
+ * a host-side query -- the one function the entry points themselves switch on, so the answer is what launches.  For tests (a test
+ * named for a form asserts that its shape reaches it), bench.py-type tools and schedulers; no device work.
+ *   m, n, k, lda, batch, strideA, strideB, strideC, beta: as passed to the entry point; count: the problems of ONE launch (1 for the
+ *   plain entry points; the grouped ones launch 8 problems at a time, so 1 .. 8; 0: nothing to do).
+ *   flags: SM_FUSED_FLAG_A_ALIGNED / _B_ALIGNED / _C_ALIGNED -- every problem's A / B / C starts on a 16-byte boundary (B and C are
+ *   at least element-aligned); _WORKSPACE -- the _ws entry points with a 16-byte aligned workspace of sm_spmma_fused_workspace_size
+ *   bytes; _EPILOGUE -- the _ex entry points with an epilogue that is not the plain one (a bias, an activation or a residual other
+ *   than D), its residual -- where read, beta != 0 -- laid out like D: aligned as C is, strideR == strideD.  (_WORKSPACE and
+ *   _EPILOGUE together: no entry point takes both.)
+ *   cus: the compute units the rule is asked for (several choices compare how well tile counts fill the chip's rounds); 0: the
+ *   current device's (256 when none is visible).  Any other value makes the call host-only.
+ * *form: SM_FUSED_FORM_NOT_TAKEN -- the entry point returns SM_STATUS_NOT_SUPPORTED; _EMPTY -- success, nothing launched (a zero
+ * extent or count); else the kernel family.  Every form but _THIN is bit-identical to sm_compress24 + sm_spmma.
+ * Status: SM_STATUS_INVALID_VALUE for form == NULL, lda < k, count > 8, an unknown flag or _WORKSPACE with _EPILOGUE. */
+#define SM_FUSED_FORM_NOT_TAKEN 0
+#define SM_FUSED_FORM_EMPTY 1
+#define SM_FUSED_FORM_THIN 2          /* n < 8, k <= 64: vector ALUs (spmma_f16_thin_kernel)                              */
+#define SM_FUSED_FORM_SPAN 3          /* ragged k, one tall contiguous A, n <= 128 (spmma_f16_fused_span_kernel)           */
+#define SM_FUSED_FORM_STREAMK 4       /* workspace given, few tiles x long K (spmma_f16_fused_sk_kernel)                   */
+#define SM_FUSED_FORM_BIG 5           /* n > 128: 256 x 256 tiles (spmma_f16_fused_big_kernel)                             */
+#define SM_FUSED_FORM_DIRECT64 6      /* n <= 64 (spmma_f16_fused_direct_kernel, 64 columns)                               */
+#define SM_FUSED_FORM_DIRECT128 7     /* n <= 128 with k < 512, n <= 256 with k == 64: 128 columns, plain A loads          */
+#define SM_FUSED_FORM_DIRECT128_NT 8  /* n <= 128 with k >= 512: 128 columns, non-temporal A loads                         */
+#define SM_FUSED_FORM_ASTAT 9         /* n > 256, k <= 512, beta == 0, aligned C, no epilogue (spmma_f16_fused_astat_kernel) */
+#define SM_FUSED_FORM_WIDEP 10        /* n > 128, k <= 1024, no epilogue: persistent wide (spmma_f16_fused_widep_kernel)    */
+#define SM_FUSED_FORM_WIDE 11         /* n > 256: one workgroup per 128 x 256 tile (spmma_f16_fused_wide_kernel)           */
+#define SM_FUSED_FORM_WIDE_NT 12      /* n <= 256: the same with non-temporal A loads                                      */
+#define SM_FUSED_FLAG_A_ALIGNED 1u
+#define SM_FUSED_FLAG_B_ALIGNED 2u
+#define SM_FUSED_FLAG_C_ALIGNED 4u
+#define SM_FUSED_FLAG_WORKSPACE 8u
+#define SM_FUSED_FLAG_EPILOGUE 16u
+int sm_spmma_fused_form(size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t count, size_t strideA, size_t strideB, size_t strideC,
+                        float beta, unsigned flags, size_t cus, int* form);
 /* The dense entry points with the same workspace: the dense twin of the stream-K form (the dense GEMM the 2:4 path is measured
  * against gets the tile economy the 2:4 path gets); same workspace contract, same bit-identity statement for uncut tiles. */
 int sm_gemm_rowmajor_f16_ws(const void* A, const void* B, void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t strideA,

@@ -126,6 +126,7 @@ _SIGS["sm_spmma_fused_f32_split_prepared"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size
 _SIGS["sm_spmma_fused_workspace_size"] = [ctypes.POINTER(_c_size)]
 _SIGS["sm_spmma_fused_workspace_state"] = [_c_ptr, ctypes.POINTER(_c_i), _c_ptr]
 _SIGS["sm_spmma_fused_streamk_plan"] = [_c_size, _c_size, _c_size, _c_size, ctypes.POINTER(_c_i), ctypes.POINTER(ctypes.c_uint)]
+_SIGS["sm_spmma_fused_form"] = [_c_size] * 9 + [_c_f, ctypes.c_uint, _c_size, ctypes.POINTER(_c_i)]
 _SIGS["sm_gemm_rowmajor_f16_ws"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 8 + [_c_f, _c_f, _c_ptr, _c_size, _c_ptr]
 _SIGS["sm_gemm_rowmajor_bf16_ws"] = _SIGS["sm_gemm_rowmajor_f16_ws"]
 _SIGS["sm_gemm_batched_f16_ws"] = [_c_ptr, _c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_size, _c_i, _c_i, _c_f, _c_f, _c_ptr, _c_size, _c_ptr]
@@ -614,6 +615,26 @@ def spmma_fused_streamk_plan(rows, n, k, problems=1):
     _check(lib().sm_spmma_fused_streamk_plan(rows, n, k, problems, ctypes.byref(takes), buf), "sm_spmma_fused_streamk_plan")
     v = list(buf)
     return bool(takes.value), dict(tg=v[0], wg=v[1], groups_full=v[2], tgl=v[3], wgl=v[4], slots=v[5], units=v[6], cut=v[7:16], cutl=v[16:25])
+
+
+# include/sparsifyme.h: SM_FUSED_FORM_* (index = value) and SM_FUSED_FLAG_*
+FUSED_FORMS = ("not_taken", "empty", "thin", "span", "streamk", "big", "direct64", "direct128", "direct128_nt", "astat", "widep", "wide", "wide_nt")
+FUSED_FLAG_A_ALIGNED, FUSED_FLAG_B_ALIGNED, FUSED_FLAG_C_ALIGNED, FUSED_FLAG_WORKSPACE, FUSED_FLAG_EPILOGUE = 1, 2, 4, 8, 16
+
+
+def spmma_fused_form(m, n, k, lda=None, batch=1, count=1, strideA=None, strideB=0, strideC=None, beta=0.0, a_aligned=True, b_aligned=True,
+                     c_aligned=True, workspace=False, epilogue=False, cus=0):
+    """The name (FUSED_FORMS) of the kernel form spmma_fused / spmma_fused_grouped run for this launch -- sm_spmma_fused_form, the
+    rule the entry points themselves switch on.  cus=0: this device's compute units; another value: host-only."""
+    lda = k if lda is None else lda
+    strideA = m * lda if strideA is None else strideA
+    strideC = m * n if strideC is None else strideC
+    flags = ((FUSED_FLAG_A_ALIGNED if a_aligned else 0) | (FUSED_FLAG_B_ALIGNED if b_aligned else 0) | (FUSED_FLAG_C_ALIGNED if c_aligned else 0) |
+             (FUSED_FLAG_WORKSPACE if workspace else 0) | (FUSED_FLAG_EPILOGUE if epilogue else 0))
+    form = _c_i(-1)
+    _check(lib().sm_spmma_fused_form(m, n, k, lda, batch, count, strideA, strideB, strideC, float(beta), flags, cus, ctypes.byref(form)),
+           "sm_spmma_fused_form")
+    return FUSED_FORMS[form.value]
 
 
 def streamk_whole_panels(plan, panels, nkt):

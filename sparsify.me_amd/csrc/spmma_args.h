@@ -80,6 +80,12 @@ int gemm_dense_twin(const DenseTwinCall& c, hipStream_t st);
 
 // spmma_f16_thin.hip: the fused 2:4 product for n < 8, k <= 64 (depthwise convolutions as im2col products) on the vector ALUs;
 // SM_STATUS_NOT_SUPPORTED for anything else
+// the shapes it takes (ONE statement: asked by spmma_fused_thin itself and by the fused dispatch rule, spmma_f16_fused.hip: fused_form);
+// on top of these A is 16-byte aligned
+inline bool thin_form_takes(size_t ngroup, size_t rows, size_t n, size_t k) {
+  return !(n == 0 || n >= 8 || k == 0 || k > 64 || ngroup < 1 || ngroup > 8 || (rows * k * 2) % 16 != 0 || rows * k * 2 < 16) &&
+         (rows + 1023) / 1024 <= 0x7fffffffu;  // (its grid: 1024 rows per workgroup)
+}
 int spmma_fused_thin(bool bf, int ngroup, const void* const* A, const void* const* B, void* const* C, size_t rows, size_t n, size_t k,
                      float alpha, float beta, hipStream_t st);
 

@@ -661,30 +661,37 @@ static SkPlan sk_plan(size_t panels, size_t nkt, size_t tn, size_t cus) {
   return best;
 }
 
+// The stream-K launcher's own limits (32-bit tile offsets, panel, stage and workgroup counts), for `panels` > 0 row panels of 256 rows:
+// null when the launch fits, else why not.  ONE statement: asked by the launcher and by the dispatch rule (fused_form), for which a
+// launch that does not fit is "not taken" -- a _ws call must succeed wherever the same call without a workspace does.
+static const char* sk_launch_limits(size_t panels, size_t n, size_t k, size_t lda, size_t cus) {
+  const size_t nkt = k / 64, tn = (n + 255) / 256;
+  if (panels > 0x7fffffu || nkt == 0 || nkt > 0xffffu) return "sm_spmma_fused_f16: grid too large";
+  if ((size_t)256 * lda * 2 + k * 2 >= ((size_t)1 << 32) || (k + 64) * n * 2 >= ((size_t)1 << 31))
+    return "sm_spmma_fused_*_ws: leading dimension too large for the stream-K form's 32-bit tile offsets";
+  const SkPlan pl = sk_plan(panels, nkt, tn, cus);
+  const size_t nwg = (size_t)pl.slots * tn;
+  if (pl.slots == 0 || nwg > cus || nwg > 1023) return "sm_spmma_fused_*_ws: the shape has more column tiles than the stream-K form has compute units for";
+  return nullptr;
+}
+
 template <int BN, bool BF = false, bool ANT = true, bool DENSE = false>
 static int launch_fused_sk(const FusedArgs& a0, void* workspace, size_t workspace_bytes, hipStream_t st) {
   constexpr int BM = 256;
+  static_assert(BN == 256, "sk_launch_limits counts 256-column tiles");
   FusedArgs a = a0;
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t panels = (size_t)a.tiles_m * a.batch * a.ngroup;
   if (panels == 0) return SM_STATUS_SUCCESS;
   const size_t nkt = (size_t)a.K / 64;
-  if (panels > 0x7fffffu || nkt == 0 || nkt > 0xffffu) {
-    set_error("sm_spmma_fused_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  if ((size_t)256 * a.lda * 2 + (size_t)a.K * 2 >= ((size_t)1 << 32) || (size_t)(a.K + 64) * a.N * 2 >= ((size_t)1 << 31)) {
-    set_error("sm_spmma_fused_*_ws: leading dimension too large for the stream-K form's 32-bit tile offsets");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   const int cus = device_cu_count();
+  if (const char* why = sk_launch_limits(panels, (size_t)a.N, (size_t)a.K, (size_t)a.lda, (size_t)cus)) {
+    set_error("%s", why);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
   SkPlan pl = sk_plan(panels, nkt, (size_t)a.tiles_n, (size_t)cus);
   const size_t nwg = (size_t)pl.slots * a.tiles_n;
-  if (pl.slots == 0 || nwg > (size_t)cus || nwg > 1023) {
-    set_error("sm_spmma_fused_*_ws: the shape has more column tiles than the stream-K form has compute units for");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   if (!workspace || !aligned16(workspace) || workspace_bytes < sk_workspace_bytes(nwg, BN)) {
     set_error("sm_spmma_fused_*_ws: the stream-K form needs a 16-byte aligned workspace of sm_spmma_fused_workspace_size bytes");
     return SM_STATUS_INVALID_VALUE;
@@ -710,9 +717,9 @@ static int launch_fused_sk(const FusedArgs& a0, void* workspace, size_t workspac
 // sk_probe_r05d.txt); the big form = rounds x stages; a 128 x 256 tile's stage (wide kernel) takes ~0.6 of a 256 x 256 one
 // (profiles/stamp_r04b_big_wide_direct.txt).  The A-stationary shapes (n > 256, k <= 512, plain store) keep their kernel: few
 // stages per tile, nothing for a K split to balance.
-static bool sk_takes(size_t rows, size_t problems, size_t n, size_t k, bool astat_shape, SkPlan& pl) {
+static bool sk_takes(size_t rows, size_t problems, size_t n, size_t k, bool astat_shape, size_t cus, SkPlan& pl) {
   if (n <= 128 || k < 128 || k % 64 != 0) return false;
-  const size_t cus = (size_t)device_cu_count(), nkt = k / 64;
+  const size_t nkt = k / 64;
   const size_t panels = (rows + 255) / 256 * problems, tn = (n + 255) / 256;
   const size_t t_big = panels * tn, t_wide = (rows + 127) / 128 * tn * problems;
   pl = sk_plan(panels, nkt, tn, cus);
@@ -1523,6 +1530,14 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
 // (profiles/astatp_r03m.txt: 3136 x 512 x 128 x 4: 158.6 vs 140.2 us; 784 x 1024 x 256 x 6: 147.6 vs 124.9 us).  As with the
 // wide kernel's long-K tiles, statically assigned work loses to the hardware's dynamic dispatch.  Removed again)
 
+// Column splits of a row panel: split the column range over several workgroups until 3/4 of the CUs have one (a split re-selects
+// its A panel, so no more than needed: 784 x 1024 x 256, b = 32: 29 / 33 / 41 us with 1 / 2 / 4 splits); >= 2 tiles per split.
+// ONE statement: the launcher's grid and the dispatch rule's round efficiency (fused_form) both ask here.
+static size_t astat_nsplit(size_t panels, size_t tiles_n, size_t cus) {
+  size_t nsplit = 1;
+  while (panels * nsplit * 4 < 3 * cus && (tiles_n + 2 * nsplit - 1) / (2 * nsplit) >= 2) nsplit *= 2;
+  return nsplit;
+}
 static size_t astat_lds_bytes(int nkt, int nsb) { return (size_t)nkt * (128 * 72) + (size_t)nsb * 64 * 128 * 2 + 8 * 32 * (64 * 2 + 8); }
 
 template <bool BF = false>
@@ -1530,13 +1545,8 @@ static int launch_fused_astat(const FusedArgs& a0, hipStream_t st) {
   FusedArgs a = a0;
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + 127) / 128;
-  // split the column range of a row panel over several workgroups until 3/4 of the CUs have one (a split re-selects
-  // its A panel, so no more than needed: 784 x 1024 x 256, b = 32: 29 / 33 / 41 us with 1 / 2 / 4 splits); >= 2 tiles
-  // per split
-  const int cus = device_cu_count();
   const size_t panels = (size_t)a.tiles_m * a.batch * a.ngroup;
-  int nsplit = 1;
-  while (panels * nsplit * 4 < (size_t)3 * cus && (a.tiles_n + 2 * nsplit - 1) / (2 * nsplit) >= 2) nsplit *= 2;
+  int nsplit = (int)astat_nsplit(panels, (size_t)a.tiles_n, (size_t)device_cu_count());
   int tps = (a.tiles_n + nsplit - 1) / nsplit;
   nsplit = (a.tiles_n + tps - 1) / tps;  // no empty splits
   const size_t nwg = panels * nsplit;
@@ -1557,8 +1567,13 @@ static int launch_fused_astat(const FusedArgs& a0, hipStream_t st) {
 
 using namespace sm;
 
-// Which shapes the two exact forms take -- ONE statement of each rule, used by spmma_fused16 below and by sm::spmma_fused16_takes_exact
-// (the prune-in-place + multiply entry points ask BEFORE they modify A, csrc/spmma_f16_pruned.hip).
+// ---------------------------------------------------------------------------------------------
+// THE DISPATCH RULE of sm_spmma_fused_{f16,bf16} and their _grouped / _ws / _ex forms -- ONE statement (fused_form), a pure host
+// function of the call's shape, alignments and the CU count: spmma_fused16 below switches on its answer, sm_spmma_fused_form
+// exports it (tests assert which form a shape runs), sm::spmma_fused16_takes_exact is a question put to it.  The sub-rules it is
+// made of (thin_form_takes, span_form_takes, stage_forms_take, dims_fit_int, sk_takes, sk_launch_limits, astat_nsplit) are each
+// stated once as well; the launchers share them.
+// ---------------------------------------------------------------------------------------------
 // span form: rows that are not whole 64-deep stages of 16-byte pieces, when A is one tall contiguous matrix, n <= 128 and a 128-row
 // span + the whole B fit the LDS (k = 147: the stem layer of every ResNet)
 static bool span_form_takes(size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t strideA, size_t strideB, size_t strideC, bool all_aligned, bool c_aligned) {
@@ -1573,97 +1588,60 @@ static bool stage_forms_take(size_t n, size_t k, size_t lda, size_t strideA, siz
 static bool dims_fit_int(size_t m, size_t n, size_t k, size_t lda, size_t batch) {
   return !(m * batch > 0x7fffffffull || n > 0x7fffffffull || k > 0x7fffffffull || lda > 0x7fffffffull);
 }
-bool sm::spmma_fused16_takes_exact(const void* A, const void* B, const void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t strideA, size_t strideB,
-                                   size_t strideC) {
-  if (!A || !B || !C || lda < k || m == 0 || n == 0 || batch == 0) return false;
-  if (n < 8 && k <= 64) return false;  // the thin form: inside the tight bound of the product, not the staged pair's bits
-  const bool all_aligned = aligned16(A) && aligned16(B), c_aligned = aligned16(C);
-  if (span_form_takes(m, n, k, lda, batch, strideA, strideB, strideC, all_aligned, c_aligned)) return true;
-  return stage_forms_take(n, k, lda, strideA, strideB, all_aligned) && dims_fit_int(m, n, k, lda, batch);
-}
 
-template <bool BF>
-static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const* Bg, void* const* Cg, size_t m, size_t n, size_t k, size_t lda,
-                         size_t batch, size_t strideA, size_t strideB, size_t strideC, float alpha, float beta,
-                         sm_stream_t stream, void* workspace = nullptr, size_t workspace_bytes = 0, const EpiArgs* epi = nullptr) {
-  // epi: sm_spmma_fused_*_ex with an epilogue that is not the plain one (a single problem, no workspace).  The same rules pick
-  // the kernel; the forms whose stores are their own (thin, A-stationary, persistent wide) are not taken.
-#define SM_LAUNCH(fn, ...) (epi ? fn<__VA_ARGS__, true>(ae, st) : fn<__VA_ARGS__, false>(a, st))
-  if (ngroup == 0) return SM_STATUS_SUCCESS;
-  if (!Ag || !Bg || !Cg || lda < k || ngroup > (size_t)MAXG) {
-    set_error("sm_spmma_fused_{f16,bf16}: invalid argument");
-    return SM_STATUS_INVALID_VALUE;
-  }
-  bool all_aligned = true, c_aligned = true;
-  for (size_t g = 0; g < ngroup; ++g) {
-    if (!Ag[g] || !Bg[g] || !Cg[g]) {
-      set_error("sm_spmma_fused_{f16,bf16}: invalid argument (null operand)");
-      return SM_STATUS_INVALID_VALUE;
-    }
-    all_aligned = all_aligned && aligned16(Ag[g]) && aligned16(Bg[g]);
-    c_aligned = c_aligned && aligned16(Cg[g]);
-  }
-  if (m == 0 || n == 0 || batch == 0) return SM_STATUS_SUCCESS;
+// Everything the rule reads of ONE launch (`count` <= MAXG same-shape problems; the operands are valid: non-null, lda >= k).
+struct FusedCall {
+  size_t m, n, k, lda, batch, count, sA, sB, sC;
+  float beta;
+  bool a_aligned, b_aligned, c_aligned;  // every problem's A / B / C starts on a 16-byte boundary
+  bool ws, ws_aligned;                   // a workspace was given (the _ws entry points); it is 16-byte aligned
+  size_t ws_bytes;
+  bool epi, r_aligned;                   // an epilogue that is not the plain one (_ex); its residual (read when beta != 0) is 16-byte aligned
+  size_t sR;                             // the residual's batch stride
+};
+struct FusedPick {
+  int form;         // SM_FUSED_FORM_*
+  bool stacked;     // the batches run as one tall matrix of m * batch rows
+  const char* why;  // SM_FUSED_FORM_NOT_TAKEN: the message of the call's SM_STATUS_NOT_SUPPORTED
+};
+
+static FusedPick fused_form(const FusedCall& c, size_t cus) {
+  const size_t m = c.m, n = c.n, k = c.k, lda = c.lda, batch = c.batch;
+  if (c.count == 0 || m == 0 || n == 0 || batch == 0) return {SM_FUSED_FORM_EMPTY, false, nullptr};
+  const bool all_aligned = c.a_aligned && c.b_aligned;
+  const bool contiguous = c.sB == 0 && c.sA == m * lda && c.sC == m * n;  // shared B, batches back to back: one tall matrix
   // (round 5) thin problems -- n < 8, k <= 64, one tall contiguous A, shared B: the depthwise layers of the model zoo -- on the
-  // vector ALUs (spmma_f16_thin.hip); result inside the tight bound of the exact product, not bit-identical to the staged pair
-  if (n < 8 && k <= 64 && lda == k && (batch == 1 || (strideB == 0 && strideA == m * lda && strideC == m * n))) {
-    if (epi) {
-      set_error("sm_spmma_fused_{f16,bf16}_ex: the thin form (n < 8) takes no epilogue");
-      return SM_STATUS_NOT_SUPPORTED;
-    }
-    const int rc = spmma_fused_thin(BF, (int)ngroup, Ag, Bg, Cg, m * batch, n, k, alpha, beta, (hipStream_t)stream);
-    if (rc != SM_STATUS_NOT_SUPPORTED) return rc;
+  // vector ALUs (spmma_f16_thin.hip); result inside the tight bound of the exact product, not bit-identical to the staged pair.
+  // What the thin launcher itself declines (thin_form_takes, an A off a 16-byte boundary) falls through to the forms below.
+  if (n < 8 && k <= 64 && lda == k && (batch == 1 || contiguous)) {
+    if (c.epi) return {SM_FUSED_FORM_NOT_TAKEN, false, "sm_spmma_fused_{f16,bf16}_ex: the thin form (n < 8) takes no epilogue"};
+    if (thin_form_takes(c.count, m * batch, n, k) && c.a_aligned) return {SM_FUSED_FORM_THIN, true, nullptr};
   }
-  // rows that are not whole 64-deep stages of 16-byte pieces: the span form, when A is one tall contiguous matrix, n <= 128
-  // and a 128-row span + the whole B fit the LDS (k = 147: the stem layer of every ResNet)
+  // rows that are not whole 64-deep stages of 16-byte pieces: the span form (span_form_takes)
   // (a residual that is read must follow D: 16-byte aligned, batches back to back)
-  const bool r_follows = !epi || beta == 0.0f || (aligned16(epi->R) && (batch == 1 || epi->sR == m * n));
-  if (span_form_takes(m, n, k, lda, batch, strideA, strideB, strideC, all_aligned, c_aligned && r_follows)) {
-    FusedArgs a = {};
-    for (size_t g = 0; g < (size_t)MAXG; ++g) {
-      const size_t s_ = g < ngroup ? g : 0;
-      a.A[g] = (const half_t*)Ag[s_]; a.B[g] = (const half_t*)Bg[s_]; a.C[g] = (half_t*)Cg[s_];
-    }
-    a.ngroup = (int)ngroup;
-    a.Mrows = (int)(m * batch); a.N = (int)n; a.K = (int)k; a.lda = (int)lda;
-    a.batch = 1; a.alpha = alpha; a.beta = beta;
-    hipStream_t st = (hipStream_t)stream;
-    FusedArgsEpi ae = {};
-    static_cast<FusedArgs&>(ae) = a;
-    if (epi) ae.e = *epi;
-    return n <= 64 ? SM_LAUNCH(launch_fused_span, 64, BF, false) : SM_LAUNCH(launch_fused_span, 128, BF, false);
-  }
+  const bool r_follows = !c.epi || c.beta == 0.0f || (c.r_aligned && (batch == 1 || c.sR == m * n));
+  if (span_form_takes(m, n, k, lda, batch, c.sA, c.sB, c.sC, all_aligned, c.c_aligned && r_follows)) return {SM_FUSED_FORM_SPAN, true, nullptr};
   // whole 64-deep stages of 16-byte aligned rows only; anything else: sm_compress24_f16 + sm_spmma_f16
-  if (!stage_forms_take(n, k, lda, strideA, strideB, all_aligned)) {
-    set_error("sm_spmma_fused_{f16,bf16}: needs k %% 64 == 0, n %% 8 == 0 and 16-byte aligned rows (use the staged path)");
-    return SM_STATUS_NOT_SUPPORTED;
+  if (!stage_forms_take(n, k, lda, c.sA, c.sB, all_aligned))
+    return {SM_FUSED_FORM_NOT_TAKEN, false, "sm_spmma_fused_{f16,bf16}: needs k % 64 == 0, n % 8 == 0 and 16-byte aligned rows (use the staged path)"};
+  if (c.count > 1 && !c.c_aligned)  // (the kernels' scalar C path keys on the pointer: one decision per launch)
+    return {SM_FUSED_FORM_NOT_TAKEN, false, "sm_spmma_fused_{f16,bf16}_grouped: needs 16-byte aligned C operands"};
+  if (!dims_fit_int(m, n, k, lda, batch)) return {SM_FUSED_FORM_NOT_TAKEN, false, "sm_spmma_fused_{f16,bf16}: dimension exceeds 2^31-1"};
+  // shared B and batches back to back (and a residual that is read laid out like D): one tall matrix of m * batch rows
+  const bool stacked = batch > 1 && contiguous && (!c.epi || c.beta == 0.0f || c.sR == m * n);
+  const size_t rows = stacked ? m * batch : m, nb = (stacked ? 1 : batch) * c.count;
+  // the A-stationary kernel's shapes: n > 256, short K, plain store of a 16-byte aligned C (beta == 0)
+  const bool astat_store = n > 256 && k <= 512 && c.beta == 0.0f && c.c_aligned && (c.sC % 8 == 0);
+  // (round 5) with a workspace: the STREAM-K form where the rounds of whole tiles leave CUs idle (sk_takes).  The A-stationary shapes
+  // keep their kernel: few stages per tile, nothing for a K split to balance.
+  //  the stream-K launcher's own limits (sk_launch_limits) are "not taken", not a failure of the call: a _ws call
+  // must succeed wherever the same call without a workspace does -- the forms below
+  if (c.ws) {
+    SkPlan pl;
+    if (sk_takes(rows, nb, n, k, astat_store, cus, pl) && c.ws_bytes >= sk_workspace_bytes((size_t)pl.slots * ((n + 255) / 256), 256) && c.ws_aligned &&
+        !sk_launch_limits((rows + 255) / 256 * nb, n, k, lda, cus))
+      return {SM_FUSED_FORM_STREAMK, stacked, nullptr};
   }
-  if (ngroup > 1 && !c_aligned) {  // (the kernels' scalar C path keys on the pointer: one decision per launch)
-    set_error("sm_spmma_fused_{f16,bf16}_grouped: needs 16-byte aligned C operands");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  if (!dims_fit_int(m, n, k, lda, batch)) {
-    set_error("sm_spmma_fused_{f16,bf16}: dimension exceeds 2^31-1");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  FusedArgs a = {};
-  for (size_t g = 0; g < (size_t)MAXG; ++g) {  // unused slots repeat problem 0 (never indexed: grp < ngroup)
-    const size_t s_ = g < ngroup ? g : 0;
-    a.A[g] = (const half_t*)Ag[s_]; a.B[g] = (const half_t*)Bg[s_]; a.C[g] = (half_t*)Cg[s_];
-  }
-  a.ngroup = (int)ngroup;
-  void* const C = Cg[0];
-  a.sA = strideA; a.sB = strideB; a.sC = strideC;
-  a.Mrows = (int)m; a.N = (int)n; a.K = (int)k; a.lda = (int)lda;
-  a.batch = (int)batch; a.alpha = alpha; a.beta = beta;
-  if (batch > 1 && strideB == 0 && strideA == m * lda && strideC == m * n && (!epi || beta == 0.0f || epi->sR == m * n)) {
-    a.Mrows = (int)(m * batch);
-    a.batch = 1;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  FusedArgsEpi ae = {};
-  static_cast<FusedArgs&>(ae) = a;
-  if (epi) ae.e = *epi;
   // n <= 128 (and n <= 256 with a single stage): the direct kernel -- dense A by LDS-DMA, selection in the consumer's
   // registers, ring of 2 so that three workgroups share a CU.
   // (round 4) n > 128: the 256-row BIG form where its one-per-CU workgroups fill the chip's rounds at least as well as the
@@ -1671,53 +1649,29 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   // 784 x 512 x 1024; it loses where halving the tile count empties the last round: 784 x 256 x 2304 x 6 = 588 tiles = 2.3
   // rounds against 4.6, 196 x 512 x 2048 x 2 = 100 tiles against 196).  Against the A-stationary kernel (n > 256, k <= 512) it
   // needs a clear margin (196 x 2048 x 512 x 3: 59 vs 68 us; 784 x 1024 x 256 x 6: 126 vs 111).
-  auto round_eff = [](size_t tiles, size_t cus) { const size_t r = (tiles + cus - 1) / cus; return r ? (double)tiles / (double)(r * cus) : 1.0; };
-  // (round 5) with a workspace: the STREAM-K form where the rounds of whole tiles leave CUs idle.  Costs in stages of a 256 x 256
-  // tile: stream-K = its share of the stage units + ~3 stages for the fix-up of the two tiles a range cuts; the big form = rounds x
-  // stages; a 128 x 256 tile's stage (wide kernel) takes ~0.6 of a 256 x 256 one (profiles/stamp_r04b_big_wide_direct.txt).  The
-  // A-stationary shapes (n > 256, k <= 512) keep their kernel: few stages per tile, nothing for a K split to balance.
-  if (workspace) {
-    const bool astat_shape = n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0);
-    SkPlan pl;
-    if (sk_takes((size_t)a.Mrows, (size_t)a.batch * a.ngroup, n, k, astat_shape, pl) &&
-        workspace_bytes >= sk_workspace_bytes((size_t)pl.slots * ((n + 255) / 256), 256) && aligned16(workspace)) {
-      //  the stream-K launcher's own limits (32-bit tile offsets, panel and workgroup counts) are "not taken", not a failure
-      // of the call: a _ws call must succeed wherever the same call without a workspace does -- fall through to the forms below
-      const int rc = n <= 256 ? launch_fused_sk<256, BF, true>(a, workspace, workspace_bytes, st) : launch_fused_sk<256, BF, false>(a, workspace, workspace_bytes, st);
-      if (rc != SM_STATUS_NOT_SUPPORTED) return rc;
-    }
-  }
+  auto round_eff = [](size_t tiles, size_t cus_) { const size_t r = (tiles + cus_ - 1) / cus_; return r ? (double)tiles / (double)(r * cus_) : 1.0; };
   if (n > 128 && k > 64) {
-    const size_t cus = (size_t)device_cu_count(), nb = (size_t)a.batch * a.ngroup;
-    const size_t t_big = ((size_t)a.Mrows + 255) / 256 * ((n + 255) / 256) * nb, t_wide = ((size_t)a.Mrows + 127) / 128 * ((n + 255) / 256) * nb;
-    const bool astat_shape = !epi && n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0);
+    const size_t t_big = (rows + 255) / 256 * ((n + 255) / 256) * nb, t_wide = (rows + 127) / 128 * ((n + 255) / 256) * nb;
     bool big = round_eff(t_big, cus) >= round_eff(t_wide, cus);
-    if (astat_shape) {
-      const size_t panels = ((size_t)a.Mrows + 127) / 128 * nb;
-      size_t ns = 1, tn = (n + 127) / 128;
-      while (panels * ns * 4 < 3 * cus && (tn + 2 * ns - 1) / (2 * ns) >= 2) ns *= 2;
-      big = round_eff(t_big, cus) > round_eff(panels * ns, cus) + 0.1;
+    if (!c.epi && astat_store) {
+      const size_t panels = (rows + 127) / 128 * nb;
+      big = round_eff(t_big, cus) > round_eff(panels * astat_nsplit(panels, (n + 127) / 128, cus), cus) + 0.1;
     }
-    // (the hint on the big form's A loads, n <= 256: measured indifferent, profiles/nt_ab_r05q.txt)
-    if (big) return n <= 256 ? SM_LAUNCH(launch_fused_big, 256, BF, 3, 2, true, false) : SM_LAUNCH(launch_fused_big, 256, BF, 3, 2, false, false);
+    if (big) return {SM_FUSED_FORM_BIG, stacked, nullptr};
   }
   // (round 5: 128-column direct tiles at ANY n -- every column tile re-reading its A rows through L2, as 12544 x 256 x 64 does at 0.89 of its roofline -- measured on
   //  the shapes the A-stationary and wide kernels serve: slower on all of them, 3136 x 512 x 128 x 4 147 vs 129 us, 784 x 1024 x 256 x 6 164 vs 114, 784 x 256 x 2304 x 6
   //  303 vs 195, 196 x 512 x 2048 x 2 55 vs 32 (profiles/ab_direct_any_r05an.txt; the rows whose two columns agree went to the big form before the hook).  Removed.)
   if (n <= 128 || (n <= 256 && k <= 64)) {
-    if (n <= 64) return SM_LAUNCH(launch_fused_direct, 64, 2, BF, 128, 4, true, false);
+    if (n <= 64) return {SM_FUSED_FORM_DIRECT64, stacked, nullptr};
     // (round 5) the non-temporal hint on the A loads only where A really is read once and streams long: with two column tiles (n = 256,
     // k = 64) the second tile's read of the same rows then misses L2 -- 12544 x 256 x 64 x 3: 200 -> 166 us without the hint -- and the
     // short-K 128-column layer is 5 % faster without it too (12544 x 128 x 256: 68.7 -> 64.8 us); 3136 x 128 x 512 / 1152 and every
     // 64-column shape keep it (1-6 % faster with it; profiles/nt_ab_r05q.txt).  Same C either way.
-    if (n > 128 || k < 512) return SM_LAUNCH(launch_fused_direct, 128, 2, BF, 128, 4, false, false);
-    return SM_LAUNCH(launch_fused_direct, 128, 2, BF, 128, 4, true, false);
+    return {n > 128 || k < 512 ? SM_FUSED_FORM_DIRECT128 : SM_FUSED_FORM_DIRECT128_NT, stacked, nullptr};
   }
   // n > 256, short K, plain store: A-stationary (the 2:4 image of a row panel stays in LDS across column tiles)
-  if (!epi && n > 256 && k <= 512 && beta == 0.0f && aligned16(C) && (strideC % 8 == 0) &&
-      astat_lds_bytes((int)(k / 64), 3) <= 160 * 1024) {
-    return launch_fused_astat<BF>(a, st);
-  }
+  if (!c.epi && astat_store && astat_lds_bytes((int)(k / 64), 3) <= 160 * 1024) return {SM_FUSED_FORM_ASTAT, stacked, nullptr};
   // wider: 256-column tiles, 8 consumer waves (wave tile 32 x 128), split loaders; for n <= 256 every row of A is loaded
   // and selected exactly once, beyond that once per 256 columns (callers with n >= 512, a long K and a reusable A are
   // better served by sm_compress24_f16 + sm_spmma_f16: bench.py --path auto decides per layer).  Three A stages in
@@ -1726,9 +1680,103 @@ static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const
   // 39.5 vs 43.9 us per instance, 784 x 256 x 1024: 19.6 vs 20.3; on 36- and 72-stage tiles the statically assigned tiles
   // lose to the hardware's dynamic dispatch (784 x 256 x 2304: 40.5 vs 39.1, 196 x 512 x 4608: 41.0 vs 35.3;
   // profiles/widep_r03g.txt), so those keep one workgroup per tile.
-  if (k <= 1024 && !epi) return launch_fused_widep<256, 4, 2, 4, 2, 3, BF>(a, st);
-  if (n > 256) return SM_LAUNCH(launch_fused_wide, 256, 4, 2, 4, 2, 3, BF, false);  // several column tiles read the same A rows: no non-temporal hint
-  return SM_LAUNCH(launch_fused_wide, 256, 4, 2, 4, 2, 3, BF, true);
+  if (k <= 1024 && !c.epi) return {SM_FUSED_FORM_WIDEP, stacked, nullptr};
+  // several column tiles read the same A rows: no non-temporal hint
+  return {n > 256 ? SM_FUSED_FORM_WIDE : SM_FUSED_FORM_WIDE_NT, stacked, nullptr};
+}
+
+static bool fused_form_is_exact(int form) { return form != SM_FUSED_FORM_NOT_TAKEN && form != SM_FUSED_FORM_EMPTY && form != SM_FUSED_FORM_THIN; }
+
+// Does a plain single call run one of the EXACT forms (the thin form is inside the tight bound, not the staged pair's bits)?  Which
+// kernel it would be depends on the CU count; whether one takes the call does not.
+bool sm::spmma_fused16_takes_exact(const void* A, const void* B, const void* C, size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t strideA, size_t strideB,
+                                   size_t strideC) {
+  if (!A || !B || !C || lda < k) return false;
+  const FusedCall c = {m, n, k, lda, batch, 1, strideA, strideB, strideC, 0.0f, aligned16(A), aligned16(B), aligned16(C), false, false, 0, false, false, 0};
+  return fused_form_is_exact(fused_form(c, 256).form);
+}
+
+// cus == 0: this device's compute units; any other value: the rule's answer for a device of that many, no device asked.
+// flags: SM_FUSED_FLAG_*; an epilogue's residual is taken to be laid out like D (16-byte aligned when C is, strideR == strideC).
+extern "C" int sm_spmma_fused_form(size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t count, size_t strideA, size_t strideB, size_t strideC,
+                                   float beta, unsigned flags, size_t cus, int* form) {
+  constexpr unsigned known = SM_FUSED_FLAG_A_ALIGNED | SM_FUSED_FLAG_B_ALIGNED | SM_FUSED_FLAG_C_ALIGNED | SM_FUSED_FLAG_WORKSPACE | SM_FUSED_FLAG_EPILOGUE;
+  if (!form || lda < k || count > (size_t)MAXG || (flags & ~known) || ((flags & SM_FUSED_FLAG_WORKSPACE) && (flags & SM_FUSED_FLAG_EPILOGUE))) {
+    set_error("sm_spmma_fused_form: invalid argument");
+    return SM_STATUS_INVALID_VALUE;
+  }
+  const bool c_al = (flags & SM_FUSED_FLAG_C_ALIGNED) != 0, ws = (flags & SM_FUSED_FLAG_WORKSPACE) != 0;
+  const FusedCall c = {m, n, k, lda, batch, count, strideA, strideB, strideC, beta, (flags & SM_FUSED_FLAG_A_ALIGNED) != 0, (flags & SM_FUSED_FLAG_B_ALIGNED) != 0, c_al,
+                       ws, ws, ws ? ~(size_t)0 : 0, (flags & SM_FUSED_FLAG_EPILOGUE) != 0, c_al, strideC};
+  *form = fused_form(c, cus ? cus : (size_t)device_cu_count()).form;
+  return SM_STATUS_SUCCESS;
+}
+
+template <bool BF>
+static int spmma_fused16(size_t ngroup, const void* const* Ag, const void* const* Bg, void* const* Cg, size_t m, size_t n, size_t k, size_t lda,
+                         size_t batch, size_t strideA, size_t strideB, size_t strideC, float alpha, float beta,
+                         sm_stream_t stream, void* workspace = nullptr, size_t workspace_bytes = 0, const EpiArgs* epi = nullptr) {
+  // epi: sm_spmma_fused_*_ex with an epilogue that is not the plain one (a single problem, no workspace).  The same rule picks
+  // the kernel; the forms whose stores are their own (thin, A-stationary, persistent wide) are not taken.
+#define SM_LAUNCH(fn, ...) (epi ? fn<__VA_ARGS__, true>(ae, st) : fn<__VA_ARGS__, false>(a, st))
+  if (ngroup == 0) return SM_STATUS_SUCCESS;
+  if (!Ag || !Bg || !Cg || lda < k || ngroup > (size_t)MAXG) {
+    set_error("sm_spmma_fused_{f16,bf16}: invalid argument");
+    return SM_STATUS_INVALID_VALUE;
+  }
+  FusedCall c = {m, n, k, lda, batch, ngroup, strideA, strideB, strideC, beta, true, true, true, workspace != nullptr, aligned16(workspace), workspace_bytes,
+                 epi != nullptr, epi && aligned16(epi->R), epi ? epi->sR : 0};
+  for (size_t g = 0; g < ngroup; ++g) {
+    if (!Ag[g] || !Bg[g] || !Cg[g]) {
+      set_error("sm_spmma_fused_{f16,bf16}: invalid argument (null operand)");
+      return SM_STATUS_INVALID_VALUE;
+    }
+    c.a_aligned = c.a_aligned && aligned16(Ag[g]);
+    c.b_aligned = c.b_aligned && aligned16(Bg[g]);
+    c.c_aligned = c.c_aligned && aligned16(Cg[g]);
+  }
+  const FusedPick pick = fused_form(c, (size_t)device_cu_count());
+  hipStream_t st = (hipStream_t)stream;
+  FusedArgs a = {};
+  for (size_t g = 0; g < (size_t)MAXG; ++g) {  // unused slots repeat problem 0 (never indexed: grp < ngroup)
+    const size_t s_ = g < ngroup ? g : 0;
+    a.A[g] = (const half_t*)Ag[s_]; a.B[g] = (const half_t*)Bg[s_]; a.C[g] = (half_t*)Cg[s_];
+  }
+  a.ngroup = (int)ngroup;
+  a.N = (int)n; a.K = (int)k; a.lda = (int)lda;
+  a.alpha = alpha; a.beta = beta;
+  if (pick.stacked) {
+    a.Mrows = (int)(m * batch);
+    a.batch = 1;
+  } else {
+    a.Mrows = (int)m;
+    a.batch = (int)batch;
+  }
+  if (pick.form != SM_FUSED_FORM_SPAN) { a.sA = strideA; a.sB = strideB; a.sC = strideC; }  // (the span form has no batch strides: one tall matrix)
+  FusedArgsEpi ae = {};
+  static_cast<FusedArgs&>(ae) = a;
+  if (epi) ae.e = *epi;
+  switch (pick.form) {
+    case SM_FUSED_FORM_EMPTY: return SM_STATUS_SUCCESS;
+    case SM_FUSED_FORM_NOT_TAKEN:
+      set_error("%s", pick.why);
+      return SM_STATUS_NOT_SUPPORTED;
+    case SM_FUSED_FORM_THIN: return spmma_fused_thin(BF, (int)ngroup, Ag, Bg, Cg, m * batch, n, k, alpha, beta, st);
+    case SM_FUSED_FORM_SPAN: return n <= 64 ? SM_LAUNCH(launch_fused_span, 64, BF, false) : SM_LAUNCH(launch_fused_span, 128, BF, false);
+    case SM_FUSED_FORM_STREAMK:
+      return n <= 256 ? launch_fused_sk<256, BF, true>(a, workspace, workspace_bytes, st) : launch_fused_sk<256, BF, false>(a, workspace, workspace_bytes, st);
+    // (the hint on the big form's A loads, n <= 256: measured indifferent, profiles/nt_ab_r05q.txt)
+    case SM_FUSED_FORM_BIG: return n <= 256 ? SM_LAUNCH(launch_fused_big, 256, BF, 3, 2, true, false) : SM_LAUNCH(launch_fused_big, 256, BF, 3, 2, false, false);
+    case SM_FUSED_FORM_DIRECT64: return SM_LAUNCH(launch_fused_direct, 64, 2, BF, 128, 4, true, false);
+    case SM_FUSED_FORM_DIRECT128: return SM_LAUNCH(launch_fused_direct, 128, 2, BF, 128, 4, false, false);
+    case SM_FUSED_FORM_DIRECT128_NT: return SM_LAUNCH(launch_fused_direct, 128, 2, BF, 128, 4, true, false);
+    case SM_FUSED_FORM_ASTAT: return launch_fused_astat<BF>(a, st);
+    case SM_FUSED_FORM_WIDEP: return launch_fused_widep<256, 4, 2, 4, 2, 3, BF>(a, st);
+    case SM_FUSED_FORM_WIDE: return SM_LAUNCH(launch_fused_wide, 256, 4, 2, 4, 2, 3, BF, false);
+    case SM_FUSED_FORM_WIDE_NT: return SM_LAUNCH(launch_fused_wide, 256, 4, 2, 4, 2, 3, BF, true);
+  }
+  set_error("sm_spmma_fused_{f16,bf16}: internal error (unknown form)");
+  return SM_STATUS_LAUNCH_FAILED;
 #undef SM_LAUNCH
 }
 
@@ -1801,7 +1849,7 @@ extern "C" int sm_spmma_fused_streamk_plan(size_t rows, size_t n, size_t k, size
     return SM_STATUS_INVALID_VALUE;
   }
   SkPlan pl = {};
-  *takes = sk_takes(rows, problems, n, k, n > 256 && k <= 512, pl) ? 1 : 0;
+  *takes = sk_takes(rows, problems, n, k, n > 256 && k <= 512, (size_t)device_cu_count(), pl) ? 1 : 0;
   unsigned* o = plan;
   *o++ = pl.tg; *o++ = pl.wg; *o++ = pl.groups_full; *o++ = pl.tgl; *o++ = pl.wgl; *o++ = pl.slots; *o++ = pl.units;
   for (int i = 0; i < 9; ++i) *o++ = pl.cut[i];
@@ -1847,7 +1895,7 @@ static int dense_twin16(const DenseTwinCall& c, hipStream_t st) {
   // returns (196 x 512 x 4608 x 3: 163 us against 110, profiles/ab_streamk_r05e.txt)
   if (c.workspace && n > 128 && n <= 256 && k >= 2048) {
     SkPlan pl;
-    if (sk_takes((size_t)c.M, (size_t)c.batch, n, k, false, pl) && c.workspace_bytes >= sk_workspace_bytes((size_t)pl.slots * ((n + 255) / 256), 256) &&
+    if (sk_takes((size_t)c.M, (size_t)c.batch, n, k, false, (size_t)device_cu_count(), pl) && c.workspace_bytes >= sk_workspace_bytes((size_t)pl.slots * ((n + 255) / 256), 256) &&
         aligned16(c.workspace))
       return launch_fused_sk<256, BF, true, true>(a, c.workspace, c.workspace_bytes, st);
   }

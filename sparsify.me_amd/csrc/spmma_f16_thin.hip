@@ -99,9 +99,13 @@ __global__ __launch_bounds__(256) void spmma_f16_thin_kernel(const ThinArgs p) {
 // n < 8, k <= 64, one tall contiguous A per problem (rows = m * batch, lda == k), shared B; up to 8 same-shape problems per launch.
 int spmma_fused_thin(bool bf, int ngroup, const void* const* A, const void* const* B, void* const* C, size_t rows, size_t n, size_t k,
                      float alpha, float beta, hipStream_t st) {
-  if (n == 0 || n >= 8 || k == 0 || k > 64 || ngroup < 1 || ngroup > 8 || (rows * k * 2) % 16 != 0 || rows * k * 2 < 16) return SM_STATUS_NOT_SUPPORTED;
+  static_assert(THIN_ROWS == 1024, "thin_form_takes (spmma_args.h) states the grid limit for 1024 rows per workgroup");
+  if (!thin_form_takes((size_t)(ngroup < 0 ? 0 : ngroup), rows, n, k)) return SM_STATUS_NOT_SUPPORTED;
   for (int g = 0; g < ngroup; ++g)
-    if (!aligned16(A[g]) || (reinterpret_cast<uintptr_t>(B[g]) & 1u) || (reinterpret_cast<uintptr_t>(C[g]) & 1u)) return SM_STATUS_NOT_SUPPORTED;
+    if (!aligned16(A[g]) || (reinterpret_cast<uintptr_t>(B[g]) & 1u) || (reinterpret_cast<uintptr_t>(C[g]) & 1u)) {
+      set_error("sm_spmma_fused_{f16,bf16}: the thin form needs a 16-byte aligned A and element-aligned B and C");
+      return SM_STATUS_NOT_SUPPORTED;
+    }
   ThinArgs a = {};
   for (int g = 0; g < 8; ++g) {
     const int s_ = g < ngroup ? g : 0;
@@ -109,10 +113,6 @@ int spmma_fused_thin(bool bf, int ngroup, const void* const* A, const void* cons
   }
   a.rows = rows; a.N = (int)n; a.K = (int)k; a.alpha = alpha; a.beta = beta;
   const size_t nblk = (rows + THIN_ROWS - 1) / THIN_ROWS;
-  if (nblk > 0x7fffffffu) {
-    set_error("sm_spmma_fused_{f16,bf16}: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   const size_t lds = (size_t)THIN_ROWS * k * 2 + 16 + k * n * 4 + 16;   // <= 128 KiB + 1.8 KiB
   static LdsOptIn optin_h, optin_b;
   if (bf) {

@@ -367,23 +367,34 @@ def check_close(got, ref, scale, tol, what, k, out="f16"):
                           f"(max err {err.max():.3e}, k = {k}, out = {out})")
 
 
+_REPORTS_WRITTEN = []
+
+
+def write_margin_report(lines):
+    """Print a margin report and keep it in the run's output directory: the first report of a session starts the file anew, a
+    later module's report follows it."""
+    import os
+    print("\n".join(lines))
+    mode = "a" if _REPORTS_WRITTEN else "w"
+    _REPORTS_WRITTEN.append(len(lines))
+    try:
+        d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, "parity_margins.txt"), mode) as fh:
+            fh.write("\n".join(lines) + "\n")
+    except OSError:
+        pass
+
+
 @pytest.fixture(scope="module", autouse=True)
 def _parity_margin_report():
     yield
     if not MARGINS:
         return
-    import os
     worst = sorted(MARGINS, key=lambda t: -t[1])[:25]
     lines = [f"{len(MARGINS)} GEMM-type comparisons against the fp64 oracle; err / (ROUND*|ref| + 2k*ACC*sum|ab|), worst first:"]
     lines += [f"  {r:6.3f}  {w}" for w, r in worst]
-    print("\n".join(lines))
-    try:
-        d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-        os.makedirs(d, exist_ok=True)
-        with open(os.path.join(d, "parity_margins.txt"), "w") as fh:
-            fh.write("\n".join(lines) + "\n")
-    except OSError:
-        pass
+    write_margin_report(lines)
 
 
 def test_mfma_lane_maps_with_identity_and_asymmetric_b(gpu, orc):
@@ -627,6 +638,7 @@ def test_fused_thin_vs_oracle(gpu, orc, shape, bf, ab):
     import torch
     m, n, k, batch = shape
     alpha, beta = ab
+    assert gpu.spmma_fused_form(m, n, k, batch=batch, beta=beta) == "thin", f"{shape} reaches another form"
     rng = np.random.default_rng(m + 5 * n + 7 * k + batch + 3 * bf)
     kind = "ties" if k == 25 else "uniform"
     if bf:
@@ -2166,21 +2178,38 @@ def test_transpose_bit_exact_with_leading_dimensions(gpu, es, npdt):
 # ---------------------------------------------------------------------------------------------
 # (f-1) fused prune -> compress -> matmul
 # ---------------------------------------------------------------------------------------------
+# the form every row of test_fused_equals_staged runs on an MI355X (256 CUs), shared and per-batch B alike; pinned without a GPU by
+# tests/test_fused_form_abi.py
+FUSED_ROW_FORMS = {(128, 64, 64, 1): "direct64", (196, 512, 256, 2): "astat", (784, 256, 1024, 2): "widep", (130, 72, 192, 1): "direct128",
+                   (96, 64, 128, 3): "direct64", (12544, 64, 576, 2): "direct64", (3136, 128, 1152, 1): "direct128_nt", (300, 136, 320, 2): "widep",
+                   (300, 520, 128, 2): "astat", (784, 1024, 256, 1): "astat", (130, 2048, 512, 1): "astat", (4000, 264, 64, 1): "astat",
+                   (260, 520, 576, 1): "widep", (3136, 256, 192, 12): "big", (2200, 264, 320, 16): "astat", (3000, 256, 128, 11): "big",
+                   (260, 520, 1088, 1): "wide", (3190, 256, 192, 24): "widep", (4785, 200, 320, 16): "widep", (3000, 256, 128, 26): "widep"}
+
+
 @pytest.mark.parametrize("shape", [(128, 64, 64, 1), (196, 512, 256, 2), (784, 256, 1024, 2), (130, 72, 192, 1), (96, 64, 128, 3),
                                    (12544, 64, 576, 2), (3136, 128, 1152, 1), (300, 136, 320, 2),
                                    # A-stationary kernel (n > 256, k <= 512): column tails, row tails, single stage, 8 stages
                                    (300, 520, 128, 2), (784, 1024, 256, 1), (130, 2048, 512, 1), (4000, 264, 64, 1),
-                                   # wide kernel beyond its one-tile range (n > 256, k > 512)
+                                   # persistent wide kernel with several column tiles (n > 256, 512 < k <= 1024)
                                    (260, 520, 576, 1),
-                                   # persistent wide kernel with more tiles than CUs (a workgroup walks 2-3 tiles): an odd
-                                   # stage count (the A image's buffer parity flips between tiles), ragged rows / columns
-                                   (3136, 256, 192, 12), (2200, 264, 320, 16), (3000, 256, 128, 11)])
+                                   # many-tile launches of the big form (its rounds fill the chip as well as the 128-row kernels') and of
+                                   # the A-stationary kernel: odd stage counts, ragged rows / columns
+                                   (3136, 256, 192, 12), (2200, 264, 320, 16), (3000, 256, 128, 11),
+                                   # wide kernel beyond its one-tile range (n > 256, k > 1024)
+                                   (260, 520, 1088, 1),
+                                   # persistent wide kernel with more tiles than CUs (599-624 tiles of 128 rows against 300-312 of 256: a
+                                   # workgroup walks 2-3 tiles): an odd stage count (the A image's buffer parity flips between tiles),
+                                   # ragged rows / columns
+                                   (3190, 256, 192, 24), (4785, 200, 320, 16), (3000, 256, 128, 26)])
 @pytest.mark.parametrize("shared_b", [True, False])
 def test_fused_equals_staged(gpu, orc, shape, shared_b):
     """sm_spmma_fused_f16(A) must be BIT-identical to sm_spmma_f16(sm_compress24_f16(A)): same kept values,
-    same position codes, same instruction sequence; and (tolerance) match the oracle."""
+    same position codes, same instruction sequence; and (tolerance) match the oracle.  The form each row is there for is asserted
+    through sm_spmma_fused_form on this device (FUSED_ROW_FORMS)."""
     import torch
     m, n, k, batch = shape
+    assert gpu.spmma_fused_form(m, n, k, batch=batch, strideB=0 if shared_b else k * n) == FUSED_ROW_FORMS[shape], f"{shape} reaches another form on this device"
     rng = np.random.default_rng(m * 3 + n + k * 5)
     A = rand(rng, batch * m * k, np.float16, "ties" if m % 7 == 0 else "uniform")
     nb = 1 if shared_b else batch
@@ -2223,6 +2252,7 @@ def test_fused_big_form_equals_staged(gpu, shape, bf):
         dB = torch.empty(nb * k * n, dtype=tdt, device="cuda")
         gpu.fill_uniform(dB, 0xB17 + k, -1.0, 1.0)
         strideB = 0 if shared_b else k * n
+        assert gpu.spmma_fused_form(m, n, k, batch=batch, strideB=strideB, beta=beta) == "big", f"{shape} (shared_b={shared_b}, beta={beta}) reaches another form"
         C0 = torch.empty(batch * m * n, dtype=tdt, device="cuda")
         gpu.fill_uniform(C0, 0xC17, -1.0, 1.0)
         C1, C2 = C0.clone(), C0.clone()
@@ -2237,6 +2267,7 @@ def test_fused_big_form_equals_staged(gpu, shape, bf):
     for i, B_ in enumerate(Bs):
         gpu.fill_uniform(B_, 0xB30 + i, -1.0, 1.0)
     Cs = [torch.full((batch * m * n,), float("nan"), dtype=tdt, device="cuda") for _ in range(3)]
+    assert gpu.spmma_fused_form(m, n, k, batch=batch, count=3) == "big"
     gpu.spmma_fused_grouped(As, Bs, Cs, m, n, k, batch=batch)
     Cref = torch.empty(batch * m * n, dtype=tdt, device="cuda")
     for i in range(3):
@@ -2397,6 +2428,7 @@ def test_fused_astat_many_panels_equals_staged(gpu, shape):
     oracle, test_spmma_f16_vs_oracle; at these sizes the CPU product would take minutes.)"""
     import torch
     m, n, k, batch = shape
+    assert gpu.spmma_fused_form(m, n, k, batch=batch) == "astat" and gpu.spmma_fused_form(m, n, k, batch=batch, count=2) == "astat", f"{shape} reaches another form"
     dA = torch.empty(batch * m * k, dtype=torch.float16, device="cuda")
     gpu.fill_uniform(dA, 1234 + m, -1.0, 1.0)
     dB = torch.empty(k * n, dtype=torch.float16, device="cuda")
@@ -2448,6 +2480,8 @@ def test_fused_span_form_equals_staged(gpu, orc, shape, bf):
     C1 = torch.zeros(batch * m * n, dtype=tdt, device="cuda")
     gpu.spmma(blob, dB, C1, m, n, k, batch, 0)
     C2 = torch.full((batch * m * n,), 7.0, dtype=tdt, device="cuda")
+    for cnt in (1, 3):
+        assert gpu.spmma_fused_form(m, n, k, batch=batch, count=cnt) == ("not_taken" if (batch * m * k) % 8 else "span"), f"{shape} reaches another form"
     if (batch * m * k) % 8:   # the operand does not end on a 16-byte boundary: the span form declines (its last DMA piece
         with pytest.raises(gpu.SparsifymeError, match="status 2"):   # would read past the buffer); callers take the staged pair
             gpu.spmma_fused(dA, dB, C2, m, n, k, batch=batch)
