@@ -244,6 +244,8 @@ def test_gemm_i8_vs_spmma_i8_on_the_pruned_matrix(gpu, shape):
 # ---------------------------------------------------------------------------------------------
 # (m, n, k, batch, lda, strideA, shared B): ragged m and n, n < 16, k = 64 (one plane), lda > k, a gap between the A
 # matrices, the folded tall-matrix case (shared B, contiguous A and C)
+# (the padding here is ordinary finite data and C is exactly sized; tests/test_gpu_strided8.py runs the same entry points with
+# NaN padding, sentinel-guarded C, strideB / strideC gaps and offset bases)
 CASES = [(64, 64, 128, 1, 128, None, True), (130, 72, 192, 3, 192, None, True), (130, 72, 192, 3, 192, None, False),
          (33, 9, 64, 2, 64, None, True), (7, 5, 320, 1, 336, None, True), (100, 130, 256, 2, 272, None, True),
          (100, 130, 256, 2, 272, 100 * 272 + 64, True), (61, 200, 128, 4, 160, 61 * 160 + 32, False), (1, 1, 64, 1, 64, None, True),
