@@ -394,7 +394,10 @@ int sm_gemm_rowmajor_f32_split(const float* A, const float* B, float* C, size_t 
  *      A_ptrs/B_ptrs/C_ptrs are device arrays of `batch` device pointers (examples/gemm.cu:65-90).
  *      ta / tb (gemm.hxx:33-34): SM_OP_N or SM_OP_T; a transposed operand is read as its stored k x m
  *      (n x k) form through the same leading dimension, which must cover a stored column (m >= k for
- *      ta = T, k >= n for tb = T; SM_STATUS_INVALID_VALUE otherwise, as the vendor BLAS). */
+ *      ta = T, k >= n for tb = T; SM_STATUS_INVALID_VALUE otherwise, as the vendor BLAS).
+ *      Precondition of the f32 / f64 forms: every pointer in the arrays is 16-byte aligned (f64: 8-byte; what hipMalloc returns
+ *      is).  The arrays live on the device, so the library cannot look at the bases before it picks the 16-byte-chunk pipeline,
+ *      and nothing checks them. */
 int sm_gemm_batched_f16(const void* const* A_ptrs, const void* const* B_ptrs, void* const* C_ptrs,
                         size_t m, size_t n, size_t k, size_t batch, int ta, int tb, float alpha,
                         float beta, sm_stream_t stream);

@@ -995,6 +995,12 @@ def test_spmma_fused_f32(gpu, orc, shape, ab):
 SPLIT_TOL = {3: 2.0 ** -21, 2: 2.0 ** -13}  # sm_spmma_fused_f32_split: |error| <= SPLIT_TOL * sum |a||b| on top of the fp32 accumulation bound
 
 
+def split_bound(planes, k, scale, ref):
+    """The bound of both split forms against the fp64 product: the dropped piece products (SPLIT_TOL) and 2 k fp32 accumulation steps, each
+    relative to scale = sum |a||b| (+ |beta||C0|), and one rounding of the result."""
+    return (SPLIT_TOL[planes] + 2.0 * k * 2.0 ** -24) * scale + 2.0 ** -22 * np.abs(ref) + 1e-30
+
+
 @pytest.mark.parametrize("shape", [(128, 64, 64, 1), (196, 128, 256, 2), (132, 72, 192, 3), (260, 256, 128, 2), (132, 200, 192, 3), (100, 512, 320, 1),
                                    (3136, 128, 576, 2), (784, 256, 1152, 2), (12544, 64, 576, 1), (300, 64, 147, 2), (130, 72, 100, 1), (128, 64, 72, 1),
                                    (3136, 64, 147, 4)], ids=lambda s_: "x".join(map(str, s_)))
@@ -1044,7 +1050,7 @@ def test_spmma_f32_split(gpu, orc, shape, planes, ab, kind):
     assert not (np.abs(host(Cs).astype(np.float64) - Co.astype(np.float64)) > FP32_TOL * np.maximum(sc_, 1e-30)).any(), "split form vs orc.spmma outside 1e-3"
     scale = abs(alpha) * (np.abs(P64) @ np.abs(B64)).reshape(-1) + abs(beta) * np.abs(C0.astype(np.float64))
     err = np.abs(host(Cs).astype(np.float64) - ref)
-    bound = (SPLIT_TOL[planes] + 2.0 * k * 2.0 ** -24) * scale + 2.0 ** -22 * np.abs(ref) + 1e-30
+    bound = split_bound(planes, k, scale, ref)
     ratio = float((err / bound).max())
     assert ratio <= 1.0, f"split planes={planes} {shape}: max err / bound = {ratio:.3f} (max err {err.max():.3e})"
     assert not (err > FP32_TOL * np.maximum(scale, 1e-30)).any()
@@ -1079,7 +1085,7 @@ def test_gemm_f32_split_dense(gpu, orc, shape, planes, kind):
     A64, B64 = A.astype(np.float64).reshape(batch * m, k), B.astype(np.float64).reshape(k, n)
     ref, scale = (A64 @ B64).reshape(-1), (np.abs(A64) @ np.abs(B64)).reshape(-1)
     err = np.abs(host(Cs).astype(np.float64) - ref)
-    bound = (SPLIT_TOL[planes] + 2.0 * k * 2.0 ** -24) * scale + 2.0 ** -22 * np.abs(ref) + 1e-30
+    bound = split_bound(planes, k, scale, ref)
     assert float((err / bound).max()) <= 1.0, f"dense split planes={planes} {shape}: max err {err.max():.3e}"
 
 
@@ -1111,7 +1117,7 @@ def test_f32_split_per_batch_b_and_alpha_beta(gpu, dense, planes):
     ref = alpha * np.einsum("bmk,bkn->bmn", P64, B64).reshape(-1) + beta * C0.astype(np.float64)
     scale = abs(alpha) * np.einsum("bmk,bkn->bmn", np.abs(P64), np.abs(B64)).reshape(-1) + abs(beta) * np.abs(C0.astype(np.float64))
     err = np.abs(host(C).astype(np.float64) - ref)
-    bound = (SPLIT_TOL[planes] + 2.0 * k * 2.0 ** -24) * scale + 2.0 ** -22 * np.abs(ref) + 1e-30
+    bound = split_bound(planes, k, scale, ref)
     assert float((err / bound).max()) <= 1.0
 
 
