@@ -446,6 +446,12 @@ int sm_spmm_bell_batched_workspace_size(size_t rows, size_t cols, size_t batch, 
 int sm_spmm_bell_batched_f32(const float* const* values, const uint64_t* const* column_indices, size_t rows,
                              size_t cols, size_t block_size, size_t ell_cols, const float* B, float* const* C,
                              size_t n, size_t batch, float alpha, float beta, void* workspace, sm_stream_t stream);
+/* Layout and meaning of the fp32 forms are those stated for the 16-bit forms below (any block_size >= 1, ragged rows and cols, an id >=
+ * cols / block_size marks an empty block, whose values are not read).
+ * Status: sm_spmm_bell_f32, sm_spmm_bell_f32_ws and sm_spmm_bell_batched_f32 return SM_STATUS_INVALID_VALUE for a null pointer
+ * (sm_spmm_bell_batched_f32: a null workspace included), block_size == 0 or ell_cols % block_size != 0; then SM_STATUS_SUCCESS without work
+ * when rows, n or batch is 0; then SM_STATUS_NOT_SUPPORTED for n > 8 * 65535 on sm_spmm_bell_f32 (the grid of its gather kernel), for
+ * rows, cols or n beyond 2^31-1 on the two workspace forms and for batch > 65535 -- all decided before any HIP call. */
 
 /* Blocked-ELL on the 16-bit matrix cores (fp16 / bfloat16 values, B and C; fp32 accumulation, one rounding of the result):
  * the operand types the reference's descriptors declare (CUDA_R_16F, spmm.hxx:57-67,107-110).  Same layout and meaning as
@@ -481,7 +487,12 @@ int sm_spmm_bell_batched_bf16(const void* const* values, const uint64_t* const* 
 /* COO with a caller-provided workspace of sm_spmm_coo_workspace_size() bytes (the reference allocates its
  * cuSPARSE buffer inside the call, spmm.hxx:183): row-sorted input runs as CSR, row-parallel, without
  * atomics (bitwise reproducible); unsorted input falls back to the atomic kernel.  workspace == NULL
- * behaves as sm_spmm_coo_f32. */
+ * behaves as sm_spmm_coo_f32.
+ * Status of the exact COO forms (sm_spmm_coo_f32, _ws, _packed): SM_STATUS_INVALID_VALUE for a null B or C, and for null rows, cols or vals
+ * when A_nnz > 0; then SM_STATUS_SUCCESS without work when A_num_rows, B_num_cols or num_batches is 0; then SM_STATUS_NOT_SUPPORTED when
+ * B_num_cols * num_batches > 65535 on sm_spmm_coo_f32 (also where another form is called without a workspace it can use), and on
+ * sm_spmm_coo_f32_ws when A_nnz exceeds 2^31-1, num_batches exceeds 65535 or B_num_cols exceeds 16 * 65535 -- all decided before any HIP
+ * call.  An entry whose row or column is out of range is skipped, never an error. */
 int sm_spmm_coo_workspace_size(size_t A_num_rows, size_t* bytes /*host*/);
 int sm_spmm_coo_f32_ws(size_t A_num_rows, size_t A_num_cols, size_t A_nnz, size_t B_num_cols,
                        size_t num_batches, const int* rows, const int* cols, const float* vals,
