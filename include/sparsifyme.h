@@ -291,7 +291,8 @@ int sm_spmma_fused_bf16_grouped_ws(size_t count, const void* const* A, const voi
  *      the span form additionally needs a 16-byte aligned R with strideR == m * n when it is read.  The THIN form (n < 8) with a
  *      non-trivial epilogue: SM_STATUS_NOT_SUPPORTED.
  *      Not covered yet (they share the routine and can follow): the grouped and _ws (stream-K) forms, sm_prune24_spmma_*,
- *      sm_conv_spmma_*, fp32, int8 and fp8. */
+ *      sm_conv_spmma_*, fp32, int8 and the fp8 matmuls (sm_spmma_fp8, sm_spmma_fused_fp8; the token-major fp8 layer
+ *      sm_linear24_fp8 takes the struct). */
 #define SM_BIAS_COL 0
 #define SM_BIAS_ROW 1
 #define SM_ACT_NONE 0
@@ -346,11 +347,66 @@ int sm_spmma_fused_bf16_ex(const void* A, const void* B, void* D, size_t m, size
  *      and out_features >= 1 is taken: Y (and R, when read) 8-byte aligned with out_features % 4 == 0 and ldy % 4 == 0 use 8-byte
  *      stores, everything else per-element stores.
  *      Enqueue only: no allocation, no synchronisation, no workspace, no memset node; capturable into a hipGraph.
- *      Not covered: fp8 / int8 token-major output, a batch dimension, in_features % 64 != 0. */
+ *      Not covered: int8 token-major output (fp8: sm_linear24_fp8 below), a batch dimension, in_features % 64 != 0. */
 int sm_linear24_f16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
                     size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
 int sm_linear24_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
                      size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+
+/* ---- The same layer on fp8 operands (W8A8, extension): the fp8 2:4 blob times fp8 tokens, token-major in and out, one launch.
+ *
+ *          Y[t][o] = round_to_out( act( s(o,t) * acc(o,t) + beta * R[t][o] + bias ) )
+ *          acc(o,t) = sum_i W_2:4[o][i] * X[t][i]         fp32, v_smfmac_f32_16x16x128_<W>_<X>
+ *          s(o,t)   = (alpha * w_scale[o]) * x_scale[t]   two fp32 multiplies in this order; a NULL scale is skipped
+ *
+ *      blob     exactly what sm_compress24_fp8(W, m = out_features, k = in_features, .., batch = 1) or
+ *               sm_quantize_compress24_fp8_* writes (sm_compress24_size(out_features, in_features, 1, 1) bytes); fmt_w: its SM_FP8_*.
+ *      X        fp8 (fmt_x), row-major tokens x in_features, leading dimension ldx >= in_features (bytes = elements); rows 16-byte
+ *               aligned.  What sm_quantize_rows_fp8_* writes, as it is: no transpose.
+ *      Y        row-major tokens x out_features, leading dimension ldy >= out_features (elements), of out_type SM_OUT_F32 / SM_OUT_F16 /
+ *               SM_OUT_BF16.  Columns at or beyond out_features are not touched.
+ *      w_scale  out_features floats (device) or NULL: the row_scale sm_quantize_compress24_fp8_* wrote for W.
+ *      x_scale  tokens floats (device) or NULL: the row_scale sm_quantize_rows_fp8_* wrote for X.
+ *      s * acc + beta * R is evaluated as sm_spmma_fp8 evaluates (alpha * row_scale[i]) * acc + beta * C; the bias is an addition of its
+ *      own after it, then the activation, then ONE rounding to the output type.
+ *      epilogue the sm_epilogue_t above, NULL = none, read in Y's coordinates as sm_linear24_{f16,bf16} read it: SM_BIAS_COL = one fp32
+ *               per out feature, SM_BIAS_ROW = one per token; R has Y's shape, type and ldy, R == Y is allowed (in place); strideR is
+ *               ignored.  With a NULL struct beta != 0 reads Y.  The validity rules and the error text are those of sm_spmma_*_ex,
+ *               checked before everything else.
+ *      Forms    sm_linear24_fp8_form below is the rule the entry point itself switches on.  The tile forms walk K in the order of
+ *               sm_spmma_fp8, one matrix instruction per 128 k, and with x_scale == NULL and no epilogue struct are bit-identical to
+ *               sm_spmma_fp8(blob, X, C, m = out_features, n = tokens, k = in_features, .., row_scale = w_scale) + sm_transpose(C).
+ *               The decode form (few tokens: a pure weight stream; the waves of a workgroup split K and add their fp32 partial tiles
+ *               in a fixed order) agrees within the arithmetic's bound, not bit for bit.  Every form gives the same bits on every run.
+ *      Status, decided before any device work, in this order: invalid epilogue: SM_STATUS_INVALID_VALUE; null blob / X / Y, blob not
+ *      16-byte aligned, fmt_w / fmt_x not SM_FP8_*, out_type not SM_OUT_*, ldx < in_features, ldy < out_features:
+ *      SM_STATUS_INVALID_VALUE; a dimension >= 2^31, a tile
+ *      grid beyond 2^31 - 1 workgroups, in_features % 64 != 0, X rows not 16-byte aligned (pointer, ldx % 16):
+ *      SM_STATUS_NOT_SUPPORTED; tokens == 0 or out_features == 0: success, nothing enqueued.  Every tokens >= 1 and out_features >= 1
+ *      is taken, odd out_features included: Y (and R, when read) aligned to four elements with out_features % 4 == 0 and ldy % 4 == 0
+ *      use four-element stores, everything else per-element stores.
+ *      Enqueue only: no allocation, no synchronisation, no workspace, no memset node; capturable into a hipGraph.
+ *      Not covered: int8, quantising X inside the layer, a batch dimension, in_features % 64 != 0, split-K across workgroups. */
+int sm_linear24_fp8(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
+                    size_t ldy, int fmt_w, int fmt_x, int out_type, float alpha, float beta, const float* w_scale, const float* x_scale,
+                    const sm_epilogue_t* epilogue, sm_stream_t stream);
+/* The form sm_linear24_fp8 runs for a shape -- the host-side statement of its dispatch rule, the one function the entry point
+ * switches on.  cus: the compute units the tile rule is sized for; 0 = the current device's (256 when no device is visible); with
+ * cus != 0 the call does no device work at all.
+ *   NOT_TAKEN   a shape the entry point answers SM_STATUS_NOT_SUPPORTED to (in_features % 64 != 0, a dimension >= 2^31,
+ *               a tile grid beyond 2^31 - 1 workgroups)
+ *   EMPTY       tokens == 0 or out_features == 0: nothing is enqueued
+ *   DECODE      tokens <= 16 and out_features <= 16384
+ *   TILE128 / TILE128x64 / TILE64   out features x tokens per workgroup: the largest tile whose grid still has >= cus workgroups
+ *               (128 x 128 needs tokens > 64 as well); 64 x 64 when neither larger tile does.
+ * *form receives SM_LINEAR24_FORM_*; SM_STATUS_INVALID_VALUE when form is NULL. */
+#define SM_LINEAR24_FORM_NOT_TAKEN 0
+#define SM_LINEAR24_FORM_EMPTY 1
+#define SM_LINEAR24_FORM_DECODE 2
+#define SM_LINEAR24_FORM_TILE64 3
+#define SM_LINEAR24_FORM_TILE128x64 4
+#define SM_LINEAR24_FORM_TILE128 5
+int sm_linear24_fp8_form(size_t tokens, size_t out_features, size_t in_features, size_t cus, int* form);
 
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +

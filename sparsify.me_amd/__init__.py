@@ -162,6 +162,9 @@ for _sfx16 in ("f16", "bf16"):
 # the token-major 2:4 weight-sparse linear layer (linear24_f16.hip)
 for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_linear24_" + _sfx16] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_f, _c_f, _c_ptr, _c_ptr]
+# ... and its fp8 form (linear24_fp8.hip) with the host-side query of its dispatch rule
+_SIGS["sm_linear24_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_i, _c_i, _c_i, _c_f, _c_f, _c_ptr, _c_ptr, _c_ptr, _c_ptr]
+_SIGS["sm_linear24_fp8_form"] = [_c_size] * 4 + [ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -422,6 +425,38 @@ def linear24(blob, X, Y, tokens, out_features, in_features, ldx=None, ldy=None, 
     fn = getattr(lib(), "sm_linear24_" + _sfx(X))
     _check(fn(_dev(blob), _dev(X), _dev(Y), tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta),
               ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24")
+
+
+# include/sparsifyme.h: SM_LINEAR24_FORM_* (index = value)
+LINEAR24_FORMS = ("not_taken", "empty", "decode", "tile64", "tile128x64", "tile128")
+
+
+def linear24_fp8(blob, X, Y, tokens, out_features, in_features, w_dtype=None, ldx=None, ldy=None, alpha=1.0, beta=0.0, w_scale=None,
+                 x_scale=None, epilogue=None):
+    """Y[tokens][out] = act((alpha * w_scale[o]) * x_scale[t] * (X[tokens][in] . W^T) + beta * R + bias) with W[out][in] the fp8 2:4 blob
+    of compress24_fp8 / quantize_compress24_fp8 and X fp8 tokens (sm_linear24_fp8): token-major in and out, one launch.  The formats
+    come from the dtypes (w_dtype: W's fp8 dtype, the blob does not carry it; None = X's), the output type from Y's (float32 / float16 /
+    bfloat16).  w_scale / x_scale: float32 device vectors or None.  epilogue: an Epilogue read in Y's coordinates, as linear24 reads it."""
+    fx = fp8_format(X.dtype)
+    fw = fx if w_dtype is None else fp8_format(w_dtype)
+    ot = _fp8_out_type(Y)
+    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
+        if v is not None and v.dtype != _t().float32:
+            raise SparsifymeError(f"linear24_fp8: {name} is float32, not {v.dtype}")
+    ldx = in_features if ldx is None else ldx
+    ldy = out_features if ldy is None else ldy
+    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
+    _check(lib().sm_linear24_fp8(_dev(blob), _dev(X), _dev(Y), tokens, out_features, in_features, ldx, ldy, fw, fx, ot, float(alpha), float(beta),
+                                 _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None,
+                                 ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24_fp8")
+
+
+def linear24_fp8_form(tokens, out_features, in_features, cus=0):
+    """The name (LINEAR24_FORMS) of the form linear24_fp8 runs for this shape -- sm_linear24_fp8_form, the rule the entry point itself
+    switches on.  cus=0: this device's compute units; another value: host-only."""
+    form = _c_i(-1)
+    _check(lib().sm_linear24_fp8_form(tokens, out_features, in_features, cus, ctypes.byref(form)), "sm_linear24_fp8_form")
+    return LINEAR24_FORMS[form.value]
 
 
 def spmma_fused_i8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, accumulate=False, scale=None):
