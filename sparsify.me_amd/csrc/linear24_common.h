@@ -1,0 +1,210 @@
+// linear24_common.h -- the core of the token-major 2:4 linear layer, shared by its two operand front ends: linear24_f16.hip
+// (sm_linear24_{f16,bf16}, 64 dense k per stage) and linear24_fp8.hip (sm_linear24_fp8, 128).  The front ends keep what depends on
+// the operand type -- the stage layout, the K loops, the matrix instruction; everything else is here, once: the dispatch rule, the
+// argument checks, the X-image swizzle, the fragment epilogue and store, the decode form's combine, the tile launcher.
+#pragma once
+#include "spmma_args.h"
+
+namespace sm {
+
+// the largest `tokens` the decode form takes (the table it is read from) ...
+constexpr size_t LINEAR24_DECODE_MAX = 16;
+// ... and the largest `out`: above it (more than 4 sixteen-row workgroups per CU) the 64 x 64 tile form is the faster weight stream
+// at every token count (profiles/linear_table.txt: out = 22016 and 28672 against out <= 12288)
+constexpr size_t LINEAR24_DECODE_MAX_OUT = 16384;
+
+// The dispatch rule, stated once: both layers switch on it, sm_linear24_fp8_form exports it.  Tiles: the largest of 128 x 128,
+// 128 x 64 and 64 x 64 that still gives each of `cus` compute units a workgroup (fewer, larger tiles re-read X and the blob less).
+inline int linear24_form(size_t tokens, size_t out, size_t in, size_t cus) {
+  if (in % 64 != 0 || tokens > 0x7fffffffull || out > 0x7fffffffull || in > 0x7fffffffull) return SM_LINEAR24_FORM_NOT_TAKEN;
+  if (tokens == 0 || out == 0) return SM_LINEAR24_FORM_EMPTY;
+  if (tokens <= LINEAR24_DECODE_MAX && out <= LINEAR24_DECODE_MAX_OUT) return SM_LINEAR24_FORM_DECODE;
+  const size_t t128 = ceil_div(out, 128) * ceil_div(tokens, 128), t64 = ceil_div(out, 128) * ceil_div(tokens, 64);
+  if (tokens > 64 && t128 >= cus) return t128 > 0x7fffffffull ? SM_LINEAR24_FORM_NOT_TAKEN : SM_LINEAR24_FORM_TILE128;  // (the grid limit)
+  if (t64 >= cus) return t64 > 0x7fffffffull ? SM_LINEAR24_FORM_NOT_TAKEN : SM_LINEAR24_FORM_TILE128x64;
+  return ceil_div(out, 64) * ceil_div(tokens, 64) > 0x7fffffffull ? SM_LINEAR24_FORM_NOT_TAKEN : SM_LINEAR24_FORM_TILE64;
+}
+
+// What the shared pieces read of a launch; each front end's argument block adds its X and its K extent.
+struct Linear24Core {
+  const char* vals;  // the blob's values, plane-major
+  const char* meta;  // the blob's metadata, plane-major [in/64][out][8 B]
+  void* Y;
+  const float* w_scale;  // per out feature, or null (the 16-bit layer has no scales: both null, never read)
+  const float* x_scale;  // per token, or null
+  size_t ldx, ldy;   // elements
+  float alpha, beta;  // (in front of the ints: the compiler reads alpha's splat as one 16-byte load, which must not reach a pointer)
+  int out, tokens;
+  int tiles_m, tiles_n;
+  int packed;        // Y (and R, when read) take four-element pieces: aligned to four elements, out % 4 == 0, ldy % 4 == 0
+  EpiArgs e;         // bias_dim in Y's coordinates (SM_BIAS_COL: per out feature); R has Y's shape, type and ldy (R = Y when none was given)
+};
+
+// The entry points' argument checks, in their order and with their statuses, and the fields of Linear24Core they settle.  `who`
+// names the entry point in every message; extra_ok / extra: checks of the entry point's own that belong to the first test, and
+// their words in its message.  x_elt: bytes of an element of X (the blob's element too); piece: bytes of four elements of Y.
+// *run = false with SM_STATUS_SUCCESS: an empty problem, nothing to launch.
+inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool extra_ok, const char* extra, const void* blob, const void* X, void* Y,
+                              size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, float alpha, float beta,
+                              const sm_epilogue_t* ep) {
+  *run = false;
+  bool plain;  // (not used: a plain epilogue takes the same kernels, whose bias / activation steps are skipped at run time)
+  if (const int rc = epilogue_args(ep, Y, 0, out, beta, a.e, &plain, who)) return rc;
+  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < out) {
+    set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < out_features)", who, extra);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  if (tokens > 0x7fffffffull || out > 0x7fffffffull || in > 0x7fffffffull) {
+    set_error("%s: dimension exceeds 2^31-1", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  if (in % 64 != 0 || !aligned16(X) || ldx % (16 / x_elt) != 0) {
+    set_error("%s: in_features %% 64 == 0 and 16-byte aligned rows of X (pointer, ldx %% %d) are required", who, (int)(16 / x_elt));
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  if (tokens == 0 || out == 0) return SM_STATUS_SUCCESS;
+  a.vals = (const char*)blob;
+  a.meta = (const char*)blob + blob_layout(out, in, x_elt, 1).meta_off;
+  a.Y = Y;
+  a.ldx = ldx; a.ldy = ldy;
+  a.out = (int)out; a.tokens = (int)tokens;
+  a.alpha = alpha; a.beta = beta;
+  const bool r_ok = beta == 0.0f || (reinterpret_cast<uintptr_t>(a.e.R) & (piece - 1)) == 0;
+  a.packed = (out % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (piece - 1)) == 0 && r_ok) ? 1 : 0;
+  *run = true;
+  return SM_STATUS_SUCCESS;
+}
+
+// The tile form's launcher, one per kernel: the tile counts, the 2^31 - 1 grid limit, the opt-in to more than 64 KiB of dynamic LDS
+// (held per instantiation), the launch.  NT threads per workgroup, LDS bytes of the whole ring.
+template <class Args, void (*KERNEL)(Args), int BM, int BN, int NT, size_t LDS>
+static int launch_linear24_tile(const Args& a0, hipStream_t st, const char* who, const char* kernel_name) {
+  Args a = a0;
+  a.tiles_m = (a.out + BM - 1) / BM;
+  a.tiles_n = (a.tokens + BN - 1) / BN;
+  const size_t nwg = (size_t)a.tiles_m * a.tiles_n;
+  if (nwg > 0x7fffffffu) {
+    set_error("%s: grid too large", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  static LdsOptIn lds_optin;
+  if (LDS > 64 * 1024) {
+    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(KERNEL), LDS, kernel_name)) return rc;
+  }
+  KERNEL<<<dim3((unsigned)nwg), dim3(NT), LDS, st>>>(a);
+  return check_launch(kernel_name);
+}
+
+// ... and the decode form's: one workgroup of NT threads per 16 out features
+template <class Args, void (*KERNEL)(Args), int NT>
+static int launch_linear24_decode(const Args& a, hipStream_t st, const char* kernel_name) {
+  KERNEL<<<dim3((unsigned)ceil_div((size_t)a.out, 16)), dim3(NT), 0, st>>>(a);
+  return check_launch(kernel_name);
+}
+
+// The X image of a stage: [tokens][128 B], 16-byte chunk c of token row t at slot c ^ ((t >> 1) & 7).  A ds_read_b128 access group is
+// 16 lanes of which 8 read chunk c of rows {0-3, 12-15} (+16i) and 8 read chunk c ^ 1 of rows {4-11}: with the row's parity choosing the
+// half of the 256-byte bank line and (t >> 1) the slot, the 16 lanes cover 16 different 16-byte slots -- all 64 banks once
+// (4.14 for the same reads over bytes).
+__device__ __forceinline__ unsigned x_swz(unsigned t) { return (t >> 1) & 7u; }
+
+// the lane's four per-out-feature values of a vector (bias, w_scale); indices past the edge are clamped, not branched round (their
+// outputs are never stored), so that the loads stay in flight under the K loop
+__device__ __forceinline__ f4 linear24_per_out(const float* v, unsigned o0, unsigned out) {
+  f4 b;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) b[q] = v[o0 + q < out ? o0 + q : out - 1];
+  return b;
+}
+
+// The 16-bit element of Y and R as the store sees it (the fp8 layer's three output types: OutElt<OT>, linear24_fp8.hip): the type,
+// the raw piece that moves four of them at once, the conversions.
+template <bool BF>
+struct Elt16 {
+  typedef half_t T;
+  typedef u2 raw_t;
+  static __device__ __forceinline__ float load(const half_t* p) { return to_f32<BF>(*p); }
+  static __device__ __forceinline__ half_t conv(float v) { return to_elt<BF>(v); }
+};
+
+// One fragment's epilogue and store: the lane holds out features o0 .. o0+3 of token t.  s * acc + beta * R evaluated as
+// store_c_tile_epi / store_c_f8 evaluate it (beta * R added only when beta != 0), the bias as an addition of its own, the activation,
+// one rounding.  s = alpha, or with SCALED (sw[q] = alpha * w_scale[o0 + q], alpha when there is none) s = sw[q] * x_scale[t].
+// R == Y is in place: the lane reads its piece before it writes it, and no other lane touches it.  Indices are unsigned: an edge
+// tile's origin plus its extent may pass 2^31 - 1 (never 2^32).
+template <class E, bool SCALED>
+__device__ __forceinline__ void linear24_store_frag(const Linear24Core& p, const f4 acc, unsigned o0, unsigned t, f4 sw, float xs, float bt, f4 bo) {
+  typedef typename E::T T;
+  typedef typename E::raw_t raw_t;
+  struct Piece { T v[4]; };
+  const unsigned out = (unsigned)p.out;
+  if (t >= (unsigned)p.tokens || o0 >= out) return;
+  const bool use_r = p.beta != 0.0f;
+  T* dst = reinterpret_cast<T*>(p.Y) + (size_t)t * p.ldy + o0;
+  const T* rs = reinterpret_cast<const T*>(p.e.R) + (size_t)t * p.ldy + o0;
+  const bool bias = p.e.bias != nullptr, bias_tok = bias && p.e.bias_dim == SM_BIAS_ROW, bias_out = bias && p.e.bias_dim == SM_BIAS_COL;
+  auto scale = [&](int q) {
+    if constexpr (SCALED) return p.x_scale ? sw[q] * xs : sw[q];
+    else return p.alpha;
+  };
+  f4 v4;
+  if (p.packed) {
+    raw_t rraw = {};
+    if (use_r) rraw = *reinterpret_cast<const raw_t*>(rs);
+    const Piece rv = __builtin_bit_cast(Piece, rraw);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v = scale(q) * acc[q];
+      if (use_r) v += p.beta * E::load(&rv.v[q]);
+      v4[q] = v;
+    }
+    v4 = epi_act4(epi_bias4(v4, bias_tok, bt, bias_out, bo), p.e.act, p.e.act_arg);
+    Piece o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o.v[q] = E::conv(v4[q]);
+    *reinterpret_cast<raw_t*>(dst) = __builtin_bit_cast(raw_t, o);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v = scale(q) * acc[q];
+      if (use_r && o0 + q < out) v += p.beta * E::load(rs + q);
+      v4[q] = v;
+    }
+    v4 = epi_act4(epi_bias4(v4, bias_tok, bt, bias_out, bo), p.e.act, p.e.act_arg);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (o0 + q < out) dst[q] = E::conv(v4[q]);
+  }
+}
+
+// The decode form's tail: every wave's partial fragments meet in LDS, wave j finishes fragment j -- lane for lane the accumulator
+// map -- adding the partials in wave order 0, 1, .. (the same bits on every run), fetches the lane's bias and scales and hands the
+// sum to STORE (linear24_store_frag, or a switch over its instantiations).  Workgroup = 16 out features from m0 x NWV waves.
+template <class Args, void (*STORE)(const Args&, f4, unsigned, unsigned, f4, float, float, f4), bool SCALED, int FN, int NWV>
+__device__ __forceinline__ void linear24_decode_tail(const Args& p, const f4 (&acc)[FN], unsigned m0) {
+  static_assert(FN * 64 <= 64 * NWV, "one thread per output piece in the combine");
+  __shared__ f4 part[NWV][FN][64];
+  const unsigned tid = threadIdx.x, lane = tid & 63u, g = lane >> 4, r = lane & 15u;
+  const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+  for (int j = 0; j < FN; ++j) part[wave][j][lane] = acc[j];
+  __syncthreads();
+  if (tid >= (unsigned)(FN * 64)) return;
+  const unsigned j = wave;
+  f4 s = part[0][j][lane];
+#pragma unroll
+  for (int w = 1; w < NWV; ++w) s += part[w][j][lane];
+  const unsigned o0 = m0 + 4u * g, t = 16u * j + r;
+  const bool tv = t < (unsigned)p.tokens;
+  f4 bo = {0.f, 0.f, 0.f, 0.f}, sw = {p.alpha, p.alpha, p.alpha, p.alpha};
+  float bt = 0.f, xs = 1.f;
+  if (p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_COL) bo = linear24_per_out(p.e.bias, o0, (unsigned)p.out);
+  if (p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_ROW && tv) bt = p.e.bias[t];
+  if constexpr (SCALED) {
+    if (p.w_scale) sw = p.alpha * linear24_per_out(p.w_scale, o0, (unsigned)p.out);
+    if (p.x_scale && tv) xs = p.x_scale[t];
+  }
+  STORE(p, s, o0, t, sw, xs, bt, bo);
+}
+
+}  // namespace sm

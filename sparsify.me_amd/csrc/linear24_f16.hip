@@ -5,87 +5,26 @@
 // dense k 8g .. 8g+7 and 32+8g .. 32+8g+7 (g = l >> 4) -- two 16-byte pieces of one X row, plain ds_read_b128, no transposing
 // read; and the lane ends with four consecutive out features of one token -- 8 contiguous bytes of Y's row, no LDS transpose.
 //
-// Two forms behind the one entry point (linear24(), below; the rule is compiled in):
+// The operand-independent core (rule, argument checks, epilogue and store, decode combine, tile launcher) is linear24_common.h,
+// shared with linear24_fp8.hip.  Two forms behind the one entry point (linear24_form(); this layer asks it with LINEAR24_F16_CUS):
 //   tile    BM out features x BN tokens per workgroup, 64 dense k per stage (BK = 64, not 128: DESIGN.md 8) brought in by global_load_lds into a ring of NS stage
 //           buffers (counted vmcnt, one barrier per stage: the pipeline of spmma_f16_dma_kernel).  K is walked in order, one SMFMAC
 //           per 64-k step into one accumulator: the bits of sm_transpose o sm_spmma_{f16,bf16}[_ex] o sm_transpose.
 //   decode  tokens <= LINEAR24_DECODE_MAX and out <= LINEAR24_DECODE_MAX_OUT: a pure weight stream.  One workgroup per 16 out features; its waves split K among
 //           themselves, stream the blob straight to registers (no other wave shares it) and add their fp32 partial tiles through
 //           LDS in wave order: deterministic, no workspace.  Other K order than the tile form: held to the arithmetic's bound.
-#include "spmma_args.h"
+#include "linear24_common.h"
 
 namespace sm {
 
-// the largest `tokens` the decode form takes (the table it is read from)
-constexpr size_t LINEAR24_DECODE_MAX = 16;
-// ... and the largest `out`: above it (more than 4 sixteen-row workgroups per CU) the 64 x 64 tile form is the faster weight stream
-// at every token count (profiles/linear_table.txt: out = 22016 and 28672 against out <= 12288)
-constexpr size_t LINEAR24_DECODE_MAX_OUT = 16384;
+// the compute-unit count the rule is asked with: a constant, not the device's, so the dispatch is the same everywhere
+constexpr size_t LINEAR24_F16_CUS = 256;
+static const char* const LINEAR24_F16_WHO = "sm_linear24_{f16,bf16}";
 
-struct Linear24Args {
-  const char* vals;  // stage-major [in/64][out][64 B]
-  const char* meta;  // stage-major [in/64][out][8 B]
+struct Linear24Args : Linear24Core {  // vals stage-major [in/64][out][64 B]
   const half_t* X;
-  half_t* Y;
-  size_t ldx, ldy;   // elements
-  int out, tokens, nkt;  // nkt = in / 64
-  int tiles_m, tiles_n;
-  int packed;        // Y (and R, when read) take 8-byte pieces: 8-byte aligned, out % 4 == 0, ldy % 4 == 0
-  float alpha, beta;
-  EpiArgs e;         // bias_dim in Y's coordinates (SM_BIAS_COL: per out feature); R has Y's shape and ldy (R = Y when none was given)
+  int nkt;  // in / 64
 };
-
-// The X image of a stage: [tokens][128 B], 16-byte chunk c of token row t at slot c ^ ((t >> 1) & 7).  A ds_read_b128 access group is
-// 16 lanes of which 8 read chunk c of rows {0-3, 12-15} (+16i) and 8 read chunk c ^ 1 of rows {4-11}: with the row's parity choosing the
-// half of the 256-byte bank line and (t >> 1) the slot, the 16 lanes cover 16 different 16-byte slots -- all 64 banks once.
-__device__ __forceinline__ unsigned x_swz(unsigned t) { return (t >> 1) & 7u; }
-
-// One fragment's epilogue and store: the lane holds out features o0 .. o0+3 of token t.  alpha * acc + beta * R evaluated as
-// store_c_tile / store_c_tile_epi evaluate it, the bias as an addition of its own, the activation, one rounding.  R == Y is in
-// place: the lane reads its 8 bytes before it writes them, and no other lane touches them.
-template <bool BF>
-__device__ __forceinline__ void linear24_store_frag(const Linear24Args& p, const f4 acc, int o0, int t, bool bias_tok, float bt, bool bias_out, f4 bo) {
-  if (t >= p.tokens || o0 >= p.out) return;
-  const bool use_r = p.beta != 0.0f;
-  half_t* dst = p.Y + (size_t)t * p.ldy + o0;
-  const half_t* rs = p.e.R + (size_t)t * p.ldy + o0;
-  f4 v4;
-  if (p.packed) {
-    h4 rv = {(half_t)0.0f, (half_t)0.0f, (half_t)0.0f, (half_t)0.0f};
-    if (use_r) rv = *reinterpret_cast<const h4*>(rs);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v = p.alpha * acc[q];
-      if (use_r) v += p.beta * to_f32<BF>(rv[q]);
-      v4[q] = v;
-    }
-    v4 = epi_act4(epi_bias4(v4, bias_tok, bt, bias_out, bo), p.e.act, p.e.act_arg);
-    h4 o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) o[q] = to_elt<BF>(v4[q]);
-    *reinterpret_cast<h4*>(dst) = o;
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v = p.alpha * acc[q];
-      if (use_r && o0 + q < p.out) v += p.beta * to_f32<BF>(rs[q]);
-      v4[q] = v;
-    }
-    v4 = epi_act4(epi_bias4(v4, bias_tok, bt, bias_out, bo), p.e.act, p.e.act_arg);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (o0 + q < p.out) dst[q] = to_elt<BF>(v4[q]);
-  }
-}
-
-// the lane's four per-out-feature bias values (SM_BIAS_COL in Y's coordinates); indices past the edge are clamped, not branched
-// round (their outputs are never stored), so that the loads stay in flight under the K loop
-__device__ __forceinline__ f4 linear24_bias_out(const Linear24Args& p, int o0) {
-  f4 b;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) b[q] = p.e.bias[o0 + q < p.out ? o0 + q : p.out - 1];
-  return b;
-}
 
 // One 64-deep stage for one wave: A fragments + index halfwords from the 64-byte-row image (as smfmac_stage reads them), X fragments
 // as two ds_read_b128 per 16 tokens, issued by hand with counted lgkmcnt (fragment j+1's reads in flight under fragment j's SMFMACs;
@@ -157,8 +96,9 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
   const unsigned wm = wave / WN, wn = wave % WN;
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
   const unsigned tile_m = lid / (unsigned)p.tiles_n, tile_n = lid - tile_m * (unsigned)p.tiles_n;
-  const int m0 = (int)tile_m * BM, n0 = (int)tile_n * BN;
-  const int mlast = p.out - 1, tlast = p.tokens - 1;
+  // row and token indices are unsigned: an edge tile's origin plus its extent may pass 2^31 - 1 (never 2^32)
+  const unsigned m0 = tile_m * BM, n0 = tile_n * BN;
+  const unsigned mlast = (unsigned)p.out - 1u, tlast = (unsigned)p.tokens - 1u;
 
   // the lane's bias values, fetched ahead of the K loop (plain loads, older than every DMA piece: the counted waits cover them)
   const bool bias_out = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_COL, bias_tok = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_ROW;
@@ -170,12 +110,12 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
   for (int j = 0; j < FN; ++j) bt[j] = 0.f;
   if (bias_out) {
 #pragma unroll
-    for (int i = 0; i < FM; ++i) bo[i] = linear24_bias_out(p, m0 + (int)(wm * TM + i * 16 + 4u * g));
+    for (int i = 0; i < FM; ++i) bo[i] = linear24_per_out(p.e.bias, m0 + (wm * TM + i * 16 + 4u * g), (unsigned)p.out);
   }
   if (bias_tok) {
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
-      const int t = n0 + (int)(wn * TN + j * 16 + r);
+      const unsigned t = n0 + (wn * TN + j * 16 + r);
       bt[j] = p.e.bias[t < tlast ? t : tlast];
     }
   }
@@ -188,21 +128,21 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
     const unsigned t = wave + (unsigned)NW * i;
     if (t < (unsigned)A_N) {
       const unsigned row = 16u * t + (lane >> 2), cs = (lane & 3u) ^ a64_swz(row);
-      int gr = m0 + (int)row;
+      unsigned gr = m0 + row;
       gr = gr < mlast ? gr : mlast;
       src[i] = p.vals + (size_t)gr * 64 + 16u * cs;
       step[i] = (size_t)p.out * 64;
       loff[i] = t * 1024u;
     } else if (t < (unsigned)(A_N + M_N)) {
       const unsigned u = t - A_N;
-      int gr = m0 + (int)(32u * u + (lane >> 1));
+      unsigned gr = m0 + (32u * u + (lane >> 1));
       gr = gr < mlast ? gr : mlast;
       src[i] = p.meta + (size_t)gr * 8 + 4u * (lane & 1u);
       step[i] = (size_t)p.out * 8;
       loff[i] = SA + u * 256u;
     } else {
       const unsigned j = t - (A_N + M_N), row = 8u * j + (lane >> 3), cs = (lane & 7u) ^ x_swz(row);
-      int gt = n0 + (int)row;
+      unsigned gt = n0 + row;
       gt = gt < tlast ? gt : tlast;
       src[i] = reinterpret_cast<const char*>(p.X + (size_t)gt * p.ldx + 8u * cs);
       step[i] = 128;
@@ -251,7 +191,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j)
-      linear24_store_frag<BF>(p, acc[i][j], m0 + (int)(wm * TM + i * 16 + 4u * g), n0 + (int)(wn * TN + j * 16 + r), bias_tok, bt[j], bias_out, bo[i]);
+      linear24_store_frag<Elt16<BF>, false>(p, acc[i][j], m0 + (wm * TM + i * 16 + 4u * g), n0 + (wn * TN + j * 16 + r), f4{}, 1.f, bt[j], bo[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -263,13 +203,11 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int FN, int NWV, int U, bool BF>
 __global__ __launch_bounds__(64 * NWV) void linear24_decode_kernel(const Linear24Args p) {
-  static_assert(FN * 64 <= 64 * NWV, "one thread per output piece in the combine");
-  __shared__ f4 part[NWV][FN][64];
   const unsigned tid = threadIdx.x, lane = tid & 63u, g = lane >> 4, r = lane & 15u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m0 = (int)blockIdx.x * 16;
-  int row = m0 + (int)r;
-  row = row < p.out - 1 ? row : p.out - 1;  // (clamped rows: computed, never stored)
+  const unsigned m0 = blockIdx.x * 16u;
+  unsigned row = m0 + r;
+  row = row < (unsigned)p.out - 1u ? row : (unsigned)p.out - 1u;  // (clamped rows: computed, never stored)
   const char* va = p.vals + (size_t)row * 64 + 16u * g;
   const char* me = p.meta + (size_t)row * 8 + 2u * g;
   const size_t vstep = (size_t)p.out * 64, mstep = (size_t)p.out * 8;
@@ -319,47 +257,13 @@ __global__ __launch_bounds__(64 * NWV) void linear24_decode_kernel(const Linear2
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < FN; ++j) part[wave][j][lane] = acc[j];
-  __syncthreads();
-  if (tid < (unsigned)(FN * 64)) {  // wave j finishes fragment j: lane for lane the accumulator map
-    const unsigned j = wave;
-    f4 s = part[0][j][lane];
-#pragma unroll
-    for (int w = 1; w < NWV; ++w) s += part[w][j][lane];
-    const int o0 = m0 + (int)(4u * g), t = 16 * (int)j + (int)r;
-    const bool bias_out = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_COL, bias_tok = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_ROW;
-    f4 bo = {0.f, 0.f, 0.f, 0.f};
-    float bt = 0.f;
-    if (bias_out) bo = linear24_bias_out(p, o0);
-    if (bias_tok && t < p.tokens) bt = p.e.bias[t];
-    linear24_store_frag<BF>(p, s, o0, t, bias_tok, bt, bias_out, bo);
-  }
+  linear24_decode_tail<Linear24Core, linear24_store_frag<Elt16<BF>, false>, false, FN, NWV>(p, acc, m0);
 }
 
 template <int BM, int BN, int WM, int WN, int NS, bool BF>
-static int launch_linear24_tile(const Linear24Args& a0, hipStream_t st) {
-  Linear24Args a = a0;
-  a.tiles_m = (a.out + BM - 1) / BM;
-  a.tiles_n = (a.tokens + BN - 1) / BN;
-  const size_t nwg = (size_t)a.tiles_m * a.tiles_n;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_linear24_{f16,bf16}: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  constexpr size_t lds = (size_t)NS * (BM * 72 + BN * 128);
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&linear24_tile_kernel<BM, BN, WM, WN, NS, BF>), lds, "linear24_tile_kernel")) return rc;
-  }
-  linear24_tile_kernel<BM, BN, WM, WN, NS, BF><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds, st>>>(a);
-  return check_launch("linear24_tile_kernel");
-}
-
-template <int FN, int NWV, int U, bool BF>
-static int launch_linear24_decode(const Linear24Args& a, hipStream_t st) {
-  linear24_decode_kernel<FN, NWV, U, BF><<<dim3((unsigned)ceil_div((size_t)a.out, 16)), dim3(64 * NWV), 0, st>>>(a);
-  return check_launch("linear24_decode_kernel");
+static int launch_linear24_tile16(const Linear24Args& a, hipStream_t st) {
+  return launch_linear24_tile<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF>, BM, BN, 64 * WM * WN, (size_t)NS * (BM * 72 + BN * 128)>(
+      a, st, LINEAR24_F16_WHO, "linear24_tile_kernel");
 }
 
 }  // namespace sm
@@ -370,39 +274,20 @@ template <bool BF>
 static int linear24(const void* blob, const void* X, void* Y, size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy, float alpha,
                     float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
   Linear24Args a = {};
-  bool plain;  // (not used: a plain epilogue takes the same kernels, whose bias / activation steps are skipped at run time)
-  if (const int rc = epilogue_args(ep, Y, 0, out, beta, a.e, &plain, "sm_linear24_{f16,bf16}")) return rc;
-  (void)plain;
-  if (!blob || !X || !Y || !aligned16(blob) || ldx < in || ldy < out) {
-    set_error("sm_linear24_{f16,bf16}: invalid argument (null operand, blob not 16-byte aligned, ldx < in_features or ldy < out_features)");
-    return SM_STATUS_INVALID_VALUE;
-  }
-  if (tokens > 0x7fffffffull || out > 0x7fffffffull || in > 0x7fffffffull) {
-    set_error("sm_linear24_{f16,bf16}: dimension exceeds 2^31-1");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  if (in % 64 != 0 || !aligned16(X) || ldx % 8 != 0) {
-    set_error("sm_linear24_{f16,bf16}: in_features %% 64 == 0 and 16-byte aligned rows of X (pointer, ldx %% 8) are required");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  if (tokens == 0 || out == 0) return SM_STATUS_SUCCESS;
-  const BlobLayout L = blob_layout(out, in, 2, 1);
-  a.vals = (const char*)blob;
-  a.meta = (const char*)blob + L.meta_off;
+  bool run;
+  const int rc = linear24_core_args(a, &run, LINEAR24_F16_WHO, true, "", blob, X, Y, tokens, out, in, ldx, ldy, 2, 8, alpha, beta, ep);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
   a.X = (const half_t*)X;
-  a.Y = (half_t*)Y;
-  a.ldx = ldx; a.ldy = ldy;
-  a.out = (int)out; a.tokens = (int)tokens; a.nkt = (int)(in / 64);
-  a.alpha = alpha; a.beta = beta;
-  const bool r_ok = beta == 0.0f || (reinterpret_cast<uintptr_t>(a.e.R) & 7u) == 0;
-  a.packed = (out % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 7u) == 0 && r_ok) ? 1 : 0;
+  a.nkt = (int)(in / 64);
   hipStream_t st = (hipStream_t)stream;
-  if (tokens <= LINEAR24_DECODE_MAX && out <= LINEAR24_DECODE_MAX_OUT) return launch_linear24_decode<1, 16, 4, BF>(a, st);
-  // the largest tile that still gives every CU a workgroup (256 CUs): fewer, larger tiles re-read X and the blob less
-  const size_t t128 = ceil_div(out, 128) * ceil_div(tokens, 128), t64 = ceil_div(out, 128) * ceil_div(tokens, 64);
-  if (tokens > 64 && t128 >= 256) return launch_linear24_tile<128, 128, 2, 2, 3, BF>(a, st);
-  if (t64 >= 256) return launch_linear24_tile<128, 64, 4, 1, 3, BF>(a, st);
-  return launch_linear24_tile<64, 64, 2, 2, 3, BF>(a, st);
+  switch (linear24_form(tokens, out, in, LINEAR24_F16_CUS)) {
+    case SM_LINEAR24_FORM_DECODE: return launch_linear24_decode<Linear24Args, linear24_decode_kernel<1, 16, 4, BF>, 64 * 16>(a, st, "linear24_decode_kernel");
+    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16<128, 128, 2, 2, 3, BF>(a, st);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16<128, 64, 4, 1, 3, BF>(a, st);
+    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16<64, 64, 2, 2, 3, BF>(a, st);
+  }
+  set_error("%s: grid too large", LINEAR24_F16_WHO);
+  return SM_STATUS_NOT_SUPPORTED;
 }
 
 extern "C" int sm_linear24_f16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
