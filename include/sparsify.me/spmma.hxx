@@ -82,6 +82,10 @@ struct spmma_fns_f16 {
                        float al, float be, const sm_epilogue_t* ep, hipStream_t st) {
     return sm_linear24_f16(blob, X, Y, tokens, out, in, ldx, ldy, al, be, ep, st);
   }
+  static int linear_glu_on(const void* blob, const void* X, void* Y, std::size_t tokens, std::size_t hidden, std::size_t in, std::size_t ldx,
+                           std::size_t ldy, int act, const float* bias, hipStream_t st) {
+    return sm_linear24_glu_f16(blob, X, Y, tokens, hidden, in, ldx, ldy, act, bias, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -126,6 +130,10 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
   static int linear_on(const void* blob, const void* X, void* Y, std::size_t tokens, std::size_t out, std::size_t in, std::size_t ldx, std::size_t ldy,
                        float al, float be, const sm_epilogue_t* ep, hipStream_t st) {
     return sm_linear24_bf16(blob, X, Y, tokens, out, in, ldx, ldy, al, be, ep, st);
+  }
+  static int linear_glu_on(const void* blob, const void* X, void* Y, std::size_t tokens, std::size_t hidden, std::size_t in, std::size_t ldx,
+                           std::size_t ldy, int act, const float* bias, hipStream_t st) {
+    return sm_linear24_glu_bf16(blob, X, Y, tokens, hidden, in, ldx, ldy, act, bias, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -493,6 +501,16 @@ class spmma_plan_t {
     if (!ready_ || batch_ != 1) return SM_STATUS_INVALID_VALUE;
     const sm_epilogue_t e = epilogue.c_struct(dY, tokens, m_, beta);
     return fns::linear_on(blob_.data().get(), dX, dY, tokens, m_, k_, ldx ? ldx : k_, ldy ? ldy : m_, alpha, beta, &e, stream);
+  }
+
+  // Extension (fp16 / bfloat16, a plan of batch_size 1 and an even m): the operand as the FUSED gate/up weight of a gated layer, rows
+  // 0 .. m/2-1 the gate projection and rows m/2 .. m-1 the up projection -- Y[tokens][m/2] = act(gate) * up in one launch
+  // (sm_linear24_glu_*).  act: SM_GLU_ACT_*; bias: m fp32 device values (gate's, then up's) or null; ldx / ldy: 0 = k / m/2.
+  int linear_glu(type_t* dX, type_t* dY, std::size_t tokens, int act = SM_GLU_ACT_SILU, const float* bias = nullptr, hipStream_t stream = nullptr,
+                 std::size_t ldx = 0, std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1 || m_ % 2 != 0) return SM_STATUS_INVALID_VALUE;
+    return fns::linear_glu_on(blob_.data().get(), dX, dY, tokens, m_ / 2, k_, ldx ? ldx : k_, ldy ? ldy : m_ / 2, act, bias, stream);
   }
 
  private:

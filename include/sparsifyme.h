@@ -278,8 +278,9 @@ int sm_spmma_fused_bf16_grouped_ws(size_t count, const void* const* A, const voi
  *             SM_ACT_LEAKY_RELU x >= 0 ? x : act_arg * x; SM_ACT_HARDSWISH x * min(max(x + 3, 0), 6) * (1/6).  Plain fp32
  *             arithmetic.  NaN in, NaN out for every activation; max(-0, 0) is +0 (ReLU, clipped ReLU and the inner clamp of
  *             hardswish return +0 for every x <= 0 that is not NaN, -0 included; leaky ReLU returns -0 for -0).
- *             GELU / SiLU / sigmoid are NOT offered: none of the layer tables this library is measured on uses them, and the
- *             device exp / erf they need would bring an error bound that has to be measured rather than derived.
+ *             GELU / sigmoid are NOT offered here: the device erf / tanh they need would bring an error bound that has to be
+ *             measured rather than derived.  SiLU is offered where the layer tables use it -- as the gate of a fused gate/up
+ *             projection (datasets/linear_shapes.csv), with its bound derived: sm_linear24_glu_{f16,bf16,fp8} below.
  *      The struct is read during the call (host memory); a NULL struct pointer, or one that says "no bias, SM_ACT_NONE, R == D
  *      (or beta == 0)", IS the plain entry point: same kernels, same bits.
  *      Status, decided before any device work: unknown act / bias_dim, beta != 0 with R == NULL, a non-finite or negative
@@ -407,6 +408,50 @@ int sm_linear24_fp8(const void* blob, const void* X, void* Y, size_t tokens, siz
 #define SM_LINEAR24_FORM_TILE128x64 4
 #define SM_LINEAR24_FORM_TILE128 5
 int sm_linear24_fp8_form(size_t tokens, size_t out_features, size_t in_features, size_t cus, int* form);
+
+/* ---- The gated (GLU) form of the token-major layers (extension): a fused gate/up projection and its gate in ONE launch, so that the
+ *      [tokens][2 hidden] intermediate is never written.
+ *
+ *          Y[t][h] = round_to_out( act(g) * u ),   g = s_g * acc(h, t) + bias[h],   u = s_u * acc(hidden + h, t) + bias[hidden + h]
+ *
+ *      blob     the UNCHANGED output of sm_compress24_*(W, m = 2 * hidden, k = in_features) for W[2 hidden][in]: rows 0 .. hidden-1 the
+ *               gate projection, rows hidden .. 2 hidden - 1 the up projection (the concatenation datasets/linear_shapes.csv counts).
+ *      X        as in the plain layers.
+ *      Y        row-major tokens x hidden, ldy >= hidden (elements), of the plain layer's type (16-bit: X's; fp8: out_type).  Columns at
+ *               or beyond hidden are not touched.
+ *      bias     2 * hidden fp32 values (device), gate's then up's, or NULL.
+ *      w_scale  2 * hidden floats or NULL; x_scale: tokens floats or NULL (fp8 only).
+ *      g and u are computed in fp32 by the expression -- and the code -- of the plain layer before its activation, with alpha = 1,
+ *      beta = 0: s = 1 (16-bit) or s = w_scale[row] * x_scale[t] (fp8, a NULL scale skipped), the bias as an addition of its own.  Then
+ *      a = act(g), y = a * u as one fp32 multiply, ONE rounding to the output type; nothing is contracted from act onward.
+ *      act      SM_GLU_ACT_NONE  a = g (bilinear); SM_GLU_ACT_RELU  a = max(g, 0) as SM_ACT_RELU computes it (max(-0, 0) = +0, NaN
+ *               propagates); SM_GLU_ACT_SILU, defined to the operation: e = expf(-g) (the device library's, <= 1 ulp), d = 1 + e,
+ *               a = g / d (correctly rounded division); when e is +inf (g below about -88.7, -inf included) a = -0.  NaN gives NaN,
+ *               +inf gives +inf.  |a - silu(g)| <= 4 * 2^-24 |silu(g)| + 2^-120 (exp 2^-23, add 2^-24, divide 2^-24; the second term
+ *               covers the cut to -0, where |silu| < 2.7e-37).  a * u is plain IEEE: 0 * inf = NaN.
+ *      Forms    sm_linear24_glu_form(tokens, hidden, in, cus) is BY DEFINITION sm_linear24_fp8_form(tokens, 2 * hidden, in, cus), plus
+ *               NOT_TAKEN for hidden > 0x3fffffff: the one function both entry points switch on (the 16-bit layer with cus = 256, fp8
+ *               with the device's; cus = 0: the device's).  The kernels are the plain layers' own (gated instantiations): a tile holds
+ *               the gate rows and the up rows of the same hidden features, so a lane ends with g and u of the same four outputs; g and
+ *               u have the bits the plain layer gives columns h and hidden + h.  The decode limits are carried over, not measured.
+ *      Status, decided before any device work, in this order: act not SM_GLU_ACT_*: SM_STATUS_INVALID_VALUE; null blob / X / Y, blob not
+ *      16-byte aligned, (fp8: fmt / out_type unknown,) ldx < in_features, ldy < hidden: SM_STATUS_INVALID_VALUE; a dimension >= 2^31,
+ *      hidden > 0x3fffffff, a tile grid beyond 2^31 - 1 workgroups: SM_STATUS_NOT_SUPPORTED; in_features % 64 != 0, X rows not 16-byte
+ *      aligned: SM_STATUS_NOT_SUPPORTED; tokens == 0 or hidden == 0: success, nothing enqueued.  Every hidden >= 1 is taken, odd hidden
+ *      included (the up rows then start at an odd blob row); the four-element store under the plain layer's conditions read on hidden.
+ *      Enqueue only: no allocation, no synchronisation, no workspace, no memset node; capturable into a hipGraph; same bits on every run.
+ *      Not covered: GELU / GeGLU, an fp8-quantised Y, interleaved gate/up layouts, alpha / beta / residual, a batch dimension. */
+#define SM_GLU_ACT_NONE 0 /* bilinear: g * u */
+#define SM_GLU_ACT_RELU 1 /* ReGLU:    max(g, 0) * u */
+#define SM_GLU_ACT_SILU 2 /* SwiGLU:   g / (1 + exp(-g)) * u */
+int sm_linear24_glu_f16(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
+                        int act, const float* bias, sm_stream_t stream);
+int sm_linear24_glu_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
+                         int act, const float* bias, sm_stream_t stream);
+int sm_linear24_glu_fp8(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
+                        int fmt_w, int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale, const float* bias,
+                        sm_stream_t stream);
+int sm_linear24_glu_form(size_t tokens, size_t hidden, size_t in_features, size_t cus, int* form);
 
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +

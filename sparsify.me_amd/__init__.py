@@ -165,6 +165,11 @@ for _sfx16 in ("f16", "bf16"):
 # ... and its fp8 form (linear24_fp8.hip) with the host-side query of its dispatch rule
 _SIGS["sm_linear24_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_i, _c_i, _c_i, _c_f, _c_f, _c_ptr, _c_ptr, _c_ptr, _c_ptr]
 _SIGS["sm_linear24_fp8_form"] = [_c_size] * 4 + [ctypes.POINTER(_c_i)]
+# the gated (gate/up) forms of both layers: one launch writes act(gate) * up
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_linear24_glu_" + _sfx16] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_i, _c_ptr, _c_ptr]
+_SIGS["sm_linear24_glu_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_i, _c_i, _c_i, _c_i, _c_ptr, _c_ptr, _c_ptr, _c_ptr]
+_SIGS["sm_linear24_glu_form"] = [_c_size] * 4 + [ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -456,6 +461,62 @@ def linear24_fp8_form(tokens, out_features, in_features, cus=0):
     switches on.  cus=0: this device's compute units; another value: host-only."""
     form = _c_i(-1)
     _check(lib().sm_linear24_fp8_form(tokens, out_features, in_features, cus, ctypes.byref(form)), "sm_linear24_fp8_form")
+    return LINEAR24_FORMS[form.value]
+
+
+# include/sparsifyme.h: SM_GLU_ACT_*
+GLU_ACTS = {"none": 0, "relu": 1, "silu": 2}
+
+
+def _glu_act(act, what):
+    if act not in GLU_ACTS:
+        raise SparsifymeError(f"{what}: act is one of {sorted(GLU_ACTS)}, not {act!r}")
+    return GLU_ACTS[act]
+
+
+def _glu_bias(bias, what):
+    if bias is not None and bias.dtype != _t().float32:
+        raise SparsifymeError(f"{what}: bias is float32, not {bias.dtype}")
+    return _dev(bias) if bias is not None else None
+
+
+def linear24_glu(blob, X, Y, tokens, hidden, in_features, act="silu", bias=None, ldx=None, ldy=None):
+    """Y[tokens][hidden] = act(g) * u, g = X . W[:hidden]^T + bias[:hidden], u = X . W[hidden:]^T + bias[hidden:], with W[2 hidden][in]
+    the 2:4 blob of compress24(W, m=2 * hidden, k=in_features): a fused gate/up projection and its gate in one launch
+    (sm_linear24_glu_*).  act: "silu" (SwiGLU), "relu" (ReGLU) or "none" (bilinear); bias: 2 * hidden float32 values or None."""
+    torch = _t()
+    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
+        raise SparsifymeError(f"linear24_glu: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+    a, b = _glu_act(act, "linear24_glu"), _glu_bias(bias, "linear24_glu")
+    ldx = in_features if ldx is None else ldx
+    ldy = hidden if ldy is None else ldy
+    fn = getattr(lib(), "sm_linear24_glu_" + _sfx(X))
+    _check(fn(_dev(blob), _dev(X), _dev(Y), tokens, hidden, in_features, ldx, ldy, a, b, _stream()), "sm_linear24_glu")
+
+
+def linear24_glu_fp8(blob, X, Y, tokens, hidden, in_features, act="silu", w_dtype=None, w_scale=None, x_scale=None, bias=None, ldx=None,
+                     ldy=None):
+    """linear24_glu on fp8 operands (sm_linear24_glu_fp8): g and u are (w_scale[row] * x_scale[t]) * acc + bias[row] with row = h and
+    hidden + h.  The formats come from the dtypes as in linear24_fp8; w_scale: 2 * hidden float32 values, x_scale: tokens, or None."""
+    fx = fp8_format(X.dtype)
+    fw = fx if w_dtype is None else fp8_format(w_dtype)
+    ot = _fp8_out_type(Y)
+    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
+        if v is not None and v.dtype != _t().float32:
+            raise SparsifymeError(f"linear24_glu_fp8: {name} is float32, not {v.dtype}")
+    a, b = _glu_act(act, "linear24_glu_fp8"), _glu_bias(bias, "linear24_glu_fp8")
+    ldx = in_features if ldx is None else ldx
+    ldy = hidden if ldy is None else ldy
+    _check(lib().sm_linear24_glu_fp8(_dev(blob), _dev(X), _dev(Y), tokens, hidden, in_features, ldx, ldy, fw, fx, ot, a,
+                                     _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None, b,
+                                     _stream()), "sm_linear24_glu_fp8")
+
+
+def linear24_glu_form(tokens, hidden, in_features, cus=0):
+    """The name (LINEAR24_FORMS) of the form the gated layers run for this shape -- sm_linear24_glu_form, by definition the plain rule
+    on 2 * hidden rows.  linear24_glu_fp8 asks with this device's compute units (cus=0), linear24_glu with cus=256."""
+    form = _c_i(-1)
+    _check(lib().sm_linear24_glu_form(tokens, hidden, in_features, cus, ctypes.byref(form)), "sm_linear24_glu_form")
     return LINEAR24_FORMS[form.value]
 
 

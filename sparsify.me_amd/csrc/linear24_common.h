@@ -25,6 +25,15 @@ inline int linear24_form(size_t tokens, size_t out, size_t in, size_t cus) {
   return ceil_div(out, 64) * ceil_div(tokens, 64) > 0x7fffffffull ? SM_LINEAR24_FORM_NOT_TAKEN : SM_LINEAR24_FORM_TILE64;
 }
 
+// The gated (gate/up) layer's rule is BY DEFINITION the plain rule on the fused weight's 2 * hidden rows (a tile of BM blob rows is
+// BM / 2 hidden features: the workgroup counts are the plain rule's), plus the limit that keeps 2 * hidden a 31-bit row count.  The
+// decode limits are carried over by weight bytes; nobody has measured them for the gated kernels.
+constexpr size_t LINEAR24_GLU_MAX_HIDDEN = 0x3fffffffull;
+inline int linear24_glu_form(size_t tokens, size_t hidden, size_t in, size_t cus) {
+  if (hidden > LINEAR24_GLU_MAX_HIDDEN) return SM_LINEAR24_FORM_NOT_TAKEN;
+  return linear24_form(tokens, 2 * hidden, in, cus);
+}
+
 // What the shared pieces read of a launch; each front end's argument block adds its X and its K extent.
 struct Linear24Core {
   const char* vals;  // the blob's values, plane-major
@@ -34,10 +43,11 @@ struct Linear24Core {
   const float* x_scale;  // per token, or null
   size_t ldx, ldy;   // elements
   float alpha, beta;  // (in front of the ints: the compiler reads alpha's splat as one 16-byte load, which must not reach a pointer)
-  int out, tokens;
+  int out, tokens;   // out: the width of Y.  The gated kernels (GLU) read it as `hidden`: their blob has 2 * out rows
   int tiles_m, tiles_n;
   int packed;        // Y (and R, when read) take four-element pieces: aligned to four elements, out % 4 == 0, ldy % 4 == 0
   EpiArgs e;         // bias_dim in Y's coordinates (SM_BIAS_COL: per out feature); R has Y's shape, type and ldy (R = Y when none was given)
+                     // the gated kernels: bias = 2 * hidden values (gate's, then up's) or null, act = SM_GLU_ACT_*, nothing else read
 };
 
 // The entry points' argument checks, in their order and with their statuses, and the fields of Linear24Core they settle.  `who`
@@ -75,8 +85,43 @@ inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool 
   return SM_STATUS_SUCCESS;
 }
 
+// The same for the gated entry points (sm_linear24_glu_*), in the order include/sparsifyme.h states: the activation first, then the
+// plain layer's list read on `hidden`.  The blob is that of W[2 * hidden][in]; alpha = 1, beta = 0, no residual.
+inline int linear24_glu_args(Linear24Core& a, bool* run, const char* who, bool extra_ok, const char* extra, const void* blob, const void* X, void* Y,
+                             size_t tokens, size_t hidden, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, int act, const float* bias) {
+  *run = false;
+  if (act != SM_GLU_ACT_NONE && act != SM_GLU_ACT_RELU && act != SM_GLU_ACT_SILU) {
+    set_error("%s: invalid argument (act is not SM_GLU_ACT_*)", who);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < hidden) {
+    set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < hidden)", who, extra);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  if (tokens > 0x7fffffffull || hidden > LINEAR24_GLU_MAX_HIDDEN || in > 0x7fffffffull) {
+    set_error("%s: dimension exceeds 2^31-1 (tokens, in_features, 2 * hidden)", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  if (in % 64 != 0 || !aligned16(X) || ldx % (16 / x_elt) != 0) {
+    set_error("%s: in_features %% 64 == 0 and 16-byte aligned rows of X (pointer, ldx %% %d) are required", who, (int)(16 / x_elt));
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  if (tokens == 0 || hidden == 0) return SM_STATUS_SUCCESS;
+  a.vals = (const char*)blob;
+  a.meta = (const char*)blob + blob_layout(2 * hidden, in, x_elt, 1).meta_off;
+  a.Y = Y;
+  a.ldx = ldx; a.ldy = ldy;
+  a.out = (int)hidden; a.tokens = (int)tokens;
+  a.alpha = 1.0f; a.beta = 0.0f;
+  a.packed = (hidden % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (piece - 1)) == 0) ? 1 : 0;
+  a.e = EpiArgs{bias, (const half_t*)Y, 0, SM_BIAS_COL, act, 0.0f, 1};
+  *run = true;
+  return SM_STATUS_SUCCESS;
+}
+
 // The tile form's launcher, one per kernel: the tile counts, the 2^31 - 1 grid limit, the opt-in to more than 64 KiB of dynamic LDS
-// (held per instantiation), the launch.  NT threads per workgroup, LDS bytes of the whole ring.
+// (held per instantiation), the launch.  NT threads per workgroup, LDS bytes of the whole ring.  BM: the features of Y (a.out) a
+// workgroup covers -- the kernel's tile rows, or half of them for a gated kernel, whose tile is BM gate rows + BM up rows.
 template <class Args, void (*KERNEL)(Args), int BM, int BN, int NT, size_t LDS>
 static int launch_linear24_tile(const Args& a0, hipStream_t st, const char* who, const char* kernel_name) {
   Args a = a0;
@@ -127,6 +172,13 @@ struct Elt16 {
   static __device__ __forceinline__ half_t conv(float v) { return to_elt<BF>(v); }
 };
 
+// s of s * acc for out feature q of the lane's four: alpha, or with SCALED sw[q] * x_scale[t] (a NULL x_scale skipped)
+template <bool SCALED>
+__device__ __forceinline__ float linear24_scale(const Linear24Core& p, f4 sw, float xs, int q) {
+  if constexpr (SCALED) return p.x_scale ? sw[q] * xs : sw[q];
+  else return p.alpha;
+}
+
 // One fragment's epilogue and store: the lane holds out features o0 .. o0+3 of token t.  s * acc + beta * R evaluated as
 // store_c_tile_epi / store_c_f8 evaluate it (beta * R added only when beta != 0), the bias as an addition of its own, the activation,
 // one rounding.  s = alpha, or with SCALED (sw[q] = alpha * w_scale[o0 + q], alpha when there is none) s = sw[q] * x_scale[t].
@@ -143,10 +195,7 @@ __device__ __forceinline__ void linear24_store_frag(const Linear24Core& p, const
   T* dst = reinterpret_cast<T*>(p.Y) + (size_t)t * p.ldy + o0;
   const T* rs = reinterpret_cast<const T*>(p.e.R) + (size_t)t * p.ldy + o0;
   const bool bias = p.e.bias != nullptr, bias_tok = bias && p.e.bias_dim == SM_BIAS_ROW, bias_out = bias && p.e.bias_dim == SM_BIAS_COL;
-  auto scale = [&](int q) {
-    if constexpr (SCALED) return p.x_scale ? sw[q] * xs : sw[q];
-    else return p.alpha;
-  };
+  auto scale = [&](int q) { return linear24_scale<SCALED>(p, sw, xs, q); };
   f4 v4;
   if (p.packed) {
     raw_t rraw = {};
@@ -175,6 +224,109 @@ __device__ __forceinline__ void linear24_store_frag(const Linear24Core& p, const
     for (int q = 0; q < 4; ++q)
       if (o0 + q < out) dst[q] = E::conv(v4[q]);
   }
+}
+
+// ---- the gated (gate/up) layer: Y[t][h] = act(g) * u, g from blob row h, u from blob row hidden + h (p.out = hidden) ----------------
+
+// The blob row behind local row `lrow` of a gated tile at hidden origin h0: 16-row fragment f = lrow / 16 is, f even, gate rows
+// h0 + 16 (f / 2) + r, and f odd the up rows of the same features -- so that a wave's accumulators 2i, 2i + 1 are a (gate, up) pair of
+// the same lane map.  Features past the edge are clamped to hidden - 1 (up: 2 hidden - 1): computed, never stored.
+__device__ __forceinline__ unsigned linear24_glu_row(unsigned h0, unsigned lrow, unsigned hidden) {
+  const unsigned f = lrow >> 4, h = h0 + 16u * (f >> 1) + (lrow & 15u);
+  return (h < hidden - 1u ? h : hidden - 1u) + ((f & 1u) ? hidden : 0u);
+}
+
+// The gate's activation on the lane's four values.  NONE and RELU are epi_act4's (the values agree: SM_GLU_ACT_RELU == SM_ACT_RELU).
+// SiLU, to the operation: e = expf(-g) (the device library's, <= 1 ulp), d = 1 + e, a = g / d (correctly rounded division);
+// e = +inf (g below about -88.7, -inf included, where g / d would be -0 or NaN): a = -0.  NaN in, NaN out; +inf gives +inf.
+__device__ __forceinline__ f4 linear24_glu_act4(f4 g, int act) {
+#pragma clang fp contract(off)
+  static_assert(SM_GLU_ACT_NONE == SM_ACT_NONE && SM_GLU_ACT_RELU == SM_ACT_RELU, "epi_act4 serves the first two");
+  if (act != SM_GLU_ACT_SILU) return epi_act4(g, act, 0.0f);
+  f4 a;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float e = expf(-g[q]);
+    const float d = 1.0f + e;
+    a[q] = e == __builtin_inff() ? -0.0f : g[q] / d;
+  }
+  return a;
+}
+
+// One (gate, up) fragment pair's store: the lane holds g and u of features h0 .. h0+3 of token t.  Each is s * acc, then the bias as an
+// addition of its own -- the expression linear24_store_frag evaluates before its activation (alpha = 1, beta = 0), through the same
+// functions; then a = act(g), y = a * u as ONE fp32 multiply (no contraction from act onward), one rounding.
+template <class E, bool SCALED>
+__device__ __forceinline__ void linear24_store_glu(const Linear24Core& p, const f4 accg, const f4 accu, unsigned h0, unsigned t, f4 swg, f4 swu, float xs,
+                                                   f4 bg, f4 bu) {
+  typedef typename E::T T;
+  typedef typename E::raw_t raw_t;
+  struct Piece { T v[4]; };
+  const unsigned hidden = (unsigned)p.out;
+  if (t >= (unsigned)p.tokens || h0 >= hidden) return;
+  T* dst = reinterpret_cast<T*>(p.Y) + (size_t)t * p.ldy + h0;
+  const bool bias = p.e.bias != nullptr;
+  f4 g4, u4v;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    g4[q] = linear24_scale<SCALED>(p, swg, xs, q) * accg[q];
+    u4v[q] = linear24_scale<SCALED>(p, swu, xs, q) * accu[q];
+  }
+  g4 = epi_bias4(g4, false, 0.f, bias, bg);
+  u4v = epi_bias4(u4v, false, 0.f, bias, bu);
+  f4 y;
+  {
+#pragma clang fp contract(off)
+    y = linear24_glu_act4(g4, p.e.act) * u4v;
+  }
+  if (p.packed) {
+    Piece o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o.v[q] = E::conv(y[q]);
+    *reinterpret_cast<raw_t*>(dst) = __builtin_bit_cast(raw_t, o);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (h0 + q < hidden) dst[q] = E::conv(y[q]);
+  }
+}
+
+// The gated decode form's tail: every wave's partial (gate, up) pair meets in LDS (2 x NWV KiB), wave 0 finishes both -- adding the
+// partials in wave order 0, 1, .. as linear24_decode_tail does, so that g and u have the plain decode kernel's bits -- fetches the
+// lane's biases and scales and hands the pair to STORE.  Workgroup = 16 hidden features from m0, tokens <= 16.
+template <class Args, void (*STORE)(const Args&, f4, f4, unsigned, unsigned, f4, f4, float, f4, f4), bool SCALED, int NWV>
+__device__ __forceinline__ void linear24_decode_tail_glu(const Args& p, const f4 (&acc)[2], unsigned m0) {
+  __shared__ f4 part[NWV][2][64];
+  const unsigned tid = threadIdx.x, lane = tid & 63u, g = lane >> 4, r = lane & 15u;
+  const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  part[wave][0][lane] = acc[0];
+  part[wave][1][lane] = acc[1];
+  __syncthreads();
+  if (tid >= 64u) return;
+  // (a loop of three turns, not straight-line code: with all 2 * NWV reads in flight at once the wave would need 8 * NWV registers
+  // for them -- beyond the 128 a 16-wave workgroup leaves each wave)
+  f4 sg = part[0][0][lane], su = part[0][1][lane];
+#pragma unroll 5
+  for (int w = 1; w < NWV; ++w) {
+    sg += part[w][0][lane];
+    su += part[w][1][lane];
+  }
+  const unsigned hidden = (unsigned)p.out, h0 = m0 + 4u * g, t = r;
+  const bool tv = t < (unsigned)p.tokens;
+  f4 bg = {0.f, 0.f, 0.f, 0.f}, bu = bg, swg = {p.alpha, p.alpha, p.alpha, p.alpha}, swu = swg;
+  float xs = 1.f;
+  if (p.e.bias != nullptr) {
+    bg = linear24_per_out(p.e.bias, h0, hidden);
+    bu = linear24_per_out(p.e.bias + hidden, h0, hidden);
+  }
+  if constexpr (SCALED) {
+    if (p.w_scale) {
+      swg = p.alpha * linear24_per_out(p.w_scale, h0, hidden);
+      swu = p.alpha * linear24_per_out(p.w_scale + hidden, h0, hidden);
+    }
+    if (p.x_scale && tv) xs = p.x_scale[t];
+  }
+  STORE(p, sg, su, h0, t, swg, swu, xs, bg, bu);
 }
 
 // The decode form's tail: every wave's partial fragments meet in LDS, wave j finishes fragment j -- lane for lane the accumulator

@@ -13,6 +13,8 @@
 //   decode  tokens <= LINEAR24_DECODE_MAX and out <= LINEAR24_DECODE_MAX_OUT: a pure weight stream.  One workgroup per 16 out features; its waves split K among
 //           themselves, stream the blob straight to registers (no other wave shares it) and add their fp32 partial tiles through
 //           LDS in wave order: deterministic, no workspace.  Other K order than the tile form: held to the arithmetic's bound.
+// The gated layer (sm_linear24_glu_{f16,bf16}: Y = act(gate) * up of a fused gate/up weight) is the GLU instantiation of the same two
+// kernels: only the blob rows a fragment is fetched from (linear24_glu_row) and the store (linear24_store_glu) differ.
 #include "linear24_common.h"
 
 namespace sm {
@@ -20,6 +22,7 @@ namespace sm {
 // the compute-unit count the rule is asked with: a constant, not the device's, so the dispatch is the same everywhere
 constexpr size_t LINEAR24_F16_CUS = 256;
 static const char* const LINEAR24_F16_WHO = "sm_linear24_{f16,bf16}";
+static const char* const LINEAR24_GLU16_WHO = "sm_linear24_glu_{f16,bf16}";
 
 struct Linear24Args : Linear24Core {  // vals stage-major [in/64][out][64 B]
   const half_t* X;
@@ -77,11 +80,14 @@ __device__ __forceinline__ void linear24_stage(const char* As, const char* Ms, c
 // (8 token rows per instruction, whole 128-byte lines, x_swz on the source).  Rows / tokens past the edge are clamped to the last
 // valid one: their products land in outputs that are never stored (an output depends on its own row and its own token only).
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, int NS, bool BF>
+// GLU: the tile's BM rows are BM / 2 gate rows and the BM / 2 up rows of the same hidden features, interleaved by 16-row fragment; p.out
+// is `hidden`, the width of Y, and the blob has 2 * p.out rows.
+template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU = false>
 __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linear24Args p) {
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
   static_assert(FM >= 1 && FN >= 1 && BM % 32 == 0 && BN % 8 == 0, "tile");
+  static_assert(!GLU || FM % 2 == 0, "a wave of a gated tile holds whole (gate, up) fragment pairs");
   static_assert(NS >= 2 && NS <= 4, "ring depth");
   constexpr int SA = BM * 64, SM_ = BM * 8, SX = BN * 128, STAGE = SA + SM_ + SX;
   constexpr int A_N = BM / 16, M_N = BM / 32, X_N = BN / 8, W = A_N + M_N + X_N;
@@ -99,6 +105,8 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
   // row and token indices are unsigned: an edge tile's origin plus its extent may pass 2^31 - 1 (never 2^32)
   const unsigned m0 = tile_m * BM, n0 = tile_n * BN;
   const unsigned mlast = (unsigned)p.out - 1u, tlast = (unsigned)p.tokens - 1u;
+  const unsigned hid0 = tile_m * (BM / 2);                           // GLU: the tile's first hidden feature
+  const size_t rows = GLU ? 2 * (size_t)p.out : (size_t)p.out;       // rows of the blob: the plane stride
 
   // the lane's bias values, fetched ahead of the K loop (plain loads, older than every DMA piece: the counted waits cover them)
   const bool bias_out = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_COL, bias_tok = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_ROW;
@@ -110,7 +118,10 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
   for (int j = 0; j < FN; ++j) bt[j] = 0.f;
   if (bias_out) {
 #pragma unroll
-    for (int i = 0; i < FM; ++i) bo[i] = linear24_per_out(p.e.bias, m0 + (wm * TM + i * 16 + 4u * g), (unsigned)p.out);
+    for (int i = 0; i < FM; ++i) {
+      if constexpr (GLU) bo[i] = linear24_per_out(p.e.bias + ((i & 1) ? p.out : 0), hid0 + (wm * (TM / 2) + (i / 2) * 16 + 4u * g), (unsigned)p.out);
+      else bo[i] = linear24_per_out(p.e.bias, m0 + (wm * TM + i * 16 + 4u * g), (unsigned)p.out);
+    }
   }
   if (bias_tok) {
 #pragma unroll
@@ -130,15 +141,17 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
       const unsigned row = 16u * t + (lane >> 2), cs = (lane & 3u) ^ a64_swz(row);
       unsigned gr = m0 + row;
       gr = gr < mlast ? gr : mlast;
+      if constexpr (GLU) gr = linear24_glu_row(hid0, row, (unsigned)p.out);
       src[i] = p.vals + (size_t)gr * 64 + 16u * cs;
-      step[i] = (size_t)p.out * 64;
+      step[i] = rows * 64;
       loff[i] = t * 1024u;
     } else if (t < (unsigned)(A_N + M_N)) {
       const unsigned u = t - A_N;
       unsigned gr = m0 + (32u * u + (lane >> 1));
       gr = gr < mlast ? gr : mlast;
+      if constexpr (GLU) gr = linear24_glu_row(hid0, 32u * u + (lane >> 1), (unsigned)p.out);  // (per lane half: a gate and an up fragment)
       src[i] = p.meta + (size_t)gr * 8 + 4u * (lane & 1u);
-      step[i] = (size_t)p.out * 8;
+      step[i] = rows * 8;
       loff[i] = SA + u * 256u;
     } else {
       const unsigned j = t - (A_N + M_N), row = 8u * j + (lane >> 3), cs = (lane & 7u) ^ x_swz(row);
@@ -187,11 +200,20 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
   }
 
   // ---- store: no LDS, no barrier -- each lane's four out features are one piece of Y's row
+  if constexpr (GLU) {
 #pragma unroll
-  for (int i = 0; i < FM; ++i)
+    for (int i = 0; i < FM; i += 2)
 #pragma unroll
-    for (int j = 0; j < FN; ++j)
-      linear24_store_frag<Elt16<BF>, false>(p, acc[i][j], m0 + (wm * TM + i * 16 + 4u * g), n0 + (wn * TN + j * 16 + r), f4{}, 1.f, bt[j], bo[i]);
+      for (int j = 0; j < FN; ++j)
+        linear24_store_glu<Elt16<BF>, false>(p, acc[i][j], acc[i + 1][j], hid0 + (wm * (TM / 2) + (i / 2) * 16 + 4u * g), n0 + (wn * TN + j * 16 + r), f4{},
+                                             f4{}, 1.f, bo[i], bo[i + 1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+        linear24_store_frag<Elt16<BF>, false>(p, acc[i][j], m0 + (wm * TM + i * 16 + 4u * g), n0 + (wn * TN + j * 16 + r), f4{}, 1.f, bt[j], bo[i]);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -201,8 +223,13 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
 // columns at or beyond `tokens` are fed zeros.  The partial tiles meet in LDS and are added in wave order 0, 1, ..: the same
 // bits on every run.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int FN, int NWV, int U, bool BF>
+// GLU: one workgroup per 16 hidden features; a wave streams the gate fragment and the up fragment of its stage (NF = 2 value and
+// metadata loads) against the same X registers, K split and combine order unchanged: g and u have this kernel's plain bits.
+template <int FN, int NWV, int U, bool BF, bool GLU = false>
 __global__ __launch_bounds__(64 * NWV) void linear24_decode_kernel(const Linear24Args p) {
+  static_assert(!GLU || FN == 1, "the gated decode form holds one token fragment");
+  constexpr int NF = GLU ? 2 : 1;  // blob fragments per stage
+  const size_t rows = GLU ? 2 * (size_t)p.out : (size_t)p.out;
   const unsigned tid = threadIdx.x, lane = tid & 63u, g = lane >> 4, r = lane & 15u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned m0 = blockIdx.x * 16u;
@@ -210,7 +237,8 @@ __global__ __launch_bounds__(64 * NWV) void linear24_decode_kernel(const Linear2
   row = row < (unsigned)p.out - 1u ? row : (unsigned)p.out - 1u;  // (clamped rows: computed, never stored)
   const char* va = p.vals + (size_t)row * 64 + 16u * g;
   const char* me = p.meta + (size_t)row * 8 + 2u * g;
-  const size_t vstep = (size_t)p.out * 64, mstep = (size_t)p.out * 8;
+  const size_t vstep = rows * 64, mstep = rows * 8;
+  const size_t vup = GLU ? (size_t)p.out * 64 : 0, mup = GLU ? (size_t)p.out * 8 : 0;  // from a gate row to its up row
   const half_t* xr[FN];
   bool xv[FN];
 #pragma unroll
@@ -219,21 +247,24 @@ __global__ __launch_bounds__(64 * NWV) void linear24_decode_kernel(const Linear2
     xv[j] = t < p.tokens;
     xr[j] = p.X + (size_t)(xv[j] ? t : 0) * p.ldx + 8u * g;
   }
-  f4 acc[FN];
+  f4 acc[NF * FN];  // GLU: {gate, up}
 #pragma unroll
-  for (int j = 0; j < FN; ++j) acc[j] = f4{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < NF * FN; ++j) acc[j] = f4{0.f, 0.f, 0.f, 0.f};
 
   for (int s = (int)wave; s < p.nkt; s += NWV * U) {
-    u4 a[U], x0[U][FN], x1[U][FN];
-    int ix[U];
+    u4 a[U][NF], x0[U][FN], x1[U][FN];
+    int ix[U][NF];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int ss = s + u * NWV;  // wave-uniform
-      a[u] = u4{0u, 0u, 0u, 0u};
-      ix[u] = 0;
-      if (ss < p.nkt) {
-        a[u] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(va + (size_t)ss * vstep));
-        ix[u] = (int)__builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(me + (size_t)ss * mstep));
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        a[u][f] = u4{0u, 0u, 0u, 0u};
+        ix[u][f] = 0;
+        if (ss < p.nkt) {
+          a[u][f] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(va + (size_t)ss * vstep + f * vup));
+          ix[u][f] = (int)__builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(me + (size_t)ss * mstep + f * mup));
+        }
       }
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
@@ -252,18 +283,21 @@ __global__ __launch_bounds__(64 * NWV) void linear24_decode_kernel(const Linear2
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           const u8v all = {x0[u][j][0], x0[u][j][1], x0[u][j][2], x0[u][j][3], x1[u][j][0], x1[u][j][1], x1[u][j][2], x1[u][j][3]};
-          acc[j] = smfmac16<BF>(__builtin_bit_cast(h8, a[u]), __builtin_bit_cast(h16, all), acc[j], ix[u]);
+#pragma unroll
+          for (int f = 0; f < NF; ++f)
+            acc[j * NF + f] = smfmac16<BF>(__builtin_bit_cast(h8, a[u][f]), __builtin_bit_cast(h16, all), acc[j * NF + f], ix[u][f]);
         }
       }
     }
   }
-  linear24_decode_tail<Linear24Core, linear24_store_frag<Elt16<BF>, false>, false, FN, NWV>(p, acc, m0);
+  if constexpr (GLU) linear24_decode_tail_glu<Linear24Core, linear24_store_glu<Elt16<BF>, false>, false, NWV>(p, acc, m0);
+  else linear24_decode_tail<Linear24Core, linear24_store_frag<Elt16<BF>, false>, false, FN, NWV>(p, acc, m0);
 }
 
-template <int BM, int BN, int WM, int WN, int NS, bool BF>
+template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU = false>
 static int launch_linear24_tile16(const Linear24Args& a, hipStream_t st) {
-  return launch_linear24_tile<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF>, BM, BN, 64 * WM * WN, (size_t)NS * (BM * 72 + BN * 128)>(
-      a, st, LINEAR24_F16_WHO, "linear24_tile_kernel");
+  return launch_linear24_tile<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF, GLU>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                              (size_t)NS * (BM * 72 + BN * 128)>(a, st, GLU ? LINEAR24_GLU16_WHO : LINEAR24_F16_WHO, "linear24_tile_kernel");
 }
 
 }  // namespace sm
@@ -297,4 +331,34 @@ extern "C" int sm_linear24_f16(const void* blob, const void* X, void* Y, size_t 
 extern "C" int sm_linear24_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
                                 size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
   return linear24<true>(blob, X, Y, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue, stream);
+}
+
+template <bool BF>
+static int linear24_glu(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in, size_t ldx, size_t ldy, int act,
+                        const float* bias, sm_stream_t stream) {
+  Linear24Args a = {};
+  bool run;
+  const int rc = linear24_glu_args(a, &run, LINEAR24_GLU16_WHO, true, "", blob, X, Y, tokens, hidden, in, ldx, ldy, 2, 8, act, bias);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.X = (const half_t*)X;
+  a.nkt = (int)(in / 64);
+  hipStream_t st = (hipStream_t)stream;
+  switch (linear24_glu_form(tokens, hidden, in, LINEAR24_F16_CUS)) {
+    case SM_LINEAR24_FORM_DECODE:
+      return launch_linear24_decode<Linear24Args, linear24_decode_kernel<1, 16, 4, BF, true>, 64 * 16>(a, st, "linear24_decode_kernel");
+    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16<128, 128, 2, 2, 3, BF, true>(a, st);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16<128, 64, 4, 1, 3, BF, true>(a, st);
+    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16<64, 64, 2, 2, 3, BF, true>(a, st);
+  }
+  set_error("%s: grid too large", LINEAR24_GLU16_WHO);
+  return SM_STATUS_NOT_SUPPORTED;
+}
+
+extern "C" int sm_linear24_glu_f16(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
+                                   int act, const float* bias, sm_stream_t stream) {
+  return linear24_glu<false>(blob, X, Y, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+}
+extern "C" int sm_linear24_glu_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
+                                    int act, const float* bias, sm_stream_t stream) {
+  return linear24_glu<true>(blob, X, Y, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
 }

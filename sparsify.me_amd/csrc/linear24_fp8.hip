@@ -17,15 +17,18 @@
 //           out features; its waves split the 128-k stages among themselves, stream the blob straight to registers and add their
 //           fp32 partial tiles through LDS in wave order: deterministic, no workspace, no atomics.  Other K order than the tile
 //           form: held to the arithmetic's bound.
+// The gated layer (sm_linear24_glu_fp8: Y = act(gate) * up of a fused gate/up weight) is the GLU instantiation of the same two
+// kernels: only the blob rows a fragment is fetched from (linear24_glu_row) and the store (linear24_store_glu) differ.
 #include "spmma_b8.h"
 #include "linear24_common.h"
 
 namespace sm {
 
 static const char* const LINEAR24_FP8_WHO = "sm_linear24_fp8";
+static const char* const LINEAR24_GLU8_WHO = "sm_linear24_glu_fp8";
 
 struct Linear8Args : Linear24Core {  // vals plane-major [in/64][out][32 B]
-  size_t Mtot;  // rows of the blob (= out)
+  size_t Mtot;  // rows of the blob (= out; the gated kernels: 2 * out)
   const uint8_t* X;
   int nplanes;   // in / 64
   int out_type;  // SM_OUT_*: the type of Y and R
@@ -46,6 +49,14 @@ __device__ __forceinline__ void linear8_store_frag_any(const Linear8Args& p, con
   else linear24_store_frag<EltOut<SM_OUT_BF16>, true>(p, acc, o0, t, sw, xs, bt, bo);
 }
 
+// ... and the gated store under the same switch
+__device__ __forceinline__ void linear8_store_glu_any(const Linear8Args& p, const f4 accg, const f4 accu, unsigned h0, unsigned t, f4 swg, f4 swu, float xs,
+                                                      f4 bg, f4 bu) {
+  if (p.out_type == SM_OUT_F32) linear24_store_glu<EltOut<SM_OUT_F32>, true>(p, accg, accu, h0, t, swg, swu, xs, bg, bu);
+  else if (p.out_type == SM_OUT_F16) linear24_store_glu<EltOut<SM_OUT_F16>, true>(p, accg, accu, h0, t, swg, swu, xs, bg, bu);
+  else linear24_store_glu<EltOut<SM_OUT_BF16>, true>(p, accg, accu, h0, t, swg, swu, xs, bg, bu);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Tile form.  Stage = 128 dense k = two planes: blob values [BM][64 B] (plane 0 | plane 1 per row, 16 rows per DMA instruction,
 // a64_swz on the source), metadata [2][BM][8 B] (4-byte pieces, 32 rows of one plane per instruction: any row count), X
@@ -53,11 +64,14 @@ __device__ __forceinline__ void linear8_store_frag_any(const Linear8Args& p, con
 // the last valid one: their products land in outputs that are never stored.  An odd plane count: the last stage's second plane
 // (values, metadata) and X's k 64 .. 127 come from the zero page, as in spmma_b8_kernel.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <class MM, int BM, int BN, int WM, int WN, int NS>
+// GLU: the tile's BM rows are BM / 2 gate rows and the BM / 2 up rows of the same hidden features, interleaved by 16-row fragment; p.out
+// is `hidden`, the width of Y, and the blob has p.Mtot = 2 * p.out rows.
+template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU = false>
 __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const Linear8Args p) {
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
   static_assert(FM >= 1 && FN >= 1 && BM % 32 == 0 && BN % 8 == 0, "tile");
+  static_assert(!GLU || FM % 2 == 0, "a wave of a gated tile holds whole (gate, up) fragment pairs");
   static_assert(NS >= 2 && NS <= 4, "ring depth");
   constexpr int SA = BM * 64, SM_ = 2 * BM * 8, SX = BN * 128, STAGE = SA + SM_ + SX;
   constexpr int MB = BM / 32;  // metadata instructions per plane
@@ -76,6 +90,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const L
   // row and token indices are unsigned: an edge tile's origin plus its extent may pass 2^31 - 1 (never 2^32)
   const unsigned m0 = tile_m * BM, n0 = tile_n * BN;
   const unsigned mlast = (unsigned)p.out - 1u, tlast = (unsigned)p.tokens - 1u;
+  const unsigned hid0 = tile_m * (BM / 2);  // GLU: the tile's first hidden feature
 
   // the lane's scales and bias values, fetched ahead of the K loop (plain loads, older than every DMA piece: the counted waits cover them)
   const bool bias_out = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_COL, bias_tok = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_ROW;
@@ -84,11 +99,13 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const L
   float bt[FN], xs[FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
-    const unsigned o0 = m0 + (wm * TM + i * 16 + 4u * g);
+    // (GLU: fragment i is the gate (i even) or up (i odd) rows of hidden features o0 ..; the vectors hold gate's values, then up's)
+    const unsigned o0 = GLU ? hid0 + (wm * (TM / 2) + (i / 2) * 16 + 4u * g) : m0 + (wm * TM + i * 16 + 4u * g);
+    const unsigned up = GLU && (i & 1) ? (unsigned)p.out : 0u;
     bo[i] = f4{0.f, 0.f, 0.f, 0.f};
     sw[i] = f4{p.alpha, p.alpha, p.alpha, p.alpha};
-    if (bias_out) bo[i] = linear24_per_out(p.e.bias, o0, (unsigned)p.out);
-    if (p.w_scale) sw[i] = p.alpha * linear24_per_out(p.w_scale, o0, (unsigned)p.out);
+    if (bias_out) bo[i] = linear24_per_out(p.e.bias + up, o0, (unsigned)p.out);
+    if (p.w_scale) sw[i] = p.alpha * linear24_per_out(p.w_scale + up, o0, (unsigned)p.out);
   }
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
@@ -111,6 +128,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const L
       const unsigned row = 16u * t + (lane >> 2), cs = (lane & 3u) ^ a64_swz(row);  // source chunk: plane cs >> 1, half cs & 1
       unsigned gr = m0 + row;
       gr = gr < mlast ? gr : mlast;
+      if constexpr (GLU) gr = linear24_glu_row(hid0, row, (unsigned)p.out);
       src[i] = p.vals + ((size_t)(cs >> 1) * p.Mtot + (size_t)gr) * 32 + 16u * (cs & 1u);
       loff[i] = t * 1024u;
       second[i] = (cs >> 1) != 0;  // per lane
@@ -118,6 +136,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const L
       const unsigned u = t - A_N, pl = u / MB, blk = u % MB;
       unsigned gr = m0 + (32u * blk + (lane >> 1));
       gr = gr < mlast ? gr : mlast;
+      if constexpr (GLU) gr = linear24_glu_row(hid0, 32u * blk + (lane >> 1), (unsigned)p.out);  // (per lane half: a gate and an up fragment)
       src[i] = p.meta + ((size_t)pl * p.Mtot + (size_t)gr) * 8 + 4u * (lane & 1u);
       loff[i] = SA + pl * (BM * 8) + blk * 256u;
       second[i] = pl != 0;
@@ -190,11 +209,20 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const L
   }
 
   // ---- store: no LDS, no barrier -- each lane's four out features are one piece of Y's row
+  if constexpr (GLU) {
 #pragma unroll
-  for (int i = 0; i < FM; ++i)
+    for (int i = 0; i < FM; i += 2)
 #pragma unroll
-    for (int j = 0; j < FN; ++j)
-      linear8_store_frag_any(p, acc[i][j], m0 + (wm * TM + i * 16 + 4u * g), n0 + (wn * TN + j * 16 + r), sw[i], xs[j], bt[j], bo[i]);
+      for (int j = 0; j < FN; ++j)
+        linear8_store_glu_any(p, acc[i][j], acc[i + 1][j], hid0 + (wm * (TM / 2) + (i / 2) * 16 + 4u * g), n0 + (wn * TN + j * 16 + r), sw[i], sw[i + 1],
+                              xs[j], bo[i], bo[i + 1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+        linear8_store_frag_any(p, acc[i][j], m0 + (wm * TM + i * 16 + 4u * g), n0 + (wn * TN + j * 16 + r), sw[i], xs[j], bt[j], bo[i]);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -204,8 +232,12 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const L
 // columns at or beyond `tokens` are fed zeros; so are the second plane and X's k 64 .. 127 of an odd last stage.  The partial tiles
 // meet in LDS and are added in wave order 0, 1, ..: the same bits on every run.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <class MM, int FN, int NWV, int U>
+// GLU: one workgroup per 16 hidden features; a wave streams the gate fragment and the up fragment of its stage (NF = 2 value and
+// metadata loads) against the same X registers, K split and combine order unchanged: g and u have this kernel's plain bits.
+template <class MM, int FN, int NWV, int U, bool GLU = false>
 __global__ __launch_bounds__(64 * NWV) void linear24_fp8_decode_kernel(const Linear8Args p) {
+  static_assert(!GLU || FN == 1, "the gated decode form holds one token fragment");
+  constexpr int NF = GLU ? 2 : 1;  // blob fragments per stage
   const unsigned tid = threadIdx.x, lane = tid & 63u, g = lane >> 4, r = lane & 15u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned m0 = blockIdx.x * 16u;
@@ -215,6 +247,7 @@ __global__ __launch_bounds__(64 * NWV) void linear24_fp8_decode_kernel(const Lin
   const char* va = p.vals + ((size_t)(g >> 1) * p.Mtot + (size_t)row) * 32 + 16u * (g & 1u);
   const char* me = p.meta + ((size_t)(g >> 1) * p.Mtot + (size_t)row) * 8 + 4u * (g & 1u);
   const size_t vstep = 2 * p.Mtot * 32, mstep = 2 * p.Mtot * 8;
+  const size_t vup = GLU ? (size_t)p.out * 32 : 0, mup = GLU ? (size_t)p.out * 8 : 0;  // from a gate row to its up row
   const int nkt = (p.nplanes + 1) / 2;
   const bool odd = (p.nplanes & 1) != 0;
   const uint8_t* xr[FN];
@@ -225,22 +258,25 @@ __global__ __launch_bounds__(64 * NWV) void linear24_fp8_decode_kernel(const Lin
     xv[j] = t < p.tokens;
     xr[j] = p.X + (size_t)(xv[j] ? t : 0) * p.ldx + 16u * g;
   }
-  f4 acc[FN];
+  f4 acc[NF * FN];  // GLU: {gate, up}
 #pragma unroll
-  for (int j = 0; j < FN; ++j) acc[j] = f4{0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < NF * FN; ++j) acc[j] = f4{0.f, 0.f, 0.f, 0.f};
 
   for (int s = (int)wave; s < nkt; s += NWV * U) {
-    u4 a[U], x0[U][FN], x1[U][FN];
-    int ix[U];
+    u4 a[U][NF], x0[U][FN], x1[U][FN];
+    int ix[U][NF];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int ss = s + u * NWV;  // wave-uniform
       const bool live = ss < nkt, tail = odd && ss == nkt - 1;
-      a[u] = u4{0u, 0u, 0u, 0u};
-      ix[u] = 0;
-      if (live && !(tail && g >= 2u)) {
-        a[u] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(va + (size_t)ss * vstep));
-        ix[u] = __builtin_nontemporal_load(reinterpret_cast<const int*>(me + (size_t)ss * mstep));
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        a[u][f] = u4{0u, 0u, 0u, 0u};
+        ix[u][f] = 0;
+        if (live && !(tail && g >= 2u)) {
+          a[u][f] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(va + (size_t)ss * vstep + f * vup));
+          ix[u][f] = __builtin_nontemporal_load(reinterpret_cast<const int*>(me + (size_t)ss * mstep + f * mup));
+        }
       }
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
@@ -259,29 +295,38 @@ __global__ __launch_bounds__(64 * NWV) void linear24_fp8_decode_kernel(const Lin
         for (int j = 0; j < FN; ++j) {
           const i8v xf = i8v{(int)x0[u][j][0], (int)x0[u][j][1], (int)x0[u][j][2], (int)x0[u][j][3],
                              (int)x1[u][j][0], (int)x1[u][j][1], (int)x1[u][j][2], (int)x1[u][j][3]};
-          acc[j] = MM::mma(__builtin_bit_cast(i4v, a[u]), xf, acc[j], ix[u]);
+#pragma unroll
+          for (int f = 0; f < NF; ++f) acc[j * NF + f] = MM::mma(__builtin_bit_cast(i4v, a[u][f]), xf, acc[j * NF + f], ix[u][f]);
         }
       }
     }
   }
-  linear24_decode_tail<Linear8Args, linear8_store_frag_any, true, FN, NWV>(p, acc, m0);
+  if constexpr (GLU) linear24_decode_tail_glu<Linear8Args, linear8_store_glu_any, true, NWV>(p, acc, m0);
+  else linear24_decode_tail<Linear8Args, linear8_store_frag_any, true, FN, NWV>(p, acc, m0);
 }
 
-template <class MM, int BM, int BN, int WM, int WN, int NS>
+template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU>
 static int launch_linear8_tile(const Linear8Args& a, hipStream_t st) {
-  return launch_linear24_tile<Linear8Args, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS>, BM, BN, 64 * WM * WN, (size_t)NS * (BM * 80 + BN * 128)>(
-      a, st, LINEAR24_FP8_WHO, "linear24_fp8_tile_kernel");
+  return launch_linear24_tile<Linear8Args, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS, GLU>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                              (size_t)NS * (BM * 80 + BN * 128)>(a, st, GLU ? LINEAR24_GLU8_WHO : LINEAR24_FP8_WHO, "linear24_fp8_tile_kernel");
 }
 
-template <int FW, int FX>
+template <int FW, int FX, bool GLU>
 static int linear8_launch(const Linear8Args& a, int form, hipStream_t st) {
   typedef MmaF8<FW, FX> MM;
   switch (form) {
-    case SM_LINEAR24_FORM_DECODE: return launch_linear24_decode<Linear8Args, linear24_fp8_decode_kernel<MM, 1, 16, 4>, 64 * 16>(a, st, "linear24_fp8_decode_kernel");
-    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile<MM, 128, 128, 2, 2, 3>(a, st);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile<MM, 128, 64, 4, 1, 3>(a, st);
-    default: return launch_linear8_tile<MM, 64, 64, 2, 2, 3>(a, st);
+    case SM_LINEAR24_FORM_DECODE:
+      return launch_linear24_decode<Linear8Args, linear24_fp8_decode_kernel<MM, 1, 16, 4, GLU>, 64 * 16>(a, st, "linear24_fp8_decode_kernel");
+    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile<MM, 128, 128, 2, 2, 3, GLU>(a, st);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile<MM, 128, 64, 4, 1, 3, GLU>(a, st);
+    default: return launch_linear8_tile<MM, 64, 64, 2, 2, 3, GLU>(a, st);
   }
+}
+
+template <bool GLU>
+static int linear8_launch_fmt(const Linear8Args& a, int fmt_w, int fmt_x, int form, hipStream_t st) {
+  if (fmt_w == SM_FP8_E4M3) return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E4M3, SM_FP8_E4M3, GLU>(a, form, st) : linear8_launch<SM_FP8_E4M3, SM_FP8_E5M2, GLU>(a, form, st);
+  return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E5M2, SM_FP8_E4M3, GLU>(a, form, st) : linear8_launch<SM_FP8_E5M2, SM_FP8_E5M2, GLU>(a, form, st);
 }
 
 }  // namespace sm
@@ -319,6 +364,37 @@ extern "C" int sm_linear24_fp8(const void* blob, const void* X, void* Y, size_t 
     set_error("%s: grid too large", LINEAR24_FP8_WHO);
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (fmt_w == SM_FP8_E4M3) return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E4M3, SM_FP8_E4M3>(a, form, st) : linear8_launch<SM_FP8_E4M3, SM_FP8_E5M2>(a, form, st);
-  return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E5M2, SM_FP8_E4M3>(a, form, st) : linear8_launch<SM_FP8_E5M2, SM_FP8_E5M2>(a, form, st);
+  return linear8_launch_fmt<false>(a, fmt_w, fmt_x, form, st);
+}
+
+extern "C" int sm_linear24_glu_form(size_t tokens, size_t hidden, size_t in_features, size_t cus, int* form) {
+  if (!form) {
+    set_error("sm_linear24_glu_form: invalid argument (form is NULL)");
+    return SM_STATUS_INVALID_VALUE;
+  }
+  *form = linear24_glu_form(tokens, hidden, in_features, cus ? cus : (size_t)device_cu_count());
+  return SM_STATUS_SUCCESS;
+}
+
+extern "C" int sm_linear24_glu_fp8(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
+                                   int fmt_w, int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale, const float* bias,
+                                   sm_stream_t stream) {
+  Linear8Args a = {};
+  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
+  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
+  bool run;
+  const int rc = linear24_glu_args(a, &run, LINEAR24_GLU8_WHO, fmt_ok && out_ok, "fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob, X, Y, tokens, hidden,
+                                   in_features, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, act, bias);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.Mtot = 2 * hidden;
+  a.X = (const uint8_t*)X;
+  a.nplanes = (int)(in_features / 64);
+  a.out_type = out_type;
+  a.w_scale = w_scale; a.x_scale = x_scale;
+  const int form = linear24_glu_form(tokens, hidden, in_features, (size_t)device_cu_count());
+  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
+    set_error("%s: grid too large", LINEAR24_GLU8_WHO);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  return linear8_launch_fmt<true>(a, fmt_w, fmt_x, form, (hipStream_t)stream);
 }
