@@ -836,6 +836,36 @@ int sm_conv_spmma_fused_f16(const void* X, const void* B, void* C, size_t N, siz
                             size_t stride, size_t pad, size_t dilation, size_t n_out, float alpha, float beta, sm_stream_t stream);
 int sm_conv_spmma_fused_bf16(const void* X, const void* B, void* C, size_t N, size_t Cin, size_t H, size_t W, size_t kh, size_t kw,
                              size_t stride, size_t pad, size_t dilation, size_t n_out, float alpha, float beta, sm_stream_t stream);
+/* WHICH KERNEL CLASS sm_conv_spmma_fused_{f16,bf16} run for a layer, and the stage plan they run it with: the dispatch rule as a
+ * host-side query -- the one function the entry points themselves switch on, so the answer is what launches.  For tests (a test
+ * named for a class asserts that its layer reaches it) and schedulers; no device work.
+ *   N .. n_out: as passed to the entry point.  flags: what the entry point reads off its pointers -- SM_CONV_FLAG_X_ALIGNED16 (X on a
+ *   16-byte boundary; implies _X_ALIGNED4), _X_ALIGNED4 (X on a 4-byte boundary), _B_ALIGNED16 (B on a 16-byte boundary).
+ * *form: SM_CONV_FORM_NOT_TAKEN -- the entry point returns SM_STATUS_NOT_SUPPORTED (sm_conv_spmma_* then needs its workspace);
+ *   _EMPTY -- success, nothing launched (N, Cin or n_out zero); _V16 -- 16-byte patch DMAs (W % 8 == 0, a 16-byte aligned X, at most
+ *   16 DMA instructions per stage); _SMALL4 / _LARGE4 -- 4-byte patch DMAs with at most 16 / at most 48 instructions per stage.
+ *   Each class has a 64-column (n_out <= 64) and a 128-column kernel: plan[0].
+ * plan (may be NULL; else SM_CONV_PLAN_WORDS unsigned), the numbers the kernel is launched with:
+ *   [0] column tile (64 or 128)      [1] RI: patch rows per channel      [2] pitch: patch row pitch in halves (padl + W)
+ *   [3] padl: zero halves in front of a row   [4] rpi: patch rows per DMA instruction   [5] nch: channels a 64-deep stage can touch
+ *   [6] a_n: patch DMA instructions per stage  [7] patch_bytes: one stage's patch buffer   [8] dynamic LDS bytes of the launch
+ *   [9] tiles_m: 128-pixel tiles per image     [10] tiles_n: column tiles
+ *   _EMPTY: zeros.  _NOT_TAKEN: [0] and, as far as the rule got before it declined, [1] .. [7] of the 4-byte plan (zeros for a
+ *   refusal that precedes the plan: n_out % 8, the alignments, K % 64, W, kh * kw); [8] .. [10] zero.  sm_last_error() then holds the
+ *   words the entry point would leave, under this query's name.
+ * Status: SM_STATUS_INVALID_VALUE for form == NULL, an unknown flag, and what the entry point answers so: a zero window extent,
+ * stride or dilation, a window larger than the padded input. */
+#define SM_CONV_FORM_NOT_TAKEN 0
+#define SM_CONV_FORM_EMPTY 1
+#define SM_CONV_FORM_V16 2
+#define SM_CONV_FORM_SMALL4 3
+#define SM_CONV_FORM_LARGE4 4
+#define SM_CONV_FLAG_X_ALIGNED16 1u
+#define SM_CONV_FLAG_X_ALIGNED4 2u
+#define SM_CONV_FLAG_B_ALIGNED16 4u
+#define SM_CONV_PLAN_WORDS 11
+int sm_conv_spmma_fused_plan(size_t N, size_t Cin, size_t H, size_t W, size_t kh, size_t kw, size_t stride, size_t pad, size_t dilation,
+                             size_t n_out, unsigned flags, int* form, unsigned* plan);
 /* The same product by the faster of its two routes (round 4): the implicit-GEMM kernel, or -- small-spatial layers with a long K
  * (out_h * out_w <= 256 and K >= 2048: the 14 x 14 x 512-channel layers of a ResNet) -- sm_im2col_compress24_* into `workspace`
  * followed by sm_spmma_*.  Same C bit for bit either way.  sm_conv_spmma_workspace gives the bytes: the blob's size

@@ -106,6 +106,7 @@ _SIGS["sm_prune24_spmma_bf16"] = _SIGS["sm_prune24_spmma_f16"]
 _SIGS["sm_prune24_compress24_f32"] = _SIGS["sm_prune24_compress24_f16"]
 _SIGS["sm_conv_spmma_fused_f16"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 10 + [_c_f, _c_f, _c_ptr]
 _SIGS["sm_conv_spmma_fused_bf16"] = _SIGS["sm_conv_spmma_fused_f16"]
+_SIGS["sm_conv_spmma_fused_plan"] = [_c_size] * 10 + [ctypes.c_uint, ctypes.POINTER(_c_i), ctypes.POINTER(ctypes.c_uint)]
 _SIGS["sm_transpose"] = [_c_ptr, _c_ptr] + [_c_size] * 8 + [_c_ptr]
 _SIGS["sm_conv_out_size"] = [_c_size, _c_size, _c_size, _c_size, _c_size, ctypes.POINTER(_c_size)]
 _SIGS["sm_im2col_f16"] = [_c_ptr] + [_c_size] * 9 + [_c_ptr, _c_ptr]
@@ -886,6 +887,25 @@ def conv_spmma_fused(X, B, C, N, Cin, H, W, kh, kw, stride, pad, dilation, n_out
     fn = getattr(lib(), "sm_conv_spmma_fused_" + _sfx(X))
     _check(fn(_dev(X), _dev(B), _dev(C), N, Cin, H, W, kh, kw, stride, pad, dilation, n_out, float(alpha), float(beta), _stream()),
            "sm_conv_spmma_fused")
+
+
+# include/sparsifyme.h: SM_CONV_FORM_* (index = value), SM_CONV_FLAG_* and the words of the plan
+CONV_FORMS = ("not_taken", "empty", "v16", "small4", "large4")
+CONV_FLAG_X_ALIGNED16, CONV_FLAG_X_ALIGNED4, CONV_FLAG_B_ALIGNED16 = 1, 2, 4
+CONV_PLAN_FIELDS = ("bn", "RI", "pitch", "padl", "rpi", "nch", "a_n", "patch_bytes", "lds", "tiles_m", "tiles_n")
+
+
+def conv_spmma_fused_plan(N, Cin, H, W, kh, kw, stride, pad, dilation, n_out, x_align=16, b_aligned=True):
+    """(form, plan): the name (CONV_FORMS) of the kernel class conv_spmma_fused runs for this layer and the stage plan it is launched
+    with as a dict (CONV_PLAN_FIELDS) -- sm_conv_spmma_fused_plan, the rule the entry points themselves switch on.  x_align: the
+    largest of 16, 4, 2 that divides X's address.  Host-only."""
+    flags = ((CONV_FLAG_X_ALIGNED16 | CONV_FLAG_X_ALIGNED4) if x_align % 16 == 0 else CONV_FLAG_X_ALIGNED4 if x_align % 4 == 0 else 0) | \
+            (CONV_FLAG_B_ALIGNED16 if b_aligned else 0)
+    form = _c_i(-1)
+    buf = (ctypes.c_uint * len(CONV_PLAN_FIELDS))()
+    _check(lib().sm_conv_spmma_fused_plan(N, Cin, H, W, kh, kw, stride, pad, dilation, n_out, flags, ctypes.byref(form), buf),
+           "sm_conv_spmma_fused_plan")
+    return CONV_FORMS[form.value], dict(zip(CONV_PLAN_FIELDS, list(buf)))
 
 
 def conv_spmma_workspace(N, Cin, H, W, kh, kw, stride, pad, dilation):

@@ -223,23 +223,8 @@ __global__ __launch_bounds__(256, SMALL ? (BN == 64 ? 4 : 3) : 1) void conv_spmm
 }
 
 template <int BN, bool BF, bool V16 = false, bool SMALL = V16>
-static int launch_conv(const ConvArgs& a0, hipStream_t st) {
-  ConvArgs a = a0;
-  a.tiles_m = (a.L + 127) / 128;
-  a.tiles_n = (a.Nout + BN - 1) / BN;
+static int launch_conv(const ConvArgs& a, size_t lds, hipStream_t st) {
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.N;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_conv_spmma_fused: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  const size_t lds_main = 2 * ((size_t)a.patch_bytes + 64 * BN * 2) + (size_t)a.khkw * 128;
-  const size_t lds_epi = (size_t)128 * (BN * 2 + 16);
-  const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  if (lds > 160 * 1024) {
-    set_error("sm_conv_spmma_fused: the activation patch of a stage (%d bytes) does not fit LDS", a.patch_bytes);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   static LdsOptIn lds_optin;
   if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&conv_spmma_fused_kernel<BN, BF, V16, SMALL>), 160 * 1024, "conv_spmma_fused_kernel")) return rc;
   conv_spmma_fused_kernel<BN, BF, V16, SMALL><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
@@ -288,61 +273,157 @@ static const char* conv_geometry_plan(size_t N, size_t Cin, size_t H, size_t W, 
   return nullptr;
 }
 
-template <bool BF>
-static int conv_spmma16(const void* X, const void* B, void* C, size_t N, size_t Cin, size_t H, size_t W, size_t kh, size_t kw,
-                        size_t stride, size_t pad, size_t dil, size_t n_out, float alpha, float beta, sm_stream_t stream) {
-  const char* name = BF ? "sm_conv_spmma_fused_bf16" : "sm_conv_spmma_fused_f16";
-  if (!X || !B || !C || kh == 0 || kw == 0 || stride == 0 || dil == 0) {
-    set_error("%s: invalid argument", name);
-    return SM_STATUS_INVALID_VALUE;
+// THE DISPATCH RULE of sm_conv_spmma_fused_*: which kernel class a call runs and the plan it is launched with, as a host function of
+// the geometry, n_out and what the entry point reads off its pointers (flags: SM_CONV_FLAG_*).  conv_spmma16 below switches on its
+// answer and sm_conv_spmma_fused_plan exports it, so a query names what launches.  No device work.
+enum ConvWhy { CONV_WHY_NONE = 0, CONV_WHY_INVALID, CONV_WHY_WINDOW, CONV_WHY_OPERANDS, CONV_WHY_GEOMETRY, CONV_WHY_GRID, CONV_WHY_LDS };
+struct ConvRule {
+  int form;         // SM_CONV_FORM_*
+  int bn;           // column tile: 64 or 128 (0 before it is chosen)
+  int why;          // ConvWhy of a refusal (form == SM_CONV_FORM_NOT_TAKEN)
+  const char* geo;  // CONV_WHY_GEOMETRY: conv_geometry_plan's words
+  size_t lds;       // dynamic LDS bytes of the launch
+  ConvArgs a;       // the kernel's arguments but for the pointers, alpha and beta
+};
+
+static void conv_fused_rule(size_t N, size_t Cin, size_t H, size_t W, size_t kh, size_t kw, size_t stride, size_t pad, size_t dil, size_t n_out,
+                            unsigned flags, ConvRule& r) {
+  r = ConvRule{};
+  r.form = SM_CONV_FORM_NOT_TAKEN;
+  if (kh == 0 || kw == 0 || stride == 0 || dil == 0) {
+    r.why = CONV_WHY_INVALID;
+    return;
   }
   {
     const size_t sh = dil * (kh - 1) + 1, sw = dil * (kw - 1) + 1;
     if (H <= (1u << 20) && W <= (1u << 20) && pad <= (1u << 20) && kh <= (1u << 20) && kw <= (1u << 20) && dil <= (1u << 20) &&
         (H + 2 * pad < sh || W + 2 * pad < sw)) {
-      set_error("%s: window larger than the padded input", name);
-      return SM_STATUS_INVALID_VALUE;
+      r.why = CONV_WHY_WINDOW;
+      return;
     }
   }
-  if (N == 0 || Cin == 0 || n_out == 0) return SM_STATUS_SUCCESS;
+  if (N == 0 || Cin == 0 || n_out == 0) {
+    r.form = SM_CONV_FORM_EMPTY;
+    return;
+  }
+  const bool x16 = (flags & SM_CONV_FLAG_X_ALIGNED16) != 0, x4 = x16 || (flags & SM_CONV_FLAG_X_ALIGNED4) != 0;
   // what the kernel takes beyond the geometry: n % 8 == 0, 16-byte aligned B rows, 4-byte aligned input rows; anything else:
   // sm_im2col_compress24_* + sm_spmma_* (the same result)
-  if (n_out % 8 != 0 || n_out > 0x7fffffffull || !aligned16(B) || (reinterpret_cast<uintptr_t>(X) & 3u) != 0) {
-    set_error("%s: needs n %% 8 == 0, a 16-byte aligned B and a 4-byte aligned X (use sm_im2col_compress24 + sm_spmma)", name);
-    return SM_STATUS_NOT_SUPPORTED;
+  if (n_out % 8 != 0 || n_out > 0x7fffffffull || !(flags & SM_CONV_FLAG_B_ALIGNED16) || !x4) {
+    r.why = CONV_WHY_OPERANDS;
+    return;
   }
   // 16-byte patch DMAs (round 4) where rows are whole 16-byte pieces: W % 8 == 0, a 16-byte aligned X, the border rounded up to
   // 8 halves and the stage's plan within 16 instructions; when only those tighter limits fail (narrow images: W = 8 gains little
   // per instruction and pays the wider border) the 4-byte form takes the layer as it did before round 4.
-  ConvArgs a = {};
-  bool v16 = W % 8 == 0 && aligned16(X);
+  bool v16 = W % 8 == 0 && x16;
   const size_t bn = n_out <= 64 ? 64 : 128;
-  const char* why = v16 ? conv_geometry_plan(N, Cin, H, W, kh, kw, stride, pad, dil, true, bn, a) : "";
+  r.bn = (int)bn;
+  const char* why = v16 ? conv_geometry_plan(N, Cin, H, W, kh, kw, stride, pad, dil, true, bn, r.a) : "";
   if (why) {
     v16 = false;
-    a = ConvArgs{};
-    why = conv_geometry_plan(N, Cin, H, W, kh, kw, stride, pad, dil, false, bn, a);
+    r.a = ConvArgs{};
+    why = conv_geometry_plan(N, Cin, H, W, kh, kw, stride, pad, dil, false, bn, r.a);
   }
   if (why) {
-    set_error("%s: %s (use sm_im2col_compress24 + sm_spmma)", name, why);
-    return SM_STATUS_NOT_SUPPORTED;
+    r.why = CONV_WHY_GEOMETRY;
+    r.geo = why;
+    return;
   }
-  a.X = (const half_t*)X; a.B = (const half_t*)B; a.C = (half_t*)C;
-  a.Nout = (int)n_out;
-  a.alpha = alpha; a.beta = beta;
-  hipStream_t st = (hipStream_t)stream;
+  r.a.Nout = (int)n_out;
+  r.a.tiles_m = (r.a.L + 127) / 128;
+  r.a.tiles_n = (int)((n_out + bn - 1) / bn);
+  if ((size_t)r.a.tiles_m * r.a.tiles_n * r.a.N > 0x7fffffffu) {
+    r.why = CONV_WHY_GRID;
+    return;
+  }
+  const size_t lds_main = 2 * ((size_t)r.a.patch_bytes + 64 * bn * 2) + (size_t)r.a.khkw * 128;
+  const size_t lds_epi = (size_t)128 * (bn * 2 + 16);
+  r.lds = lds_main > lds_epi ? lds_main : lds_epi;
+  if (r.lds > 160 * 1024) {
+    r.why = CONV_WHY_LDS;
+    return;
+  }
   // (256-column tiles for n_out > 128 -- the patch gathered once per 256 output channels -- were built and measured in round 4:
   //  n = 256 unchanged (73.8 vs 74.1 us), n = 512 slower (134 vs 103 us: 223 registers, two workgroups per CU, half the tiles);
   //  profiles/conv_levers_r04k.txt.  Not kept.)
-  if (v16) return n_out <= 64 ? launch_conv<64, BF, true>(a, st) : launch_conv<128, BF, true>(a, st);
-  if (a.a_n <= 16) return n_out <= 64 ? launch_conv<64, BF, false, true>(a, st) : launch_conv<128, BF, false, true>(a, st);
-  if (n_out <= 64) return launch_conv<64, BF>(a, st);
-  return launch_conv<128, BF>(a, st);
+  r.form = v16 ? SM_CONV_FORM_V16 : r.a.a_n <= 16 ? SM_CONV_FORM_SMALL4 : SM_CONV_FORM_LARGE4;
+}
+
+// The status and the words of a refusal (r.form == SM_CONV_FORM_NOT_TAKEN), under the entry point's name.
+static int conv_refusal(const char* name, const ConvRule& r) {
+  switch (r.why) {
+    case CONV_WHY_INVALID:
+      set_error("%s: invalid argument", name);
+      return SM_STATUS_INVALID_VALUE;
+    case CONV_WHY_WINDOW:
+      set_error("%s: window larger than the padded input", name);
+      return SM_STATUS_INVALID_VALUE;
+    case CONV_WHY_OPERANDS:
+      set_error("%s: needs n %% 8 == 0, a 16-byte aligned B and a 4-byte aligned X (use sm_im2col_compress24 + sm_spmma)", name);
+      return SM_STATUS_NOT_SUPPORTED;
+    case CONV_WHY_GEOMETRY:
+      set_error("%s: %s (use sm_im2col_compress24 + sm_spmma)", name, r.geo);
+      return SM_STATUS_NOT_SUPPORTED;
+    case CONV_WHY_GRID:
+      set_error("sm_conv_spmma_fused: grid too large");
+      return SM_STATUS_NOT_SUPPORTED;
+    default:
+      set_error("sm_conv_spmma_fused: the activation patch of a stage (%d bytes) does not fit LDS", r.a.patch_bytes);
+      return SM_STATUS_NOT_SUPPORTED;
+  }
+}
+
+template <bool BF>
+static int conv_spmma16(const void* X, const void* B, void* C, size_t N, size_t Cin, size_t H, size_t W, size_t kh, size_t kw,
+                        size_t stride, size_t pad, size_t dil, size_t n_out, float alpha, float beta, sm_stream_t stream) {
+  const char* name = BF ? "sm_conv_spmma_fused_bf16" : "sm_conv_spmma_fused_f16";
+  if (!X || !B || !C) {
+    set_error("%s: invalid argument", name);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  const unsigned flags = (aligned16(X) ? SM_CONV_FLAG_X_ALIGNED16 : 0u) | ((reinterpret_cast<uintptr_t>(X) & 3u) == 0 ? SM_CONV_FLAG_X_ALIGNED4 : 0u) |
+                         (aligned16(B) ? SM_CONV_FLAG_B_ALIGNED16 : 0u);
+  ConvRule r;
+  conv_fused_rule(N, Cin, H, W, kh, kw, stride, pad, dil, n_out, flags, r);
+  if (r.form == SM_CONV_FORM_EMPTY) return SM_STATUS_SUCCESS;
+  if (r.form == SM_CONV_FORM_NOT_TAKEN) return conv_refusal(name, r);
+  ConvArgs& a = r.a;
+  a.X = (const half_t*)X; a.B = (const half_t*)B; a.C = (half_t*)C;
+  a.alpha = alpha; a.beta = beta;
+  hipStream_t st = (hipStream_t)stream;
+  const bool n64 = r.bn == 64;
+  switch (r.form) {
+    case SM_CONV_FORM_V16: return n64 ? launch_conv<64, BF, true>(a, r.lds, st) : launch_conv<128, BF, true>(a, r.lds, st);
+    case SM_CONV_FORM_SMALL4: return n64 ? launch_conv<64, BF, false, true>(a, r.lds, st) : launch_conv<128, BF, false, true>(a, r.lds, st);
+    default: return n64 ? launch_conv<64, BF>(a, r.lds, st) : launch_conv<128, BF>(a, r.lds, st);
+  }
 }
 
 }  // namespace sm
 
 using namespace sm;
+
+extern "C" int sm_conv_spmma_fused_plan(size_t N, size_t Cin, size_t H, size_t W, size_t kh, size_t kw, size_t stride, size_t pad, size_t dilation,
+                                        size_t n_out, unsigned flags, int* form, unsigned* plan) {
+  if (!form || (flags & ~(SM_CONV_FLAG_X_ALIGNED16 | SM_CONV_FLAG_X_ALIGNED4 | SM_CONV_FLAG_B_ALIGNED16)) != 0) {
+    set_error("sm_conv_spmma_fused_plan: invalid argument");
+    return SM_STATUS_INVALID_VALUE;
+  }
+  ConvRule r;
+  conv_fused_rule(N, Cin, H, W, kh, kw, stride, pad, dilation, n_out, flags, r);
+  // a refusal leaves the entry point's words in sm_last_error(), under this query's name
+  if (r.form == SM_CONV_FORM_NOT_TAKEN && conv_refusal("sm_conv_spmma_fused_plan", r) == SM_STATUS_INVALID_VALUE) return SM_STATUS_INVALID_VALUE;
+  *form = r.form;
+  if (plan) {
+    const bool taken = r.form != SM_CONV_FORM_NOT_TAKEN && r.form != SM_CONV_FORM_EMPTY;
+    const unsigned v[SM_CONV_PLAN_WORDS] = {(unsigned)r.bn, (unsigned)r.a.RI, (unsigned)r.a.pitch, (unsigned)r.a.padl, (unsigned)r.a.rpi, (unsigned)r.a.nch,
+                                            (unsigned)r.a.a_n, (unsigned)r.a.patch_bytes, taken ? (unsigned)r.lds : 0u,
+                                            taken ? (unsigned)r.a.tiles_m : 0u, taken ? (unsigned)r.a.tiles_n : 0u};
+    for (int i = 0; i < SM_CONV_PLAN_WORDS; ++i) plan[i] = v[i];
+  }
+  return SM_STATUS_SUCCESS;
+}
 
 extern "C" int sm_conv_spmma_fused_f16(const void* X, const void* B, void* C, size_t N, size_t Cin, size_t H, size_t W, size_t kh,
                                        size_t kw, size_t stride, size_t pad, size_t dilation, size_t n_out, float alpha, float beta,

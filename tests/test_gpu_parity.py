@@ -2888,7 +2888,7 @@ CONV_CASES = [  # N, Cin, H, W, kh, kw, stride, pad, dil, n_out
     (1, 128, 56, 56, 3, 3, 1, 1, 1, 128),    # ResNet-50 conv3_x geometry
     (1, 64, 112, 112, 3, 3, 1, 1, 1, 64),    # one patch row per DMA instruction
     (2, 64, 28, 28, 3, 3, 2, 1, 1, 64),      # stride 2
-    (2, 64, 14, 14, 1, 1, 1, 0, 1, 72),      # 1 x 1, n % 64 != 0
+    (2, 64, 14, 14, 1, 1, 1, 0, 1, 72),      # 1 x 1 on 14 x 14, n % 64 != 0: a stage's 64 channels x 11 rows need 88 DMA instructions > 48: declined (not for its window)
     (1, 64, 20, 20, 3, 3, 1, 2, 2, 64),      # dilation 2
     (1, 256, 14, 14, 3, 3, 1, 1, 1, 256),    # two column tiles
     (1, 64, 18, 18, 5, 5, 1, 2, 1, 64),      # 25 phases
@@ -2904,7 +2904,8 @@ CONV_CASES = [  # N, Cin, H, W, kh, kw, stride, pad, dil, n_out
 def test_conv_spmma_fused_equals_im2col_compress_spmma(gpu, orc, case, bf):
     """sm_conv_spmma_fused_* (implicit GEMM: the A operand is gathered from an activation patch in LDS) must be
     BIT-identical to sm_im2col_compress24_* + sm_spmma_* -- same kept values, same codes, same SMFMAC sequence -- and,
-    through that pair, match the oracle (im2col restatement -> compress -> spmma, fp64 accumulation)."""
+    through that pair, match the oracle (im2col restatement -> compress -> spmma, fp64 accumulation).  The 1 x 1 case of the list is declined
+    (status 2) for the size of its stage plan, not for its window: tests/test_gpu_conv.py runs the 1 x 1 layers the kernel takes."""
     import torch
     N, Cin, H, W, kh, kw, s_, p_, d_, n_out = case
     rng = np.random.default_rng(Cin + H * 3 + kh * 7 + s_)
@@ -2926,8 +2927,9 @@ def test_conv_spmma_fused_equals_im2col_compress_spmma(gpu, orc, case, bf):
     gpu.spmma(blob, dB, C1, L, n_out, K, N, 0)
     C2 = torch.full((N * L * n_out,), 7.0, dtype=tdt, device="cuda")
     if kh * kw == 1:
-        # a 1 x 1 window makes A a plain transpose of X (64 channels per stage: nothing to gather, nothing saved); the
-        # kernel declines it and the documented pair above is the path
+        # a 1 x 1 window makes a 64-deep stage touch 64 channels: on this 14 x 14 image that is nch * RI = 64 * 11 patch rows, 8 per DMA
+        # instruction = 88 instructions against the plan's limit of 48.  THAT declines the case (sm_conv_spmma_fused_plan: "too many DMA
+        # instructions"), and the documented pair above is the path; a smaller 1 x 1 layer is taken (tests/test_gpu_conv.py)
         with pytest.raises(gpu.SparsifymeError, match="status 2"):
             gpu.conv_spmma_fused(dX, dB, C2, N, Cin, H, W, kh, kw, s_, p_, d_, n_out)
         return
