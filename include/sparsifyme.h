@@ -115,6 +115,76 @@ int sm_prune24_compress24_bf16(const void* A_in, void* A_out, size_t m, size_t k
 int sm_prune24_compress24_f32(const float* A_in, float* A_out, size_t m, size_t k, size_t ld, size_t batch, size_t strideA,
                               void* blob, int* d_valid, int alg, sm_stream_t stream);
 
+/* ---- WHICH KERNEL a prune / check / compress / decompress / one-pass call runs: the dispatch rules of the entry points above as
+ *      host-side queries -- each is the one function its entry point itself switches on, so the answer is what launches.  For tests (a
+ *      test named for a kernel asserts that its call reaches it) and tools; no device work.  Arguments are the call's own sizes and
+ *      strides, elt_bytes (2: f16 and bf16, which dispatch alike; 4: fp32), alg, and the operand POINTERS, which are taken as addresses
+ *      only (alignment, null or not) and never dereferenced.  *form = _INVALID: the entry point returns SM_STATUS_INVALID_VALUE; _EMPTY:
+ *      success, nothing launched.  Status: SM_STATUS_INVALID_VALUE for form == NULL or another elt_bytes.
+ *
+ *      sm_prune24_form / sm_prune24_check_form (SM_PRUNE24_FORM_*):
+ *        STRIP and the check run one kernel with two flags: VEC -- both pointers 16-byte aligned and ld % 8 == 0 (fp32: ld % 4 == 0),
+ *        16-byte accesses, else element accesses; FLAT -- ld == k and k % 8 == 0, rows back to back.
+ *        TILE, 16-bit: _TILE2 -- k % 8 == 0, ld % 8 == 0, both pointers 16-byte aligned (two tiles per thread); _SPAN -- not _TILE2,
+ *        ld == k, k <= 4096, both pointers 16-byte aligned: 8 .. 64 rows per workgroup through LDS (*span_rows, chosen by how the tile
+ *        count fills the workgroup; span_rows may be NULL); _ELEMENT_VEC -- both pointers 8-byte aligned and ld % 4 == 0;
+ *        _ELEMENT_SCALAR -- everything else.  TILE, fp32: _ELEMENT_VEC (16-byte aligned, ld % 4 == 0) or _ELEMENT_SCALAR.
+ *      sm_compress24_form (SM_COMPRESS24_FORM_*): _FLAT -- A 16-byte aligned, ld == k, k % 64 == 0, strideA a multiple of 16 bytes,
+ *        batches back to back (strideA == m * ld or batch == 1); _ROWSPAN -- 16-bit only, not _FLAT: A 16-byte aligned, batches back
+ *        to back (strideA == m * ld or batch == 1), 32 * ld * 2 + 32 <= 48 KiB (ld <= 767), any ld >= k (nothing behind the last
+ *        logical element, (M - 1) * ld + k, is read); _GENERAL_VEC (A 16-byte aligned, ld and strideA multiples of 16 bytes) / _GENERAL_SCALAR -- everything else.
+ *      sm_decompress24_form (SM_DECOMPRESS24_FORM_*): _VEC (A 16-byte aligned, ld and strideA multiples of 16 bytes) / _SCALAR.
+ *      sm_prune24_compress24_form (SM_PRUNE24_COMPRESS24_FORM_*): the one-pass kernel is taken when k % 64 == 0, ld and strideA are
+ *        multiples of 16 bytes and A_in and a non-null A_out are 16-byte aligned: _ONEPASS_TILE, _ONEPASS_TILE_NOBLOB (16-bit, TILE,
+ *        blob == NULL: the blob's re-selection compiled out) or _ONEPASS_STRIP; plan[0] = 1 for the FLAT instantiation (batch == 1, or
+ *        batches back to back with m % 4 == 0), plan[1] = lpr_log2 (3 .. 6: lanes along k per tile row, the largest power of two
+ *        <= 64 dividing k / 8), plan[2] = nj (passes per row, k / 8 >> lpr_log2), plan[3] = the grid, plan[4] = 1 when the grid was
+ *        capped at 8 workgroups per compute unit (`cus`; 0: the current device's, 256 when none is visible; any other value makes the
+ *        call host-only).  Otherwise the three launches: _FALLBACK_TALL_SPAN (16-bit TILE with A_out, the batch one tall matrix --
+ *        batch == 1, or batches back to back and m % 4 == 0 -- that sm_prune24's span form takes: prune and flag in one pass),
+ *        _FALLBACK_TALL (the batch as one tall matrix: back to back, and STRIP or m % 4 == 0), _FALLBACK_PER_BATCH (a prune and a
+ *        check launch per batch matrix, at A + b * strideA); plan[5] = matrices the prune and check loops run over.  _NOT_SUPPORTED:
+ *        TILE + blob without A_out off the one-pass kernel; the entry point returns SM_STATUS_NOT_SUPPORTED before anything -- the
+ *        flag word included -- is touched.  plan: >= 6 unsigned, or NULL. */
+#define SM_PRUNE24_FORM_INVALID 0
+#define SM_PRUNE24_FORM_EMPTY 1
+#define SM_PRUNE24_FORM_STRIP_SCALAR 2       /* prune_strip_kernel / prune_check_kernel, element accesses                */
+#define SM_PRUNE24_FORM_STRIP_VEC 3          /* ... 16-byte accesses                                                      */
+#define SM_PRUNE24_FORM_STRIP_FLAT_SCALAR 4  /* ... rows back to back, element accesses                                   */
+#define SM_PRUNE24_FORM_STRIP_FLAT_VEC 5     /* ... rows back to back, 16-byte accesses                                   */
+#define SM_PRUNE24_FORM_TILE2 6              /* prune_tile2_kernel                                                        */
+#define SM_PRUNE24_FORM_SPAN 7               /* prune_tile_span_kernel                                                    */
+#define SM_PRUNE24_FORM_ELEMENT_SCALAR 8     /* prune_tile_kernel, element accesses                                       */
+#define SM_PRUNE24_FORM_ELEMENT_VEC 9        /* prune_tile_kernel, one 8-byte (16-bit) / 16-byte (fp32) access per tile row */
+#define SM_COMPRESS24_FORM_INVALID 0
+#define SM_COMPRESS24_FORM_EMPTY 1
+#define SM_COMPRESS24_FORM_FLAT 2            /* compress_flat_kernel                                                      */
+#define SM_COMPRESS24_FORM_ROWSPAN 3         /* compress_rowspan_f16_kernel                                               */
+#define SM_COMPRESS24_FORM_GENERAL_SCALAR 4  /* compress_kernel, element loads                                            */
+#define SM_COMPRESS24_FORM_GENERAL_VEC 5     /* compress_kernel, 16-byte loads                                            */
+#define SM_DECOMPRESS24_FORM_INVALID 0
+#define SM_DECOMPRESS24_FORM_EMPTY 1
+#define SM_DECOMPRESS24_FORM_SCALAR 2
+#define SM_DECOMPRESS24_FORM_VEC 3
+#define SM_PRUNE24_COMPRESS24_FORM_INVALID 0
+#define SM_PRUNE24_COMPRESS24_FORM_EMPTY 1
+#define SM_PRUNE24_COMPRESS24_FORM_NOT_SUPPORTED 2
+#define SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL_SPAN 3
+#define SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL 4
+#define SM_PRUNE24_COMPRESS24_FORM_FALLBACK_PER_BATCH 5
+#define SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE 6
+#define SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE_NOBLOB 7
+#define SM_PRUNE24_COMPRESS24_FORM_ONEPASS_STRIP 8
+int sm_prune24_form(const void* A_in, const void* A_out, size_t m, size_t k, size_t ld, size_t elt_bytes, int alg, int* form,
+                    unsigned* span_rows);
+int sm_prune24_check_form(const void* A, const void* d_valid, size_t m, size_t k, size_t ld, size_t elt_bytes, int* form);
+int sm_compress24_form(const void* A, const void* blob, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, size_t elt_bytes,
+                       int* form);
+int sm_decompress24_form(const void* blob, const void* A, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, size_t elt_bytes,
+                         int* form);
+int sm_prune24_compress24_form(const void* A_in, const void* A_out, size_t m, size_t k, size_t ld, size_t batch, size_t strideA,
+                               const void* blob, size_t elt_bytes, int alg, size_t cus, int* form, unsigned* plan);
+
 /* ---- (a2 + a4 without a blob, rounds 4 + 6) the whole call sequence of sparsifyme::spmma() (spmma.hxx:82-113: prune TILE in place,
  *      check, compress, multiply) with NO compressed blob: reads A_in, writes the pruned operand to A_out (A_in itself: in place, what
  *      the reference does; or a second buffer), raises *d_valid (NULL: not wanted; 0 iff every strip written holds <= 2 non-zeros,

@@ -104,6 +104,12 @@ _SIGS["sm_prune24_compress24_bf16"] = _SIGS["sm_prune24_compress24_f16"]
 _SIGS["sm_prune24_spmma_f16"] = [_c_ptr, _c_ptr, _c_ptr, _c_ptr] + [_c_size] * 8 + [_c_i, _c_ptr, _c_f, _c_f, _c_ptr]
 _SIGS["sm_prune24_spmma_bf16"] = _SIGS["sm_prune24_spmma_f16"]
 _SIGS["sm_prune24_compress24_f32"] = _SIGS["sm_prune24_compress24_f16"]
+_SIGS["sm_prune24_form"] = [_c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_size, _c_i, ctypes.POINTER(_c_i), ctypes.POINTER(ctypes.c_uint)]
+_SIGS["sm_prune24_check_form"] = [_c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_size, ctypes.POINTER(_c_i)]
+_SIGS["sm_compress24_form"] = [_c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_size, _c_size, _c_size, ctypes.POINTER(_c_i)]
+_SIGS["sm_decompress24_form"] = _SIGS["sm_compress24_form"]
+_SIGS["sm_prune24_compress24_form"] = [_c_ptr, _c_ptr, _c_size, _c_size, _c_size, _c_size, _c_size, _c_ptr, _c_size, _c_i, _c_size,
+                                       ctypes.POINTER(_c_i), ctypes.POINTER(ctypes.c_uint)]
 _SIGS["sm_conv_spmma_fused_f16"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 10 + [_c_f, _c_f, _c_ptr]
 _SIGS["sm_conv_spmma_fused_bf16"] = _SIGS["sm_conv_spmma_fused_f16"]
 _SIGS["sm_conv_spmma_fused_plan"] = [_c_size] * 10 + [ctypes.c_uint, ctypes.POINTER(_c_i), ctypes.POINTER(ctypes.c_uint)]
@@ -349,6 +355,63 @@ def api_spmma_step_fused(A, Apruned, B, C, blob, d_valid, m, n, k, batch):
 def decompress24(blob, m, k, ld, batch, strideA, A):
     fn = getattr(lib(), "sm_decompress24_" + _sfx(A))
     _check(fn(_dev(blob), m, k, ld, batch, strideA, _dev(A), _stream()), "sm_decompress24")
+
+
+# ---- which kernel a prune / check / compress / decompress / one-pass call runs (include/sparsifyme.h: sm_*_form) ----
+# names of SM_PRUNE24_FORM_*, SM_COMPRESS24_FORM_*, SM_DECOMPRESS24_FORM_* and SM_PRUNE24_COMPRESS24_FORM_*, in order
+PRUNE24_FORMS = ("invalid", "empty", "strip_scalar", "strip_vec", "strip_flat_scalar", "strip_flat_vec", "tile2", "span", "element_scalar",
+                 "element_vec")
+COMPRESS24_FORMS = ("invalid", "empty", "flat", "rowspan", "general_scalar", "general_vec")
+DECOMPRESS24_FORMS = ("invalid", "empty", "scalar", "vec")
+PRUNE24_COMPRESS24_FORMS = ("invalid", "empty", "not_supported", "fallback_tall_span", "fallback_tall", "fallback_per_batch", "onepass_tile",
+                            "onepass_tile_noblob", "onepass_strip")
+
+
+def _addr(x):
+    """An operand of a form query as an address: None, an int (a dummy address: the queries never dereference) or a tensor."""
+    if x is None or isinstance(x, int):
+        return x
+    return x.data_ptr()
+
+
+def prune24_form(A_in, A_out, m, k, ld, elt_bytes, alg=PRUNE_STRIP, with_span_rows=False):
+    """The name (PRUNE24_FORMS) of the kernel class prune24 runs for this call -- sm_prune24_form; operands: tensors or addresses.
+    with_span_rows: (name, rows per span of the span form or 0)."""
+    form, rows = _c_i(-1), ctypes.c_uint(0)
+    _check(lib().sm_prune24_form(_addr(A_in), _addr(A_out), m, k, ld, elt_bytes, alg, ctypes.byref(form), ctypes.byref(rows)), "sm_prune24_form")
+    return (PRUNE24_FORMS[form.value], rows.value) if with_span_rows else PRUNE24_FORMS[form.value]
+
+
+def prune24_check_form(A, d_valid, m, k, ld, elt_bytes):
+    form = _c_i(-1)
+    _check(lib().sm_prune24_check_form(_addr(A), _addr(d_valid), m, k, ld, elt_bytes, ctypes.byref(form)), "sm_prune24_check_form")
+    return PRUNE24_FORMS[form.value]
+
+
+def compress24_form(A, blob, m, k, ld, batch, strideA, elt_bytes):
+    form = _c_i(-1)
+    _check(lib().sm_compress24_form(_addr(A), _addr(blob), m, k, ld, batch, strideA, elt_bytes, ctypes.byref(form)), "sm_compress24_form")
+    return COMPRESS24_FORMS[form.value]
+
+
+def decompress24_form(blob, A, m, k, ld, batch, strideA, elt_bytes):
+    form = _c_i(-1)
+    _check(lib().sm_decompress24_form(_addr(blob), _addr(A), m, k, ld, batch, strideA, elt_bytes, ctypes.byref(form)), "sm_decompress24_form")
+    return DECOMPRESS24_FORMS[form.value]
+
+
+def prune24_compress24_form(A_in, A_out, m, k, ld, batch, strideA, blob, elt_bytes, alg=PRUNE_TILE, cus=0):
+    """(name in PRUNE24_COMPRESS24_FORMS, plan) of a prune24_compress24 call -- sm_prune24_compress24_form.  plan: dict(flat, lpr_log2, nj,
+    grid, capped) for the one-pass kernel, dict(matrices) for the three-launch fallback, {} otherwise.  cus = 0: this device's CU count."""
+    form, plan = _c_i(-1), (ctypes.c_uint * 6)()
+    _check(lib().sm_prune24_compress24_form(_addr(A_in), _addr(A_out), m, k, ld, batch, strideA, _addr(blob), elt_bytes, alg, cus,
+                                            ctypes.byref(form), plan), "sm_prune24_compress24_form")
+    name = PRUNE24_COMPRESS24_FORMS[form.value]
+    if name.startswith("onepass"):
+        return name, dict(flat=bool(plan[0]), lpr_log2=plan[1], nj=plan[2], grid=plan[3], capped=bool(plan[4]))
+    if name.startswith("fallback"):
+        return name, dict(matrices=plan[5])
+    return name, {}
 
 
 BIAS_COL, BIAS_ROW = 0, 1

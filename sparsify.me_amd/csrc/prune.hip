@@ -344,9 +344,11 @@ __global__ __launch_bounds__(256) void prune_tile_span_kernel(const uint16_t* A_
   }
 }
 
-// the span form's launcher: SM_STATUS_NOT_SUPPORTED when the shape is not its (then the element-wise kernel runs)
-int prune24_tile_span_u16(const void* A_in, void* A_out, size_t m, size_t k, size_t ld, bool bf, int* d_valid, hipStream_t st) {
-  if (ld != k || k == 0 || m == 0 || (size_t)8 * k * 2 > 64 * 1024 || !aligned16(A_in) || !aligned16(A_out) || m * k > ((size_t)1 << 40)) return SM_STATUS_NOT_SUPPORTED;
+// Does the span form take this TILE prune, and with how many rows per span?  0: not its shape (then the element-wise kernel runs).  Pure host
+// arithmetic on sizes and pointer VALUES -- the one statement of the condition: prune24_tile_span_u16, prune24_form and prune_fused.hip's
+// prune_compress24_form all ask here.
+unsigned prune24_span_rows(const void* A_in, const void* A_out, size_t m, size_t k, size_t ld) {
+  if (ld != k || k == 0 || m == 0 || (size_t)8 * k * 2 > 64 * 1024 || !aligned16(A_in) || !aligned16(A_out) || m * k > ((size_t)1 << 40)) return 0;
   // rows per span: the multiple of 8 (<= 64, span within 64 KiB) whose tile count fills whole rounds of the workgroup's 256 threads best
   // (k = 147: 37 tiles per tile row -- 32 rows = 296 tiles = two rounds at 58 %; 24 rows = 222 tiles = one round at 87 %)
   const size_t tpr = (k + 3) / 4;
@@ -357,8 +359,15 @@ int prune24_tile_span_u16(const void* A_in, void* A_out, size_t m, size_t k, siz
     const double util = (double)tiles / (double)(ceil_div(tiles, (size_t)256) * 256);
     if (util > best + 1e-9) { best = util; span_rows = r; }
   }
+  if (ceil_div(m, (size_t)span_rows) > 0x7fffffffull) return 0;
+  return span_rows;
+}
+
+// the span form's launcher: SM_STATUS_NOT_SUPPORTED when the shape is not its (prune24_span_rows)
+int prune24_tile_span_u16(const void* A_in, void* A_out, size_t m, size_t k, size_t ld, bool bf, int* d_valid, hipStream_t st) {
+  const unsigned span_rows = prune24_span_rows(A_in, A_out, m, k, ld);
+  if (span_rows == 0) return SM_STATUS_NOT_SUPPORTED;
   const size_t spans = ceil_div(m, (size_t)span_rows), lds = (size_t)span_rows * k * 2;
-  if (spans > 0x7fffffffull) return SM_STATUS_NOT_SUPPORTED;
   if (bf) prune_tile_span_kernel<true><<<(unsigned)spans, 256, lds, st>>>((const uint16_t*)A_in, (uint16_t*)A_out, m, (unsigned)k, d_valid, span_rows);
   else prune_tile_span_kernel<false><<<(unsigned)spans, 256, lds, st>>>((const uint16_t*)A_in, (uint16_t*)A_out, m, (unsigned)k, d_valid, span_rows);
   return check_launch("prune_tile_span_kernel");
@@ -529,8 +538,8 @@ __global__ __launch_bounds__(256) void compress_rowspan_f16_kernel(const uint16_
   extern __shared__ __attribute__((aligned(16))) unsigned char span[];
   const size_t R0 = (size_t)blockIdx.x * 32;
   const unsigned rows = (unsigned)(M - R0 < 32 ? M - R0 : 32);
-  const size_t total = M * ld * 2;                 // bytes of the whole input
-  const size_t b0 = R0 * ld * 2, b1 = (R0 + rows) * ld * 2;
+  const size_t total = ((M - 1) * ld + k) * 2;     // bytes up to the last logical element (ld > k: no padding behind it)
+  const size_t b0 = R0 * ld * 2, b1 = (R0 + rows) * ld * 2 < total ? (R0 + rows) * ld * 2 : total;
   const size_t a0 = b0 & ~(size_t)15;              // A is 16-byte aligned (launcher)
   const unsigned char* src = reinterpret_cast<const unsigned char*>(A);
   for (size_t off = a0 + (size_t)threadIdx.x * 16; off < b1; off += 256 * 16) {
@@ -631,81 +640,151 @@ static int launch_sparsify(void* weights, uint64_t* mask, size_t m, size_t n, si
   return check_launch("sparsify_generic_kernel");
 }
 
-template <typename T>
-static bool vec_ok_2d(const void* a, const void* b, size_t ld, size_t stride) {
-  constexpr size_t per16 = 16 / sizeof(T);
-  // 8 elements are moved as one (f16) or two (f32) 16-byte accesses at element offsets that are
-  // multiples of 8, so rows and batches must start on 16-byte boundaries.
+// ---------------------------------------------------------------------------------------------
+// THE DISPATCH RULES of sm_prune24_*, sm_prune24_check_*, sm_compress24_* and sm_decompress24_* -- each ONE pure host function of the
+// call's sizes, strides, element size and pointer VALUES (never dereferenced) that returns an SM_PRUNE24_FORM_* / SM_COMPRESS24_FORM_* /
+// SM_DECOMPRESS24_FORM_* value: the launchers below switch on it and keep no second copy of a condition, sm_*_form export it (tests
+// named for a kernel assert through it that their call reaches that kernel).
+// ---------------------------------------------------------------------------------------------
+// 8 elements are moved as one (16-bit) or two (fp32) 16-byte accesses at element offsets that are multiples of 8, so rows and batches
+// must start on 16-byte boundaries.
+static bool vec_ok_2d(size_t elt, const void* a, const void* b, size_t ld, size_t stride) {
+  const size_t per16 = 16 / elt;
   return aligned16(a) && aligned16(b) && ld % per16 == 0 && stride % per16 == 0;
+}
+// STRIP prune and the check: one kernel, two flags -- vec (16-byte accesses) and flat (rows back to back: no division per item; the
+// kernel restates `ld == k && k % 8 == 0` itself)
+static int strip_form(size_t elt, const void* a, const void* b, size_t k, size_t ld) {
+  const bool vec = vec_ok_2d(elt, a, b, ld, 0), flat = ld == k && k % 8 == 0;
+  return flat ? (vec ? SM_PRUNE24_FORM_STRIP_FLAT_VEC : SM_PRUNE24_FORM_STRIP_FLAT_SCALAR) : (vec ? SM_PRUNE24_FORM_STRIP_VEC : SM_PRUNE24_FORM_STRIP_SCALAR);
+}
+static int prune24_form(size_t elt, const void* A_in, const void* A_out, size_t m, size_t k, size_t ld, int alg, unsigned* span_rows) {
+  if (span_rows) *span_rows = 0;
+  if (!A_in || !A_out || ld < k || (alg != SM_PRUNE_TILE && alg != SM_PRUNE_STRIP)) return SM_PRUNE24_FORM_INVALID;
+  if (m == 0 || k == 0) return SM_PRUNE24_FORM_EMPTY;
+  if (alg == SM_PRUNE_STRIP) return strip_form(elt, A_in, A_out, k, ld);
+  // 16-bit types are bound by the rule's arithmetic (two tiles per thread with packed adds: 3.76 -> 3.20 ms on the ResNet-50
+  // table); fp32 moves twice the bytes for the same arithmetic and stays on the one-tile kernel (5.1 TB/s)
+  if (elt == 2 && k % 8 == 0 && vec_ok_2d(elt, A_in, A_out, ld, 0)) return SM_PRUNE24_FORM_TILE2;
+  if (elt == 2) {  // (round 6) ragged rows of one contiguous 16-bit matrix: the span form
+    const unsigned r = prune24_span_rows(A_in, A_out, m, k, ld);
+    if (span_rows) *span_rows = r;
+    if (r) return SM_PRUNE24_FORM_SPAN;
+  }
+  // the element-wise kernel moves 4 elements per row access: 8-byte (16-bit) / 16-byte (fp32) alignment
+  const size_t per = 4;
+  const bool vec = (reinterpret_cast<uintptr_t>(A_in) % (per * elt) == 0) && (reinterpret_cast<uintptr_t>(A_out) % (per * elt) == 0) && ld % per == 0;
+  return vec ? SM_PRUNE24_FORM_ELEMENT_VEC : SM_PRUNE24_FORM_ELEMENT_SCALAR;
+}
+static int prune24_check_form(size_t elt, const void* A, const void* d_valid, size_t m, size_t k, size_t ld) {
+  if (!A || !d_valid || ld < k) return SM_PRUNE24_FORM_INVALID;
+  if (m == 0 || k == 0) return SM_PRUNE24_FORM_EMPTY;
+  return strip_form(elt, A, A, k, ld);
+}
+static int compress24_form(size_t elt, const void* A, const void* blob, size_t m, size_t k, size_t ld, size_t batch, size_t strideA) {
+  if (!A || !blob || ld < k || !aligned16(blob)) return SM_COMPRESS24_FORM_INVALID;
+  const BlobLayout L = blob_layout(m, k, elt, batch);
+  if (L.M == 0 || k == 0) return SM_COMPRESS24_FORM_EMPTY;
+  const bool vec_ok = vec_ok_2d(elt, A, A, ld, strideA);
+  const size_t nunits = ceil_div(L.M, (size_t)8) * (L.kc / 64);
+  if (vec_ok && L.kc == k && ld == k && (batch == 1 || strideA == m * ld) && nunits < 0xfffffff0ull) return SM_COMPRESS24_FORM_FLAT;
+  if (elt == 2) {
+    // rows that are not whole 16-byte chunks (or k % 64 != 0), back to back: staged through LDS as one contiguous span
+    const size_t span_bytes = 32 * ld * 2 + 32;
+    if (aligned16(A) && (batch == 1 || strideA == m * ld) && span_bytes <= 48 * 1024 && L.kc / 64 <= 0xffffffu && ceil_div(L.M, (size_t)32) < 0x7fffffffull)
+      return SM_COMPRESS24_FORM_ROWSPAN;
+  }
+  return vec_ok ? SM_COMPRESS24_FORM_GENERAL_VEC : SM_COMPRESS24_FORM_GENERAL_SCALAR;
+}
+static int decompress24_form(size_t elt, const void* blob, const void* A, size_t m, size_t k, size_t ld, size_t batch, size_t strideA) {
+  if (!A || !blob || ld < k) return SM_DECOMPRESS24_FORM_INVALID;
+  if (m * batch == 0 || k == 0) return SM_DECOMPRESS24_FORM_EMPTY;
+  return vec_ok_2d(elt, A, A, ld, strideA) ? SM_DECOMPRESS24_FORM_VEC : SM_DECOMPRESS24_FORM_SCALAR;
 }
 
 template <typename T, bool BF = false>
 static int launch_prune(const void* A_in, void* A_out, size_t m, size_t k, size_t ld, int alg, hipStream_t st) {
-  if (!A_in || !A_out || ld < k || (alg != SM_PRUNE_TILE && alg != SM_PRUNE_STRIP)) {
-    set_error("sm_prune24: invalid argument");
-    return SM_STATUS_INVALID_VALUE;
+  const int form = prune24_form(sizeof(T), A_in, A_out, m, k, ld, alg, nullptr);
+  switch (form) {
+    case SM_PRUNE24_FORM_INVALID:
+      set_error("sm_prune24: invalid argument");
+      return SM_STATUS_INVALID_VALUE;
+    case SM_PRUNE24_FORM_EMPTY:
+      return SM_STATUS_SUCCESS;
+    case SM_PRUNE24_FORM_STRIP_SCALAR:
+    case SM_PRUNE24_FORM_STRIP_VEC:
+    case SM_PRUNE24_FORM_STRIP_FLAT_SCALAR:
+    case SM_PRUNE24_FORM_STRIP_FLAT_VEC: {
+      const bool vec_ok = form == SM_PRUNE24_FORM_STRIP_VEC || form == SM_PRUNE24_FORM_STRIP_FLAT_VEC;
+      prune_strip_kernel<T><<<stream_grid(m * ceil_div(k, 8), 256, true), 256, 0, st>>>((const T*)A_in, (T*)A_out, m, k, ld, vec_ok);
+      return check_launch("prune_strip_kernel");
+    }
+    case SM_PRUNE24_FORM_TILE2:  // (16-bit only: prune24_form never answers it, nor _SPAN, for fp32)
+      if constexpr (sizeof(T) == 2) {
+        prune_tile2_kernel<T, BF><<<stream_grid(ceil_div(m, 4) * (k / 8), 256), 256, 0, st>>>((const T*)A_in, (T*)A_out, m, k, ld);
+        return check_launch("prune_tile2_kernel");
+      } else {
+        set_error("sm_prune24: the two-tile form is 16-bit only");
+        return SM_STATUS_NOT_SUPPORTED;
+      }
+    case SM_PRUNE24_FORM_SPAN:  // (no flag wanted here)
+      if constexpr (sizeof(T) == 2) {
+        return prune24_tile_span_u16(A_in, A_out, m, k, ld, BF, nullptr, st);
+      } else {
+        set_error("sm_prune24: the span form is 16-bit only");
+        return SM_STATUS_NOT_SUPPORTED;
+      }
+    default: {
+      const bool vec_ok = form == SM_PRUNE24_FORM_ELEMENT_VEC;
+      prune_tile_kernel<T, BF><<<stream_grid(ceil_div(m, 4) * ceil_div(k, 4), 256), 256, 0, st>>>((const T*)A_in, (T*)A_out, m, k, ld, vec_ok);
+      return check_launch("prune_tile_kernel");
+    }
   }
-  if (m == 0 || k == 0) return SM_STATUS_SUCCESS;
-  if (alg == SM_PRUNE_STRIP) {
-    const bool vec_ok = vec_ok_2d<T>(A_in, A_out, ld, 0);
-    prune_strip_kernel<T><<<stream_grid(m * ceil_div(k, 8), 256, true), 256, 0, st>>>((const T*)A_in, (T*)A_out, m, k, ld, vec_ok);
-    return check_launch("prune_strip_kernel");
-  }
-  // TILE moves 4 elements per row access: 8-byte (f16) / 16-byte (f32) alignment
-  const size_t per = 4;
-  const bool vec_ok = (reinterpret_cast<uintptr_t>(A_in) % (per * sizeof(T)) == 0) &&
-                      (reinterpret_cast<uintptr_t>(A_out) % (per * sizeof(T)) == 0) && ld % per == 0;
-  // fp16 is bound by the rule's arithmetic (two tiles per thread with packed adds: 3.76 -> 3.20 ms on the ResNet-50
-  // table); fp32 moves twice the bytes for the same arithmetic and stays on the one-tile kernel (5.1 TB/s)
-  if (sizeof(T) == 2 && k % 8 == 0 && vec_ok_2d<T>(A_in, A_out, ld, 0)) {
-    prune_tile2_kernel<T, BF><<<stream_grid(ceil_div(m, 4) * (k / 8), 256), 256, 0, st>>>((const T*)A_in, (T*)A_out, m, k, ld);
-    return check_launch("prune_tile2_kernel");
-  }
-  if (sizeof(T) == 2) {  // (round 6) ragged rows of one contiguous 16-bit matrix: the span form (no flag wanted here)
-    const int rc = prune24_tile_span_u16(A_in, A_out, m, k, ld, BF, nullptr, st);
-    if (rc != SM_STATUS_NOT_SUPPORTED) return rc;
-  }
-  prune_tile_kernel<T, BF><<<stream_grid(ceil_div(m, 4) * ceil_div(k, 4), 256), 256, 0, st>>>((const T*)A_in, (T*)A_out, m, k, ld, vec_ok);
-  return check_launch("prune_tile_kernel");
 }
 
+// the check kernel on one matrix, ORed into *d_valid (no reset of the flag)
 template <typename T>
-static int launch_check(const void* A, size_t m, size_t k, size_t ld, int* d_valid, hipStream_t st) {
-  if (!A || !d_valid || ld < k) {
+static int check_accumulate(const void* A, size_t m, size_t k, size_t ld, int* d_valid, hipStream_t st) {
+  const int form = prune24_check_form(sizeof(T), A, d_valid, m, k, ld);
+  if (form == SM_PRUNE24_FORM_INVALID) {
     set_error("sm_prune24_check: invalid argument");
     return SM_STATUS_INVALID_VALUE;
   }
-  if (hipMemsetAsync(d_valid, 0, sizeof(int), st) != hipSuccess) return check_launch("hipMemsetAsync");
-  if (m == 0 || k == 0) return SM_STATUS_SUCCESS;
-  const bool vec_ok = vec_ok_2d<T>(A, A, ld, 0);
+  if (form == SM_PRUNE24_FORM_EMPTY) return SM_STATUS_SUCCESS;
+  const bool vec_ok = form == SM_PRUNE24_FORM_STRIP_VEC || form == SM_PRUNE24_FORM_STRIP_FLAT_VEC;
   prune_check_kernel<T><<<stream_grid(m * ceil_div(k, 8), 256), 256, 0, st>>>((const T*)A, m, k, ld, vec_ok, d_valid);
   return check_launch("prune_check_kernel");
 }
 
+template <typename T>
+static int launch_check(const void* A, size_t m, size_t k, size_t ld, int* d_valid, hipStream_t st) {
+  if (prune24_check_form(sizeof(T), A, d_valid, m, k, ld) == SM_PRUNE24_FORM_INVALID) {
+    set_error("sm_prune24_check: invalid argument");
+    return SM_STATUS_INVALID_VALUE;
+  }
+  if (hipMemsetAsync(d_valid, 0, sizeof(int), st) != hipSuccess) return check_launch("hipMemsetAsync");
+  return check_accumulate<T>(A, m, k, ld, d_valid, st);
+}
+
 // the check kernel without the reset of the flag (prune_fused.hip: one flag over several batch matrices)
 int prune_check_accumulate_u16(const void* A, size_t m, size_t k, size_t ld, int* d_valid, hipStream_t st) {
-  if (m == 0 || k == 0) return SM_STATUS_SUCCESS;
-  const bool vec_ok = vec_ok_2d<uint16_t>(A, A, ld, 0);
-  prune_check_kernel<uint16_t><<<stream_grid(m * ceil_div(k, 8), 256), 256, 0, st>>>((const uint16_t*)A, m, k, ld, vec_ok, d_valid);
-  return check_launch("prune_check_kernel");
+  return check_accumulate<uint16_t>(A, m, k, ld, d_valid, st);
 }
 
 int prune_check_accumulate_u32(const void* A, size_t m, size_t k, size_t ld, int* d_valid, hipStream_t st) {
-  if (m == 0 || k == 0) return SM_STATUS_SUCCESS;
-  const bool vec_ok = vec_ok_2d<uint32_t>(A, A, ld, 0);
-  prune_check_kernel<uint32_t><<<stream_grid(m * ceil_div(k, 8), 256), 256, 0, st>>>((const uint32_t*)A, m, k, ld, vec_ok, d_valid);
-  return check_launch("prune_check_kernel");
+  return check_accumulate<uint32_t>(A, m, k, ld, d_valid, st);
 }
 
 template <typename T>
 static int launch_compress(const void* A, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, void* blob,
                            hipStream_t st) {
-  if (!A || !blob || ld < k || !aligned16(blob)) {
+  const int form = compress24_form(sizeof(T), A, blob, m, k, ld, batch, strideA);
+  if (form == SM_COMPRESS24_FORM_INVALID) {
     set_error("sm_compress24: invalid argument (blob must be 16-byte aligned)");
     return SM_STATUS_INVALID_VALUE;
   }
+  if (form == SM_COMPRESS24_FORM_EMPTY) return SM_STATUS_SUCCESS;
   const BlobLayout L = blob_layout(m, k, sizeof(T), batch);
-  if (L.M == 0 || k == 0) return SM_STATUS_SUCCESS;
   // zero the alignment gaps so a blob is a pure function of its input
   const size_t vbytes = L.M * (L.kc / 2) * sizeof(T), mbytes = L.M * (L.kc / 8);
   if (L.meta_off > vbytes && hipMemsetAsync((char*)blob + vbytes, 0, L.meta_off - vbytes, st) != hipSuccess)
@@ -713,48 +792,55 @@ static int launch_compress(const void* A, size_t m, size_t k, size_t ld, size_t 
   if (L.total > L.meta_off + mbytes &&
       hipMemsetAsync((char*)blob + L.meta_off + mbytes, 0, L.total - L.meta_off - mbytes, st) != hipSuccess)
     return check_launch("hipMemsetAsync");
-  const bool vec_ok = vec_ok_2d<T>(A, A, ld, strideA);
-  const size_t items = L.M * (L.kc / 8);
-  const size_t nunits = ceil_div(L.M, (size_t)8) * (L.kc / 64);
-  if (vec_ok && L.kc == k && ld == k && (batch == 1 || strideA == m * ld) && nunits < 0xfffffff0ull) {
-    // two loads per lane (8 units per block) measured best on the ResNet-50 table (1.72 ms against 1.85 with 4,
-    // 2.00 with 8, 1.84 with 1: profiles/sweep_r01_i_compress.txt)
-    constexpr int NLD = 2;
-    const unsigned nstage = (unsigned)(L.kc / 64), grid = (unsigned)ceil_div(nunits, (size_t)(4 * NLD));
-    T* v = (T*)blob;
-    unsigned char* mt = (unsigned char*)blob + L.meta_off;
-    compress_flat_kernel<T, true, NLD><<<grid, 256, 0, st>>>((const T*)A, L.M, k, nstage, (unsigned)nunits, v, mt);
-    return check_launch("compress_flat_kernel");
-  }
-  if constexpr (sizeof(T) == 2) {
-    // rows that are not whole 16-byte chunks (or k % 64 != 0), back to back: staged through LDS as one contiguous span
-    const size_t span_bytes = 32 * ld * 2 + 32;
-    if (aligned16(A) && (batch == 1 || strideA == m * ld) && span_bytes <= 48 * 1024 && L.kc / 64 <= 0xffffffu &&
-        ceil_div(L.M, (size_t)32) < 0x7fffffffull) {
-      compress_rowspan_f16_kernel<<<(unsigned)ceil_div(L.M, (size_t)32), 256, span_bytes, st>>>(
-          (const uint16_t*)A, L.M, k, ld, (unsigned)(L.kc / 64), (uint16_t*)blob, (unsigned char*)blob + L.meta_off);
-      return check_launch("compress_rowspan_f16_kernel");
+  switch (form) {
+    case SM_COMPRESS24_FORM_FLAT: {
+      // two loads per lane (8 units per block) measured best on the ResNet-50 table (1.72 ms against 1.85 with 4,
+      // 2.00 with 8, 1.84 with 1: profiles/sweep_r01_i_compress.txt)
+      constexpr int NLD = 2;
+      const size_t nunits = ceil_div(L.M, (size_t)8) * (L.kc / 64);
+      const unsigned nstage = (unsigned)(L.kc / 64), grid = (unsigned)ceil_div(nunits, (size_t)(4 * NLD));
+      T* v = (T*)blob;
+      unsigned char* mt = (unsigned char*)blob + L.meta_off;
+      compress_flat_kernel<T, true, NLD><<<grid, 256, 0, st>>>((const T*)A, L.M, k, nstage, (unsigned)nunits, v, mt);
+      return check_launch("compress_flat_kernel");
+    }
+    case SM_COMPRESS24_FORM_ROWSPAN:
+      if constexpr (sizeof(T) == 2) {
+        const size_t span_bytes = 32 * ld * 2 + 32;
+        compress_rowspan_f16_kernel<<<(unsigned)ceil_div(L.M, (size_t)32), 256, span_bytes, st>>>(
+            (const uint16_t*)A, L.M, k, ld, (unsigned)(L.kc / 64), (uint16_t*)blob, (unsigned char*)blob + L.meta_off);
+        return check_launch("compress_rowspan_f16_kernel");
+      }
+      set_error("sm_compress24: the rowspan form is 16-bit only");  // (compress24_form never answers it for fp32)
+      return SM_STATUS_NOT_SUPPORTED;
+    default: {
+      const bool vec_ok = form == SM_COMPRESS24_FORM_GENERAL_VEC;
+      compress_kernel<T><<<stream_grid(L.M * (L.kc / 8), 256), 256, 0, st>>>((const T*)A, m, k, ld, strideA, L.kc, L.M, (T*)blob,
+                                                                            (unsigned char*)blob + L.meta_off, vec_ok);
+      return check_launch("compress_kernel");
     }
   }
-  const unsigned grid = stream_grid(items, 256);
-  compress_kernel<T><<<grid, 256, 0, st>>>((const T*)A, m, k, ld, strideA, L.kc, L.M, (T*)blob,
-                                           (unsigned char*)blob + L.meta_off, vec_ok);
-  return check_launch("compress_kernel");
 }
 
 template <typename T>
 static int launch_decompress(const void* blob, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, void* A,
                              hipStream_t st) {
-  if (!A || !blob || ld < k) {
+  const int form = decompress24_form(sizeof(T), blob, A, m, k, ld, batch, strideA);
+  if (form == SM_DECOMPRESS24_FORM_INVALID) {
     set_error("sm_decompress24: invalid argument");
     return SM_STATUS_INVALID_VALUE;
   }
+  if (form == SM_DECOMPRESS24_FORM_EMPTY) return SM_STATUS_SUCCESS;
   const BlobLayout L = blob_layout(m, k, sizeof(T), batch);
-  if (L.M == 0 || k == 0) return SM_STATUS_SUCCESS;
-  const bool vec_ok = vec_ok_2d<T>(A, A, ld, strideA);
   decompress_kernel<T><<<stream_grid(L.M * (L.kc / 8), 256), 256, 0, st>>>(
-      (const T*)blob, (const unsigned char*)blob + L.meta_off, m, k, ld, strideA, L.kc, L.M, (T*)A, vec_ok);
+      (const T*)blob, (const unsigned char*)blob + L.meta_off, m, k, ld, strideA, L.kc, L.M, (T*)A, form == SM_DECOMPRESS24_FORM_VEC);
   return check_launch("decompress_kernel");
+}
+
+static bool form_elt_ok(size_t elt_bytes, const void* out, const char* name) {
+  if (out && (elt_bytes == 2 || elt_bytes == 4)) return true;
+  set_error("%s: invalid argument (form == NULL or elt_bytes not 2 or 4)", name);
+  return false;
 }
 
 }  // namespace sm
@@ -834,6 +920,28 @@ int sm_decompress24_f16(const void* blob, size_t m, size_t k, size_t ld, size_t 
 }
 int sm_decompress24_f32(const void* blob, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, float* A, sm_stream_t s) {
   return launch_decompress<uint32_t>(blob, m, k, ld, batch, strideA, A, (hipStream_t)s);
+}
+
+/* ---- the dispatch rules above as host-side queries (include/sparsifyme.h) ---- */
+int sm_prune24_form(const void* A_in, const void* A_out, size_t m, size_t k, size_t ld, size_t elt_bytes, int alg, int* form, unsigned* span_rows) {
+  if (!form_elt_ok(elt_bytes, form, "sm_prune24_form")) return SM_STATUS_INVALID_VALUE;
+  *form = prune24_form(elt_bytes, A_in, A_out, m, k, ld, alg, span_rows);
+  return SM_STATUS_SUCCESS;
+}
+int sm_prune24_check_form(const void* A, const void* d_valid, size_t m, size_t k, size_t ld, size_t elt_bytes, int* form) {
+  if (!form_elt_ok(elt_bytes, form, "sm_prune24_check_form")) return SM_STATUS_INVALID_VALUE;
+  *form = prune24_check_form(elt_bytes, A, d_valid, m, k, ld);
+  return SM_STATUS_SUCCESS;
+}
+int sm_compress24_form(const void* A, const void* blob, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, size_t elt_bytes, int* form) {
+  if (!form_elt_ok(elt_bytes, form, "sm_compress24_form")) return SM_STATUS_INVALID_VALUE;
+  *form = compress24_form(elt_bytes, A, blob, m, k, ld, batch, strideA);
+  return SM_STATUS_SUCCESS;
+}
+int sm_decompress24_form(const void* blob, const void* A, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, size_t elt_bytes, int* form) {
+  if (!form_elt_ok(elt_bytes, form, "sm_decompress24_form")) return SM_STATUS_INVALID_VALUE;
+  *form = decompress24_form(elt_bytes, blob, A, m, k, ld, batch, strideA);
+  return SM_STATUS_SUCCESS;
 }
 
 }  // extern "C"

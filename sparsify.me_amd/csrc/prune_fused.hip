@@ -370,52 +370,123 @@ int prune24_tile_span_u16(const void* A_in, void* A_out, size_t m, size_t k, siz
 }
 extern "C" int sm_compress24_f16(const void*, size_t, size_t, size_t, size_t, size_t, void*, sm_stream_t);
 
-template <bool BF>
-static int prune_compress16(const void* A_in, void* A_out, size_t m, size_t k, size_t ld, size_t batch, size_t strideA,
-                            void* blob, int* d_valid, int alg, sm_stream_t stream) {
-  const char* name = BF ? "sm_prune24_compress24_bf16" : "sm_prune24_compress24_f16";
+namespace sm {
+unsigned prune24_span_rows(const void* A_in, const void* A_out, size_t m, size_t k, size_t ld);  // prune.hip: 0 = the span form does not take it
+}
+
+// ---------------------------------------------------------------------------------------------
+// THE DISPATCH RULE of sm_prune24_compress24_{f16,bf16,f32} -- ONE pure host function of the call's sizes, strides, element size, alg,
+// pointer VALUES (never dereferenced; blob / A_out: null or not, and their alignment) and the CU count: the entry points switch on its
+// answer, sm_prune24_compress24_form exports it.
+// ---------------------------------------------------------------------------------------------
+struct OnePassPick {
+  int form;  // SM_PRUNE24_COMPRESS24_FORM_*
+  // the one-pass kernel's launch (forms _ONEPASS_*)
+  bool flat;      // FLAT instantiation: the batch is one tall matrix (contiguous batches and m % 4 == 0, or batch == 1)
+  unsigned rows, trows, gtr_total, ppr, lpr_log2, nj, grid;
+  bool capped;    // the grid was cut to 8 blocks per CU
+  // the three-launch fallback (forms _FALLBACK_*)
+  size_t nbm, fb_rows;  // matrices the prune / check loops run over, rows of each
+};
+static OnePassPick prune_compress24_form(size_t elt, const void* A_in, const void* A_out, size_t m, size_t k, size_t ld, size_t batch, size_t strideA,
+                                         const void* blob, int alg, size_t cus /*0: this device's*/) {
+  OnePassPick p = {};
   if (!A_in || ld < k || (alg != SM_PRUNE_STRIP && alg != SM_PRUNE_TILE) || (blob && !aligned16(blob))) {
-    set_error("%s: invalid argument", name);
-    return SM_STATUS_INVALID_VALUE;
+    p.form = SM_PRUNE24_COMPRESS24_FORM_INVALID;
+    return p;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (d_valid && hipMemsetAsync(d_valid, 0, sizeof(int), st) != hipSuccess) return check_launch("hipMemsetAsync(d_valid)");
-  if (m == 0 || k == 0 || batch == 0) return SM_STATUS_SUCCESS;
-  const bool fast = k % 64 == 0 && ld % 8 == 0 && strideA % 8 == 0 && aligned16(A_in) && (!A_out || aligned16(A_out)) &&
+  if (m == 0 || k == 0 || batch == 0) {
+    p.form = SM_PRUNE24_COMPRESS24_FORM_EMPTY;
+    return p;
+  }
+  const size_t per16 = 16 / elt;
+  const bool fast = k % 64 == 0 && ld % per16 == 0 && strideA % per16 == 0 && aligned16(A_in) && (!A_out || aligned16(A_out)) &&
                     batch * ceil_div(m, (size_t)4) < 0x3fffffffull && k / 8 < 0xffffffffull && m * batch < 0xfffffff0ull;
   if (!fast) {
     // shapes the one-pass kernel does not take (k % 64 != 0: the 7x7x3 stem layer; unaligned rows): the same three
     // steps as separate launches, per batch matrix (a TILE never straddles two matrices)
-    int rc = SM_STATUS_SUCCESS;
-    const void* src = A_in;
+    if (!A_out && alg == SM_PRUNE_TILE && blob) {
+      p.form = SM_PRUNE24_COMPRESS24_FORM_NOT_SUPPORTED;
+      return p;
+    }
     // the batch as one tall matrix when its matrices are back to back and no TILE can straddle two of them
     const bool tall = batch == 1 || (strideA == m * ld && (alg == SM_PRUNE_STRIP || m % 4 == 0));
-    const size_t nbm = tall ? 1 : batch, rows = tall ? m * batch : m;
-    bool flag_done = false;
-    if (A_out) {
-      // (round 6) TILE on one contiguous matrix with ragged rows (the stem layer, k = 147): the span form prunes AND raises the flag in
-      // one pass -- no separate check pass (the flag is derived from the stored values, as the one-pass kernel derives it)
-      if (alg == SM_PRUNE_TILE && nbm == 1 && prune24_tile_span_u16(A_in, A_out, rows, k, ld, BF, d_valid, st) == SM_STATUS_SUCCESS) {
-        flag_done = true;
-      } else {
-        for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b) {
-          const uint16_t* ai = (const uint16_t*)A_in + b * strideA;
-          uint16_t* ao = (uint16_t*)A_out + b * strideA;
-          rc = BF ? sm_prune24_bf16(ai, ao, rows, k, ld, alg, stream) : sm_prune24_f16(ai, ao, rows, k, ld, alg, stream);
+    p.nbm = tall ? 1 : batch;
+    p.fb_rows = tall ? m * batch : m;
+    // (round 6) TILE on one contiguous 16-bit matrix with ragged rows (the stem layer, k = 147): the span form prunes AND raises the flag in
+    // one pass -- no separate check pass (the flag is derived from the stored values, as the one-pass kernel derives it)
+    if (elt == 2 && A_out && alg == SM_PRUNE_TILE && tall && prune24_span_rows(A_in, A_out, p.fb_rows, k, ld)) p.form = SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL_SPAN;
+    else p.form = tall ? SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL : SM_PRUNE24_COMPRESS24_FORM_FALLBACK_PER_BATCH;
+    return p;
+  }
+  // 16-bit TILE without a blob: the prune + flag pass alone, the blob's re-selection compiled out (the fp32 kernel has no such instantiation)
+  p.form = alg == SM_PRUNE_STRIP ? SM_PRUNE24_COMPRESS24_FORM_ONEPASS_STRIP
+                                 : (elt == 2 && !blob ? SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE_NOBLOB : SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE);
+  p.flat = batch == 1 || (strideA == m * ld && m % 4 == 0);
+  p.rows = (unsigned)(p.flat ? m * batch : 0);
+  p.trows = (unsigned)ceil_div(m, (size_t)4);
+  p.gtr_total = (unsigned)(p.flat ? ceil_div(m * batch, (size_t)4) : batch * p.trows);
+  p.ppr = (unsigned)(k / 8);
+  p.lpr_log2 = 3;  // k % 64 == 0: ppr is a multiple of 8
+  while (p.lpr_log2 < 6 && p.ppr % (2u << p.lpr_log2) == 0) ++p.lpr_log2;
+  p.nj = p.ppr >> p.lpr_log2;
+  const size_t wave_units = ceil_div((size_t)p.gtr_total, (size_t)(64u >> p.lpr_log2));
+  size_t blocks = ceil_div(wave_units, (size_t)4);
+  const size_t cap = (cus ? cus : (size_t)device_cu_count()) * 8;  // 2 blocks per SIMD: the kernel holds ~3 waves per SIMD
+  p.capped = blocks > cap;
+  if (p.capped) blocks = cap;
+  p.grid = (unsigned)(blocks ? blocks : 1);
+  return p;
+}
+
+template <bool BF>
+static int prune_compress16(const void* A_in, void* A_out, size_t m, size_t k, size_t ld, size_t batch, size_t strideA,
+                            void* blob, int* d_valid, int alg, sm_stream_t stream) {
+  const char* name = BF ? "sm_prune24_compress24_bf16" : "sm_prune24_compress24_f16";
+  const OnePassPick pick = prune_compress24_form(2, A_in, A_out, m, k, ld, batch, strideA, blob, alg, 0);
+  if (pick.form == SM_PRUNE24_COMPRESS24_FORM_INVALID) {
+    set_error("%s: invalid argument", name);
+    return SM_STATUS_INVALID_VALUE;
+  }
+  if (pick.form == SM_PRUNE24_COMPRESS24_FORM_NOT_SUPPORTED) {  // decided before anything is touched, the flag word included
+    set_error("%s: TILE + blob without A_out needs k %% 64 == 0 and 16-byte aligned rows", name);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (d_valid && hipMemsetAsync(d_valid, 0, sizeof(int), st) != hipSuccess) return check_launch("hipMemsetAsync(d_valid)");
+  switch (pick.form) {
+    case SM_PRUNE24_COMPRESS24_FORM_EMPTY:
+      return SM_STATUS_SUCCESS;
+    case SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL_SPAN:
+    case SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL:
+    case SM_PRUNE24_COMPRESS24_FORM_FALLBACK_PER_BATCH: {
+      int rc = SM_STATUS_SUCCESS;
+      const void* src = A_in;
+      const size_t nbm = pick.nbm, rows = pick.fb_rows;
+      bool flag_done = false;
+      if (A_out) {
+        if (pick.form == SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL_SPAN) {
+          rc = prune24_tile_span_u16(A_in, A_out, rows, k, ld, BF, d_valid, st);
+          flag_done = true;
+        } else {
+          for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b) {
+            const uint16_t* ai = (const uint16_t*)A_in + b * strideA;
+            uint16_t* ao = (uint16_t*)A_out + b * strideA;
+            rc = BF ? sm_prune24_bf16(ai, ao, rows, k, ld, alg, stream) : sm_prune24_f16(ai, ao, rows, k, ld, alg, stream);
+          }
         }
+        src = A_out;
       }
-      src = A_out;
-    } else if (alg == SM_PRUNE_TILE && blob) {
-      set_error("%s: TILE + blob without A_out needs k %% 64 == 0 and 16-byte aligned rows", name);
-      return SM_STATUS_NOT_SUPPORTED;
+      if (rc == SM_STATUS_SUCCESS && d_valid && A_out && !flag_done) {
+        // the flag of every batch matrix is OR-ed into *d_valid (zeroed above)
+        for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b)
+          rc = prune_check_accumulate_u16((const uint16_t*)A_out + b * strideA, rows, k, ld, d_valid, st);
+      }
+      if (rc == SM_STATUS_SUCCESS && blob) rc = sm_compress24_f16(src, m, k, ld, batch, strideA, blob, stream);
+      return rc;
     }
-    if (rc == SM_STATUS_SUCCESS && d_valid && A_out && !flag_done) {
-      // the flag of every batch matrix is OR-ed into *d_valid (zeroed above)
-      for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b)
-        rc = prune_check_accumulate_u16((const uint16_t*)A_out + b * strideA, rows, k, ld, d_valid, st);
-    }
-    if (rc == SM_STATUS_SUCCESS && blob) rc = sm_compress24_f16(src, m, k, ld, batch, strideA, blob, stream);
-    return rc;
+    default:
+      break;
   }
   const BlobLayout L = blob_layout(m, k, 2, batch);
   if (blob) {  // zero the alignment gaps so a blob is a pure function of its input (as sm_compress24_*)
@@ -433,27 +504,22 @@ static int prune_compress16(const void* A_in, void* A_out, size_t m, size_t k, s
   a.meta = blob ? (unsigned char*)blob + L.meta_off : nullptr;
   a.d_valid = d_valid;
   a.m = m; a.ld = ld; a.strideA = strideA; a.M = L.M;
-  const bool flat = batch == 1 || (strideA == m * ld && m % 4 == 0);
-  a.rows = (unsigned)(flat ? m * batch : 0);
-  a.trows = (unsigned)ceil_div(m, (size_t)4);
-  a.gtr_total = (unsigned)(flat ? ceil_div(m * batch, (size_t)4) : batch * a.trows);
-  a.ppr = (unsigned)(k / 8);
-  a.lpr_log2 = 3;  // k % 64 == 0: ppr is a multiple of 8
-  while (a.lpr_log2 < 6 && a.ppr % (2u << a.lpr_log2) == 0) ++a.lpr_log2;
-  const size_t wave_units = ceil_div((size_t)a.gtr_total, (size_t)(64u >> a.lpr_log2));
-  size_t blocks = ceil_div(wave_units, (size_t)4);
-  const size_t cap = (size_t)device_cu_count() * 8;  // 2 blocks per SIMD: the kernel holds ~3 waves per SIMD
-  if (blocks > cap) blocks = cap;
-  const unsigned grid = (unsigned)(blocks ? blocks : 1);
-  if (alg == SM_PRUNE_TILE && !blob) {  // the prune + flag pass alone (no blob wanted): the blob's re-selection compiled out
-    if (flat) prune_compress_kernel<BF, true, true, false><<<grid, 256, 0, st>>>(a);
-    else prune_compress_kernel<BF, true, false, false><<<grid, 256, 0, st>>>(a);
-  } else if (alg == SM_PRUNE_TILE) {
-    if (flat) prune_compress_kernel<BF, true, true><<<grid, 256, 0, st>>>(a);
-    else prune_compress_kernel<BF, true, false><<<grid, 256, 0, st>>>(a);
-  } else {
-    if (flat) prune_compress_kernel<BF, false, true><<<grid, 256, 0, st>>>(a);
-    else prune_compress_kernel<BF, false, false><<<grid, 256, 0, st>>>(a);
+  a.rows = pick.rows; a.trows = pick.trows; a.gtr_total = pick.gtr_total; a.ppr = pick.ppr; a.lpr_log2 = pick.lpr_log2;
+  const unsigned grid = pick.grid;
+  const bool flat = pick.flat;
+  switch (pick.form) {
+    case SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE_NOBLOB:
+      if (flat) prune_compress_kernel<BF, true, true, false><<<grid, 256, 0, st>>>(a);
+      else prune_compress_kernel<BF, true, false, false><<<grid, 256, 0, st>>>(a);
+      break;
+    case SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE:
+      if (flat) prune_compress_kernel<BF, true, true><<<grid, 256, 0, st>>>(a);
+      else prune_compress_kernel<BF, true, false><<<grid, 256, 0, st>>>(a);
+      break;
+    default:
+      if (flat) prune_compress_kernel<BF, false, true><<<grid, 256, 0, st>>>(a);
+      else prune_compress_kernel<BF, false, false><<<grid, 256, 0, st>>>(a);
+      break;
   }
   return check_launch("prune_compress_kernel");
 }
@@ -477,31 +543,36 @@ int prune_check_accumulate_u32(const void* A, size_t m, size_t k, size_t ld, int
 extern "C" int sm_prune24_compress24_f32(const float* A_in, float* A_out, size_t m, size_t k, size_t ld, size_t batch, size_t strideA,
                                          void* blob, int* d_valid, int alg, sm_stream_t stream) {
   const char* name = "sm_prune24_compress24_f32";
-  if (!A_in || ld < k || (alg != SM_PRUNE_STRIP && alg != SM_PRUNE_TILE) || (blob && !aligned16(blob))) {
+  const OnePassPick pick = prune_compress24_form(4, A_in, A_out, m, k, ld, batch, strideA, blob, alg, 0);
+  if (pick.form == SM_PRUNE24_COMPRESS24_FORM_INVALID) {
     set_error("%s: invalid argument", name);
     return SM_STATUS_INVALID_VALUE;
   }
+  if (pick.form == SM_PRUNE24_COMPRESS24_FORM_NOT_SUPPORTED) {  // decided before anything is touched, the flag word included
+    set_error("%s: TILE + blob without A_out needs k %% 64 == 0 and 16-byte aligned rows", name);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
   hipStream_t st = (hipStream_t)stream;
   if (d_valid && hipMemsetAsync(d_valid, 0, sizeof(int), st) != hipSuccess) return check_launch("hipMemsetAsync(d_valid)");
-  if (m == 0 || k == 0 || batch == 0) return SM_STATUS_SUCCESS;
-  const bool fast = k % 64 == 0 && ld % 4 == 0 && strideA % 4 == 0 && aligned16(A_in) && (!A_out || aligned16(A_out)) &&
-                    batch * ceil_div(m, (size_t)4) < 0x3fffffffull && k / 8 < 0xffffffffull && m * batch < 0xfffffff0ull;
-  if (!fast) {  // the same three steps as separate launches (k % 64 != 0, unaligned rows)
-    int rc = SM_STATUS_SUCCESS;
-    const float* src = A_in;
-    const bool tall = batch == 1 || (strideA == m * ld && (alg == SM_PRUNE_STRIP || m % 4 == 0));
-    const size_t nbm = tall ? 1 : batch, rows = tall ? m * batch : m;
-    if (A_out) {
-      for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b) rc = sm_prune24_f32(A_in + b * strideA, A_out + b * strideA, rows, k, ld, alg, stream);
-      src = A_out;
-    } else if (alg == SM_PRUNE_TILE && blob) {
-      set_error("%s: TILE + blob without A_out needs k %% 64 == 0 and 16-byte aligned rows", name);
-      return SM_STATUS_NOT_SUPPORTED;
+  switch (pick.form) {
+    case SM_PRUNE24_COMPRESS24_FORM_EMPTY:
+      return SM_STATUS_SUCCESS;
+    case SM_PRUNE24_COMPRESS24_FORM_FALLBACK_TALL:
+    case SM_PRUNE24_COMPRESS24_FORM_FALLBACK_PER_BATCH: {  // the same three steps as separate launches (k % 64 != 0, unaligned rows)
+      int rc = SM_STATUS_SUCCESS;
+      const float* src = A_in;
+      const size_t nbm = pick.nbm, rows = pick.fb_rows;
+      if (A_out) {
+        for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b) rc = sm_prune24_f32(A_in + b * strideA, A_out + b * strideA, rows, k, ld, alg, stream);
+        src = A_out;
+      }
+      if (rc == SM_STATUS_SUCCESS && d_valid && A_out)
+        for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b) rc = prune_check_accumulate_u32(A_out + b * strideA, rows, k, ld, d_valid, st);
+      if (rc == SM_STATUS_SUCCESS && blob) rc = sm_compress24_f32(src, m, k, ld, batch, strideA, blob, stream);
+      return rc;
     }
-    if (rc == SM_STATUS_SUCCESS && d_valid && A_out)
-      for (size_t b = 0; b < nbm && rc == SM_STATUS_SUCCESS; ++b) rc = prune_check_accumulate_u32(A_out + b * strideA, rows, k, ld, d_valid, st);
-    if (rc == SM_STATUS_SUCCESS && blob) rc = sm_compress24_f32(src, m, k, ld, batch, strideA, blob, stream);
-    return rc;
+    default:
+      break;
   }
   const BlobLayout L = blob_layout(m, k, 4, batch);
   if (blob) {
@@ -517,24 +588,34 @@ extern "C" int sm_prune24_compress24_f32(const float* A_in, float* A_out, size_t
   a.meta = blob ? (unsigned char*)blob + L.meta_off : nullptr;
   a.d_valid = d_valid;
   a.m = m; a.ld = ld; a.strideA = strideA; a.M = L.M;
-  const bool flat = batch == 1 || (strideA == m * ld && m % 4 == 0);
-  a.rows = (unsigned)(flat ? m * batch : 0);
-  a.trows = (unsigned)ceil_div(m, (size_t)4);
-  a.gtr_total = (unsigned)(flat ? ceil_div(m * batch, (size_t)4) : batch * a.trows);
-  a.ppr = (unsigned)(k / 8);
-  a.lpr_log2 = 3;
-  while (a.lpr_log2 < 6 && a.ppr % (2u << a.lpr_log2) == 0) ++a.lpr_log2;
-  const size_t wave_units = ceil_div((size_t)a.gtr_total, (size_t)(64u >> a.lpr_log2));
-  size_t blocks = ceil_div(wave_units, (size_t)4);
-  const size_t cap = (size_t)device_cu_count() * 8;
-  if (blocks > cap) blocks = cap;
-  const unsigned grid = (unsigned)(blocks ? blocks : 1);
-  if (alg == SM_PRUNE_TILE) {
-    if (flat) prune_compress_f32_kernel<true, true><<<grid, 256, 0, st>>>(a);
+  a.rows = pick.rows; a.trows = pick.trows; a.gtr_total = pick.gtr_total; a.ppr = pick.ppr; a.lpr_log2 = pick.lpr_log2;
+  const unsigned grid = pick.grid;
+  if (pick.form == SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE) {
+    if (pick.flat) prune_compress_f32_kernel<true, true><<<grid, 256, 0, st>>>(a);
     else prune_compress_f32_kernel<true, false><<<grid, 256, 0, st>>>(a);
   } else {
-    if (flat) prune_compress_f32_kernel<false, true><<<grid, 256, 0, st>>>(a);
+    if (pick.flat) prune_compress_f32_kernel<false, true><<<grid, 256, 0, st>>>(a);
     else prune_compress_f32_kernel<false, false><<<grid, 256, 0, st>>>(a);
   }
   return check_launch("prune_compress_f32_kernel");
+}
+
+extern "C" int sm_prune24_compress24_form(const void* A_in, const void* A_out, size_t m, size_t k, size_t ld, size_t batch, size_t strideA, const void* blob,
+                                          size_t elt_bytes, int alg, size_t cus, int* form, unsigned* plan) {
+  if (!form || (elt_bytes != 2 && elt_bytes != 4)) {
+    set_error("sm_prune24_compress24_form: invalid argument (form == NULL or elt_bytes not 2 or 4)");
+    return SM_STATUS_INVALID_VALUE;
+  }
+  const OnePassPick p = prune_compress24_form(elt_bytes, A_in, A_out, m, k, ld, batch, strideA, blob, alg, cus);
+  *form = p.form;
+  if (plan) {
+    const bool one = p.form >= SM_PRUNE24_COMPRESS24_FORM_ONEPASS_TILE;
+    plan[0] = one ? (p.flat ? 1u : 0u) : 0u;
+    plan[1] = one ? p.lpr_log2 : 0u;
+    plan[2] = one ? p.nj : 0u;
+    plan[3] = one ? p.grid : 0u;
+    plan[4] = one ? (p.capped ? 1u : 0u) : 0u;
+    plan[5] = one ? 0u : (unsigned)(p.nbm > 0xffffffffull ? 0xffffffffull : p.nbm);
+  }
+  return SM_STATUS_SUCCESS;
 }

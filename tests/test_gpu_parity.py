@@ -85,9 +85,12 @@ def test_sparsify_positional_generic_block_and_unaligned(gpu, orc):
 # ---------------------------------------------------------------------------------------------
 PRUNE_SHAPES = [(1, 4, 4), (4, 4, 4), (3, 5, 5), (7, 147, 147), (10, 147, 152), (16, 64, 64), (33, 72, 80),
                 (196, 512, 512), (784, 1024, 1024), (130, 260, 264), (5, 3, 3), (257, 8, 8),
-                # round 6: the span form of TILE (16-bit types, ld == k, ragged rows): several 32-row spans, a short last span that ends off a
-                # 16-byte boundary, m % 4 != 0, k % 4 != 0, the widest k whose span still fits (1022) and one beyond it (element-wise kernel)
+                # round 6: the span form of TILE (16-bit types, ld == k, ragged rows): several spans, a short last span that ends off a
+                # 16-byte boundary, m % 4 != 0, k % 4 != 0, and two wide rows -- 1022 and 1026 BOTH run the span form (it takes every k <= 4096
+                # and picks 8 to 64 rows per span; the element-wise kernel on contiguous ragged rows is tests/test_gpu_prune_classes.py's, k = 4097)
                 (129, 147, 147), (100, 30, 30), (64, 1022, 1022), (40, 1026, 1026), (3136, 147, 147)]
+# the kernel class (sm_prune24_form) of the rows above whose comment names one: TILE on fp16 (fp32 has no span form: element-wise, ld odd)
+PRUNE_SHAPE_FORMS = {(129, 147, 147): "span", (100, 30, 30): "span", (64, 1022, 1022): "span", (40, 1026, 1026): "span", (3136, 147, 147): "span"}
 
 
 @pytest.mark.parametrize("dtype", [np.float16, np.float32])
@@ -103,6 +106,9 @@ def test_prune24(gpu, orc, dtype, alg, shape, kind):
     dA = to_dev(A)
     dOut = torch.zeros_like(dA)
     dOut.copy_(dA)  # padding columns must stay as they are
+    if shape in PRUNE_SHAPE_FORMS and alg == 0:
+        want_form = PRUNE_SHAPE_FORMS[shape] if dtype == np.float16 else ("element_vec" if ld % 4 == 0 else "element_scalar")
+        assert gpu.prune24_form(dA, dOut, m, k, ld, A.itemsize, alg) == want_form, f"{shape} reaches another kernel"
     gpu.prune24(dA, dOut, m, k, ld, alg)
     assert np.array_equal(bits(host(dOut)), want), "out-of-place prune differs from the oracle"
     gpu.prune24(dA, dA, m, k, ld, alg)  # in place, as spmma.hxx:86 does
