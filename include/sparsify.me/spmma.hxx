@@ -86,6 +86,14 @@ struct spmma_fns_f16 {
                            std::size_t ldy, int act, const float* bias, hipStream_t st) {
     return sm_linear24_glu_f16(blob, X, Y, tokens, hidden, in, ldx, ldy, act, bias, st);
   }
+  static int linear_grouped_on(const void* blob, const void* X, void* Y, const int* off, std::size_t groups, std::size_t tokens, std::size_t out,
+                               std::size_t in, std::size_t ldx, std::size_t ldy, float al, float be, const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_linear24_grouped_f16(blob, X, Y, off, groups, tokens, out, in, ldx, ldy, al, be, ep, st);
+  }
+  static int linear_glu_grouped_on(const void* blob, const void* X, void* Y, const int* off, std::size_t groups, std::size_t tokens, std::size_t hidden,
+                                   std::size_t in, std::size_t ldx, std::size_t ldy, int act, const float* bias, hipStream_t st) {
+    return sm_linear24_grouped_glu_f16(blob, X, Y, off, groups, tokens, hidden, in, ldx, ldy, act, bias, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -134,6 +142,14 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
   static int linear_glu_on(const void* blob, const void* X, void* Y, std::size_t tokens, std::size_t hidden, std::size_t in, std::size_t ldx,
                            std::size_t ldy, int act, const float* bias, hipStream_t st) {
     return sm_linear24_glu_bf16(blob, X, Y, tokens, hidden, in, ldx, ldy, act, bias, st);
+  }
+  static int linear_grouped_on(const void* blob, const void* X, void* Y, const int* off, std::size_t groups, std::size_t tokens, std::size_t out,
+                               std::size_t in, std::size_t ldx, std::size_t ldy, float al, float be, const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_linear24_grouped_bf16(blob, X, Y, off, groups, tokens, out, in, ldx, ldy, al, be, ep, st);
+  }
+  static int linear_glu_grouped_on(const void* blob, const void* X, void* Y, const int* off, std::size_t groups, std::size_t tokens, std::size_t hidden,
+                                   std::size_t in, std::size_t ldx, std::size_t ldy, int act, const float* bias, hipStream_t st) {
+    return sm_linear24_grouped_glu_bf16(blob, X, Y, off, groups, tokens, hidden, in, ldx, ldy, act, bias, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -511,6 +527,38 @@ class spmma_plan_t {
     using fns = detail::spmma_fns<type_t>;
     if (!ready_ || batch_ != 1 || m_ % 2 != 0) return SM_STATUS_INVALID_VALUE;
     return fns::linear_glu_on(blob_.data().get(), dX, dY, tokens, m_ / 2, k_, ldx ? ldx : k_, ldy ? ldy : m_ / 2, act, bias, stream);
+  }
+
+  // Extension (fp16 / bfloat16, a plan of batch_size 1 whose m is groups * out): the operand as the STACKED weights of `groups` experts
+  // of one shape, expert g in rows g * out .. (g + 1) * out - 1 -- every expert's linear layer on its own tokens in one launch
+  // (sm_linear24_grouped_*).  The tokens of X and Y are sorted by expert; d_offsets: groups + 1 int32 values in DEVICE memory, expert g
+  // owns token rows [d_offsets[g], d_offsets[g + 1]); they are read on the device only.  ldx / ldy: 0 = k / out.
+  int linear_grouped(type_t* dX, type_t* dY, const int* d_offsets, std::size_t groups, std::size_t tokens, float alpha = 1.0f, float beta = 0.0f,
+                     hipStream_t stream = nullptr, std::size_t ldx = 0, std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1 || groups == 0 || m_ % groups != 0) return SM_STATUS_INVALID_VALUE;
+    const std::size_t out = m_ / groups;
+    return fns::linear_grouped_on(blob_.data().get(), dX, dY, d_offsets, groups, tokens, out, k_, ldx ? ldx : k_, ldy ? ldy : out, alpha, beta, nullptr,
+                                  stream);
+  }
+  // the same with an epilogue: an SM_BIAS_COL bias holds m values (expert-major), an SM_BIAS_ROW bias and the residual are in Y's rows
+  int linear_grouped(type_t* dX, type_t* dY, const int* d_offsets, std::size_t groups, std::size_t tokens, const spmma_epilogue_t& epilogue,
+                     float alpha = 1.0f, float beta = 0.0f, hipStream_t stream = nullptr, std::size_t ldx = 0, std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1 || groups == 0 || m_ % groups != 0) return SM_STATUS_INVALID_VALUE;
+    const std::size_t out = m_ / groups;
+    const sm_epilogue_t e = epilogue.c_struct(dY, tokens, out, beta);
+    return fns::linear_grouped_on(blob_.data().get(), dX, dY, d_offsets, groups, tokens, out, k_, ldx ? ldx : k_, ldy ? ldy : out, alpha, beta, &e, stream);
+  }
+  // ... and the gated form (m = groups * 2 * hidden: each expert's gate rows followed by its up rows): Y[tokens][hidden] = act(gate) * up
+  // per expert in one launch (sm_linear24_grouped_glu_*).  bias: m fp32 device values in the blob's row order, or null; ldy: 0 = hidden.
+  int linear_glu_grouped(type_t* dX, type_t* dY, const int* d_offsets, std::size_t groups, std::size_t tokens, int act = SM_GLU_ACT_SILU,
+                         const float* bias = nullptr, hipStream_t stream = nullptr, std::size_t ldx = 0, std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1 || groups == 0 || m_ % (2 * groups) != 0) return SM_STATUS_INVALID_VALUE;
+    const std::size_t hidden = m_ / (2 * groups);
+    return fns::linear_glu_grouped_on(blob_.data().get(), dX, dY, d_offsets, groups, tokens, hidden, k_, ldx ? ldx : k_, ldy ? ldy : hidden, act, bias,
+                                      stream);
   }
 
  private:

@@ -523,6 +523,66 @@ int sm_linear24_glu_fp8(const void* blob, const void* X, void* Y, size_t tokens,
                         sm_stream_t stream);
 int sm_linear24_glu_form(size_t tokens, size_t hidden, size_t in_features, size_t cus, int* form);
 
+/* ---- The GROUPED forms of the token-major layers (extension): `groups` experts of ONE shape behind one launch -- the feed-forward
+ *      block of a mixture-of-experts layer, whose per-expert token counts exist only on the device (they are the router's output).
+ *
+ *          for g in 0 .. groups-1, t in [lo_g, hi_g):   Y[t] = sm_linear24_*( blob of expert g, X[t] )      (plain or gated)
+ *
+ *      blob     the UNCHANGED output of sm_compress24_* / sm_prune24_compress24_* / sm_quantize_compress24_fp8_* for the stacked weight
+ *               W[groups * out_features][in_features] (m = groups * out_features, or m = out_features with batch = groups: the same
+ *               bytes).  Gated: W[groups][2 * hidden][in_features], each expert's gate rows followed by its up rows.
+ *      X, Y     what the plain layers take: row-major, `tokens` rows, ldx / ldy; the tokens sorted by group.
+ *      group_offsets  groups + 1 int32 values in DEVICE memory, read on the device only (the call never copies them to the host, so a
+ *               captured graph stays valid when the routing changes).  Group g owns token rows [lo_g, hi_g),
+ *               lo_g = clamp(off[g], 0, tokens), hi_g = clamp(off[g + 1], lo_g, tokens).  Whatever the array holds, no byte outside the
+ *               `tokens` rows of X and Y (and R) and outside the blob is touched.  Rows of Y no group owns are not written.  Ranges that
+ *               overlap because the offsets decrease give unspecified values in the overlap (the kernels hand the overlap to the
+ *               earlier group); nothing else is affected.
+ *      Per-out-feature vectors (an SM_BIAS_COL bias, w_scale): groups * out_features floats, expert-major; gated: groups * 2 * hidden,
+ *      each expert's gate values then its up values.  Per-token vectors (an SM_BIAS_ROW bias, x_scale) and R: in Y's global rows.
+ *      Arithmetic: the plain layer's own.  Group g's rows of Y have the bits sm_linear24_* (sm_linear24_glu_*) gives on that slice of
+ *      X with expert g's own blob in a TILE form: the same K order, the one rounding, the same epilogue order (the kernels are the
+ *      plain layers' tile kernels, GROUPED instantiations).  The same bits on every run.
+ *      Forms    sm_linear24_grouped_form(tokens, groups, out_features, in_features, cus) is the one rule every grouped entry point
+ *               switches on (16-bit with cus = 256, fp8 with the device's; cus = 0: the device's; gated: asked with
+ *               out_features = 2 * hidden).  Never DECODE.  With mean = ceil(tokens / groups):
+ *                 TILE128      mean > 64 and ceil(out / 128) * ceil(tokens / 128) >= cus
+ *                 TILE128x64   else, when ceil(out / 128) * ceil(tokens / 64) >= cus
+ *                 TILE64       else
+ *                 NOT_TAKEN / EMPTY as in the statuses below.
+ *               The thresholds are the plain rule's, carried over, NOT measured for the grouped launch.  The grid is tiles_m * slots
+ *               workgroups, slots = min(tokens, ceil(tokens / BN) + groups - 1): an upper bound on sum_g ceil(count_g / BN) for every
+ *               distribution (a non-empty group has ceil(c / BN) = floor((c - 1) / BN) + 1, so n non-empty groups of T tokens in all
+ *               need <= floor((T - n) / BN) + n <= ceil(T / BN) + groups - 1 tiles; and ceil(c / BN) <= c).  A workgroup finds its
+ *               group by walking group_offsets (scalar loads, at most 2 * groups of them); the real tiles run group by group in the
+ *               plain layer's order, and a workgroup beyond the last real tile returns at once.  NOT_TAKEN's grid limit is read on
+ *               this product.
+ *      Status, decided before any device work, in this order: invalid epilogue (gated: act not SM_GLU_ACT_*): SM_STATUS_INVALID_VALUE;
+ *      null blob / X / Y / group_offsets, blob not 16-byte aligned, (fp8: fmt / out_type unknown,) ldx < in_features,
+ *      ldy < out_features: SM_STATUS_INVALID_VALUE; a dimension >= 2^31, groups > SM_LINEAR24_MAX_GROUPS, groups * out_features (gated:
+ *      groups * 2 * hidden) > 2^31 - 1, a grid beyond 2^31 - 1 workgroups: SM_STATUS_NOT_SUPPORTED; in_features % 64 != 0, X rows not
+ *      16-byte aligned: SM_STATUS_NOT_SUPPORTED; tokens == 0, out_features == 0 or groups == 0: success, nothing enqueued.
+ *      Enqueue only: no allocation, no synchronisation, no workspace, no memset node; capturable into a hipGraph.
+ *      Not covered: a grouped decode form (few tokens per expert run the 64 x 64 tile form: DESIGN.md 8), a per-token gather / scatter
+ *      index (un-permuted tokens), a top-k combine weight on the 16-bit path, experts of differing shapes, an fp8-quantised Y; the
+ *      plain layers' rules and kernels are unchanged. */
+#define SM_LINEAR24_MAX_GROUPS 1024
+int sm_linear24_grouped_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t out_features,
+                            size_t in_features, size_t ldx, size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_linear24_grouped_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t out_features,
+                             size_t in_features, size_t ldx, size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_linear24_grouped_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t out_features,
+                            size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, float alpha, float beta,
+                            const float* w_scale, const float* x_scale, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_linear24_grouped_glu_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
+                                size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream);
+int sm_linear24_grouped_glu_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
+                                 size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream);
+int sm_linear24_grouped_glu_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
+                                size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, int act, const float* w_scale,
+                                const float* x_scale, const float* bias, sm_stream_t stream);
+int sm_linear24_grouped_form(size_t tokens, size_t groups, size_t out_features, size_t in_features, size_t cus, int* form);
+
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +
  * sm_spmma_f32 to fp32 accumulation order.  Needs k % 32 == 0, n % 4 == 0, 16-byte aligned rows. */

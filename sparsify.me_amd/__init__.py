@@ -177,6 +177,11 @@ for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_linear24_glu_" + _sfx16] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_i, _c_ptr, _c_ptr]
 _SIGS["sm_linear24_glu_fp8"] = [_c_ptr, _c_ptr, _c_ptr] + [_c_size] * 5 + [_c_i, _c_i, _c_i, _c_i, _c_ptr, _c_ptr, _c_ptr, _c_ptr]
 _SIGS["sm_linear24_glu_form"] = [_c_size] * 4 + [ctypes.POINTER(_c_i)]
+# the grouped (per-expert) forms: the plain signatures with (group_offsets, groups) in front of tokens
+for _sfx16 in ("f16", "bf16", "fp8"):
+    _SIGS["sm_linear24_grouped_" + _sfx16] = _SIGS["sm_linear24_" + _sfx16][:3] + [_c_ptr, _c_size] + _SIGS["sm_linear24_" + _sfx16][3:]
+    _SIGS["sm_linear24_grouped_glu_" + _sfx16] = _SIGS["sm_linear24_glu_" + _sfx16][:3] + [_c_ptr, _c_size] + _SIGS["sm_linear24_glu_" + _sfx16][3:]
+_SIGS["sm_linear24_grouped_form"] = [_c_size] * 5 + [ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -581,6 +586,93 @@ def linear24_glu_form(tokens, hidden, in_features, cus=0):
     on 2 * hidden rows.  linear24_glu_fp8 asks with this device's compute units (cus=0), linear24_glu with cus=256."""
     form = _c_i(-1)
     _check(lib().sm_linear24_glu_form(tokens, hidden, in_features, cus, ctypes.byref(form)), "sm_linear24_glu_form")
+    return LINEAR24_FORMS[form.value]
+
+
+# include/sparsifyme.h: SM_LINEAR24_MAX_GROUPS
+LINEAR24_MAX_GROUPS = 1024
+
+
+def _group_offsets(group_offsets, what):
+    if group_offsets.dtype != _t().int32:
+        raise SparsifymeError(f"{what}: group_offsets is int32, not {group_offsets.dtype}")
+    return _dev(group_offsets)
+
+
+def linear24_grouped(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, ldx=None, ldy=None, alpha=1.0, beta=0.0,
+                     epilogue=None):
+    """linear24 per expert in one launch (sm_linear24_grouped_*): blob is that of the stacked W[groups * out][in], the tokens of X
+    and Y are sorted by expert, and group_offsets (groups + 1 int32 values on the device, never copied to the host) says where each
+    expert's rows begin.  A "col" bias holds groups * out values, expert-major; a "row" bias and the residual are in Y's rows."""
+    torch = _t()
+    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
+        raise SparsifymeError(f"linear24_grouped: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+    off = _group_offsets(group_offsets, "linear24_grouped")
+    ldx = in_features if ldx is None else ldx
+    ldy = out_features if ldy is None else ldy
+    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
+    fn = getattr(lib(), "sm_linear24_grouped_" + _sfx(X))
+    _check(fn(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta),
+              ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24_grouped")
+
+
+def linear24_grouped_fp8(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, w_dtype=None, ldx=None, ldy=None, alpha=1.0,
+                         beta=0.0, w_scale=None, x_scale=None, epilogue=None):
+    """linear24_fp8 per expert in one launch (sm_linear24_grouped_fp8); w_scale: groups * out float32 values, expert-major; x_scale:
+    tokens values in Y's rows."""
+    fx = fp8_format(X.dtype)
+    fw = fx if w_dtype is None else fp8_format(w_dtype)
+    ot = _fp8_out_type(Y)
+    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
+        if v is not None and v.dtype != _t().float32:
+            raise SparsifymeError(f"linear24_grouped_fp8: {name} is float32, not {v.dtype}")
+    off = _group_offsets(group_offsets, "linear24_grouped_fp8")
+    ldx = in_features if ldx is None else ldx
+    ldy = out_features if ldy is None else ldy
+    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
+    _check(lib().sm_linear24_grouped_fp8(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, out_features, in_features, ldx, ldy, fw, fx, ot,
+                                         float(alpha), float(beta), _dev(w_scale) if w_scale is not None else None,
+                                         _dev(x_scale) if x_scale is not None else None, ctypes.addressof(st) if st is not None else None,
+                                         _stream()), "sm_linear24_grouped_fp8")
+
+
+def linear24_grouped_glu(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, act="silu", bias=None, ldx=None, ldy=None):
+    """linear24_glu per expert in one launch (sm_linear24_grouped_glu_*): blob is that of W[groups][2 hidden][in], each expert's gate
+    rows then its up rows; bias: groups * 2 * hidden float32 values in the same order, or None."""
+    torch = _t()
+    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
+        raise SparsifymeError(f"linear24_grouped_glu: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+    a, b = _glu_act(act, "linear24_grouped_glu"), _glu_bias(bias, "linear24_grouped_glu")
+    off = _group_offsets(group_offsets, "linear24_grouped_glu")
+    ldx = in_features if ldx is None else ldx
+    ldy = hidden if ldy is None else ldy
+    fn = getattr(lib(), "sm_linear24_grouped_glu_" + _sfx(X))
+    _check(fn(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, hidden, in_features, ldx, ldy, a, b, _stream()), "sm_linear24_grouped_glu")
+
+
+def linear24_grouped_glu_fp8(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, act="silu", w_dtype=None, w_scale=None,
+                             x_scale=None, bias=None, ldx=None, ldy=None):
+    """linear24_glu_fp8 per expert in one launch (sm_linear24_grouped_glu_fp8); w_scale and bias: groups * 2 * hidden float32 values."""
+    fx = fp8_format(X.dtype)
+    fw = fx if w_dtype is None else fp8_format(w_dtype)
+    ot = _fp8_out_type(Y)
+    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
+        if v is not None and v.dtype != _t().float32:
+            raise SparsifymeError(f"linear24_grouped_glu_fp8: {name} is float32, not {v.dtype}")
+    a, b = _glu_act(act, "linear24_grouped_glu_fp8"), _glu_bias(bias, "linear24_grouped_glu_fp8")
+    off = _group_offsets(group_offsets, "linear24_grouped_glu_fp8")
+    ldx = in_features if ldx is None else ldx
+    ldy = hidden if ldy is None else ldy
+    _check(lib().sm_linear24_grouped_glu_fp8(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, hidden, in_features, ldx, ldy, fw, fx, ot, a,
+                                             _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None,
+                                             b, _stream()), "sm_linear24_grouped_glu_fp8")
+
+
+def linear24_grouped_form(tokens, groups, out_features, in_features, cus=0):
+    """The name (LINEAR24_FORMS) of the form the grouped layers run -- sm_linear24_grouped_form; never "decode".  The gated layers ask
+    with out_features = 2 * hidden; the fp8 layers with this device's compute units (cus=0), the 16-bit layers with cus=256."""
+    form = _c_i(-1)
+    _check(lib().sm_linear24_grouped_form(tokens, groups, out_features, in_features, cus, ctypes.byref(form)), "sm_linear24_grouped_form")
     return LINEAR24_FORMS[form.value]
 
 

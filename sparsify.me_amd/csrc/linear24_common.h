@@ -1,7 +1,8 @@
 // linear24_common.h -- the core of the token-major 2:4 linear layer, shared by its two operand front ends: linear24_f16.hip
 // (sm_linear24_{f16,bf16}, 64 dense k per stage) and linear24_fp8.hip (sm_linear24_fp8, 128).  The front ends keep what depends on
 // the operand type -- the stage layout, the K loops, the matrix instruction; everything else is here, once: the dispatch rule, the
-// argument checks, the X-image swizzle, the fragment epilogue and store, the decode form's combine, the tile launcher.
+// argument checks, the X-image swizzle, the fragment epilogue and store, the decode form's combine, the tile launcher -- and what the
+// grouped (per-expert) entry points add: their rule, the slot bound, the workgroup's view of its expert, the grouped launcher.
 #pragma once
 #include "spmma_args.h"
 
@@ -34,6 +35,51 @@ inline int linear24_glu_form(size_t tokens, size_t hidden, size_t in, size_t cus
   return linear24_form(tokens, 2 * hidden, in, cus);
 }
 
+// ---- the grouped layers (sm_linear24_grouped_*): `groups` experts of one shape, tokens sorted by expert, ONE launch ------------------
+// The largest group count a call takes: the device-side walk over group_offsets is one load per group (linear24_group_view).
+constexpr size_t LINEAR24_MAX_GROUPS = SM_LINEAR24_MAX_GROUPS;
+
+// Token-tile slots of a grouped launch: min(tokens, ceil(tokens / BN) + groups - 1), an upper bound on sum_g ceil(c_g / BN) for every
+// distribution of at most `tokens` tokens over the groups.  Proof: a non-empty group has ceil(c / BN) = floor((c - 1) / BN) + 1, so
+// with n non-empty groups the sum is <= floor((T - n) / BN) + n <= floor((T - 1) / BN) + n <= ceil(T / BN) + groups - 1 (T = sum c_g
+// <= tokens); and ceil(c / BN) <= c gives the other term.  The counts live on the device: the grid is sized by the bound, and a slot
+// beyond the last real tile returns at once.
+inline size_t linear24_grouped_slots(size_t tokens, size_t groups, size_t bn) {
+  const size_t s = ceil_div(tokens, bn) + groups - 1;
+  return s < tokens ? s : tokens;
+}
+
+// The grouped rule, stated once: both grouped layers switch on it, sm_linear24_grouped_form exports it.  It is the plain tile rule
+// with the MEAN group size ceil(tokens / groups) deciding whether a 128-token tile is worth having, and never the decode form (no
+// grouped decode kernel: DESIGN.md 8).  The thresholds are the plain rule's, carried over, not measured.  out: rows of ONE expert.
+// The grid limit is read on tiles_m * slots, the grid the launcher asks for.
+inline int linear24_grouped_form(size_t tokens, size_t groups, size_t out, size_t in, size_t cus) {
+  if (in % 64 != 0 || tokens > 0x7fffffffull || out > 0x7fffffffull || in > 0x7fffffffull) return SM_LINEAR24_FORM_NOT_TAKEN;
+  if (groups > LINEAR24_MAX_GROUPS || (groups != 0 && out > 0x7fffffffull / groups)) return SM_LINEAR24_FORM_NOT_TAKEN;
+  if (tokens == 0 || out == 0 || groups == 0) return SM_LINEAR24_FORM_EMPTY;
+  const size_t mean = ceil_div(tokens, groups);
+  const size_t t128 = ceil_div(out, 128) * ceil_div(tokens, 128), t64 = ceil_div(out, 128) * ceil_div(tokens, 64);
+  auto grid = [&](size_t bm, size_t bn, int form) {
+    return ceil_div(out, bm) * linear24_grouped_slots(tokens, groups, bn) > 0x7fffffffull ? SM_LINEAR24_FORM_NOT_TAKEN : form;
+  };
+  if (mean > 64 && t128 >= cus) return grid(128, 128, SM_LINEAR24_FORM_TILE128);
+  if (t64 >= cus) return grid(128, 64, SM_LINEAR24_FORM_TILE128x64);
+  return grid(64, 64, SM_LINEAR24_FORM_TILE64);
+}
+
+// ... and the gated one: BY DEFINITION the grouped rule on 2 * hidden rows per expert; hidden <= 0x3fffffff / groups is its
+// groups * rows <= 2^31 - 1 read on hidden.
+inline int linear24_grouped_glu_form(size_t tokens, size_t groups, size_t hidden, size_t in, size_t cus) {
+  if (hidden > LINEAR24_GLU_MAX_HIDDEN) return SM_LINEAR24_FORM_NOT_TAKEN;
+  return linear24_grouped_form(tokens, groups, 2 * hidden, in, cus);
+}
+
+// What a grouped entry point adds to the argument checks below: the offsets (device) and the group count.
+struct Linear24Groups {
+  const int* offsets;
+  size_t groups;
+};
+
 // What the shared pieces read of a launch; each front end's argument block adds its X and its K extent.
 struct Linear24Core {
   const char* vals;  // the blob's values, plane-major
@@ -53,14 +99,15 @@ struct Linear24Core {
 // The entry points' argument checks, in their order and with their statuses, and the fields of Linear24Core they settle.  `who`
 // names the entry point in every message; extra_ok / extra: checks of the entry point's own that belong to the first test, and
 // their words in its message.  x_elt: bytes of an element of X (the blob's element too); piece: bytes of four elements of Y.
-// *run = false with SM_STATUS_SUCCESS: an empty problem, nothing to launch.
+// *run = false with SM_STATUS_SUCCESS: an empty problem, nothing to launch.  grp (the grouped entry points): `out` is then ONE
+// expert's row count and the blob that of W[groups * out][in]; the checks gain the offsets, the group limit and groups * out.
 inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool extra_ok, const char* extra, const void* blob, const void* X, void* Y,
                               size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, float alpha, float beta,
-                              const sm_epilogue_t* ep) {
+                              const sm_epilogue_t* ep, const Linear24Groups* grp = nullptr) {
   *run = false;
   bool plain;  // (not used: a plain epilogue takes the same kernels, whose bias / activation steps are skipped at run time)
   if (const int rc = epilogue_args(ep, Y, 0, out, beta, a.e, &plain, who)) return rc;
-  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < out) {
+  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < out || (grp && !grp->offsets)) {
     set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < out_features)", who, extra);
     return SM_STATUS_INVALID_VALUE;
   }
@@ -68,13 +115,17 @@ inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool 
     set_error("%s: dimension exceeds 2^31-1", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
+  if (grp && (grp->groups > LINEAR24_MAX_GROUPS || (grp->groups != 0 && out > 0x7fffffffull / grp->groups))) {
+    set_error("%s: groups exceeds SM_LINEAR24_MAX_GROUPS or groups * out_features exceeds 2^31-1", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
   if (in % 64 != 0 || !aligned16(X) || ldx % (16 / x_elt) != 0) {
     set_error("%s: in_features %% 64 == 0 and 16-byte aligned rows of X (pointer, ldx %% %d) are required", who, (int)(16 / x_elt));
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (tokens == 0 || out == 0) return SM_STATUS_SUCCESS;
+  if (tokens == 0 || out == 0 || (grp && grp->groups == 0)) return SM_STATUS_SUCCESS;
   a.vals = (const char*)blob;
-  a.meta = (const char*)blob + blob_layout(out, in, x_elt, 1).meta_off;
+  a.meta = (const char*)blob + blob_layout(out, in, x_elt, grp ? grp->groups : 1).meta_off;
   a.Y = Y;
   a.ldx = ldx; a.ldy = ldy;
   a.out = (int)out; a.tokens = (int)tokens;
@@ -88,13 +139,14 @@ inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool 
 // The same for the gated entry points (sm_linear24_glu_*), in the order include/sparsifyme.h states: the activation first, then the
 // plain layer's list read on `hidden`.  The blob is that of W[2 * hidden][in]; alpha = 1, beta = 0, no residual.
 inline int linear24_glu_args(Linear24Core& a, bool* run, const char* who, bool extra_ok, const char* extra, const void* blob, const void* X, void* Y,
-                             size_t tokens, size_t hidden, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, int act, const float* bias) {
+                             size_t tokens, size_t hidden, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, int act, const float* bias,
+                             const Linear24Groups* grp = nullptr) {
   *run = false;
   if (act != SM_GLU_ACT_NONE && act != SM_GLU_ACT_RELU && act != SM_GLU_ACT_SILU) {
     set_error("%s: invalid argument (act is not SM_GLU_ACT_*)", who);
     return SM_STATUS_INVALID_VALUE;
   }
-  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < hidden) {
+  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < hidden || (grp && !grp->offsets)) {
     set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < hidden)", who, extra);
     return SM_STATUS_INVALID_VALUE;
   }
@@ -102,13 +154,17 @@ inline int linear24_glu_args(Linear24Core& a, bool* run, const char* who, bool e
     set_error("%s: dimension exceeds 2^31-1 (tokens, in_features, 2 * hidden)", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
+  if (grp && (grp->groups > LINEAR24_MAX_GROUPS || (grp->groups != 0 && hidden > LINEAR24_GLU_MAX_HIDDEN / grp->groups))) {
+    set_error("%s: groups exceeds SM_LINEAR24_MAX_GROUPS or groups * 2 * hidden exceeds 2^31-1", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
   if (in % 64 != 0 || !aligned16(X) || ldx % (16 / x_elt) != 0) {
     set_error("%s: in_features %% 64 == 0 and 16-byte aligned rows of X (pointer, ldx %% %d) are required", who, (int)(16 / x_elt));
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (tokens == 0 || hidden == 0) return SM_STATUS_SUCCESS;
+  if (tokens == 0 || hidden == 0 || (grp && grp->groups == 0)) return SM_STATUS_SUCCESS;
   a.vals = (const char*)blob;
-  a.meta = (const char*)blob + blob_layout(2 * hidden, in, x_elt, 1).meta_off;
+  a.meta = (const char*)blob + blob_layout(2 * hidden, in, x_elt, grp ? grp->groups : 1).meta_off;
   a.Y = Y;
   a.ldx = ldx; a.ldy = ldy;
   a.out = (int)hidden; a.tokens = (int)tokens;
@@ -119,15 +175,11 @@ inline int linear24_glu_args(Linear24Core& a, bool* run, const char* who, bool e
   return SM_STATUS_SUCCESS;
 }
 
-// The tile form's launcher, one per kernel: the tile counts, the 2^31 - 1 grid limit, the opt-in to more than 64 KiB of dynamic LDS
-// (held per instantiation), the launch.  NT threads per workgroup, LDS bytes of the whole ring.  BM: the features of Y (a.out) a
-// workgroup covers -- the kernel's tile rows, or half of them for a gated kernel, whose tile is BM gate rows + BM up rows.
-template <class Args, void (*KERNEL)(Args), int BM, int BN, int NT, size_t LDS>
-static int launch_linear24_tile(const Args& a0, hipStream_t st, const char* who, const char* kernel_name) {
-  Args a = a0;
-  a.tiles_m = (a.out + BM - 1) / BM;
-  a.tiles_n = (a.tokens + BN - 1) / BN;
-  const size_t nwg = (size_t)a.tiles_m * a.tiles_n;
+// The tile forms' launch, one per kernel: the 2^31 - 1 grid limit on tiles_m * tiles_n, the opt-in to more than 64 KiB of dynamic LDS
+// (held per instantiation), the launch.  NT threads per workgroup, LDS bytes of the whole ring.
+template <class A, void (*KERNEL)(A), int NT, size_t LDS>
+static int launch_linear24_grid(const A& a, hipStream_t st, const char* who, const char* kernel_name) {
+  const size_t nwg = (size_t)a.tiles_m * (size_t)a.tiles_n;
   if (nwg > 0x7fffffffu) {
     set_error("%s: grid too large", who);
     return SM_STATUS_NOT_SUPPORTED;
@@ -140,11 +192,105 @@ static int launch_linear24_tile(const Args& a0, hipStream_t st, const char* who,
   return check_launch(kernel_name);
 }
 
+// The tile form's launcher: the tile counts, then the launch.  BM: the features of Y (a.out) a workgroup covers -- the kernel's tile
+// rows, or half of them for a gated kernel, whose tile is BM gate rows + BM up rows.
+template <class Args, void (*KERNEL)(Args), int BM, int BN, int NT, size_t LDS>
+static int launch_linear24_tile(const Args& a0, hipStream_t st, const char* who, const char* kernel_name) {
+  Args a = a0;
+  a.tiles_m = (a.out + BM - 1) / BM;
+  a.tiles_n = (a.tokens + BN - 1) / BN;
+  return launch_linear24_grid<Args, KERNEL, NT, LDS>(a, st, who, kernel_name);
+}
+
 // ... and the decode form's: one workgroup of NT threads per 16 out features
 template <class Args, void (*KERNEL)(Args), int NT>
 static int launch_linear24_decode(const Args& a, hipStream_t st, const char* kernel_name) {
   KERNEL<<<dim3((unsigned)ceil_div((size_t)a.out, 16)), dim3(NT), 0, st>>>(a);
   return check_launch(kernel_name);
+}
+
+// The argument block of a GROUPED tile kernel: the front end's own block + the offsets.  The plain instantiations keep taking the
+// front end's block itself, so their code is what it was.
+template <class Args>
+struct Linear24Grouped : Args {
+  const int* group_offsets;  // groups + 1 values, device
+  int groups;
+};
+template <class Args, bool GROUPED> struct Linear24ArgsSel { typedef Args type; typedef const Args& view_t; };
+template <class Args> struct Linear24ArgsSel<Args, true> { typedef Linear24Grouped<Args> type; typedef Args view_t; };
+
+// The grouped launcher: the plain one with tiles_n = the slot bound (linear24_grouped_slots) and the offsets handed on.
+template <class Args, void (*KERNEL)(Linear24Grouped<Args>), int BM, int BN, int NT, size_t LDS>
+static int launch_linear24_tile_grouped(const Args& a0, const Linear24Groups& grp, hipStream_t st, const char* who, const char* kernel_name) {
+  Linear24Grouped<Args> a;
+  static_cast<Args&>(a) = a0;
+  a.group_offsets = grp.offsets;
+  a.groups = (int)grp.groups;
+  a.tiles_m = (a.out + BM - 1) / BM;
+  a.tiles_n = (int)linear24_grouped_slots((size_t)a.tokens, grp.groups, BN);
+  return launch_linear24_grid<Linear24Grouped<Args>, KERNEL, NT, LDS>(a, st, who, kernel_name);
+}
+
+// A grouped workgroup's view of the launch: from its block id to (group, out tile, local token tile), then the argument block cut down
+// to that group.  Group g owns tokens [lo, hi): lo = clamp(off[g], 0, tokens) raised to the end of the groups before it,
+// hi = clamp(off[g + 1], lo, tokens) -- for non-decreasing offsets the ranges of include/sparsifyme.h; where offsets decrease the
+// overlap goes to the earlier group, so that the ranges stay disjoint, their tiles stay within the slot bound, and no group outside
+// the overlap loses a tile.  nt_g = ceil((hi - lo) / BN) token tiles each.
+// The real tiles are ordered as the per-expert launches of the plain layer would be, one after the other: group-major, within a group
+// the plain kernel's (out tile, token tile) order -- so the workgroups that run together share one expert's X rows and walk its
+// weight once, as they do in the plain layer (with the out tile outermost across ALL groups every workgroup of a wave of the grid
+// had token rows of its own and X came from beyond L2 again for every out tile: the 8192-token cells of profiles/
+// linear_grouped_table.txt were 8 - 38 % behind the per-expert loop).  T = tiles_m * sum_g nt_g of them; xcd_remap is applied on T,
+// not on the grid, so each XCD gets a contiguous eighth of the REAL tiles; blocks T .. gridDim.x - 1 return.
+// Two walks over group_offsets -- the first for T, the second for the group -- of at most LINEAR24_MAX_GROUPS loads each, from one
+// address per step, the same in every lane and every wave of the workgroup (scalar loads; nothing is written).  Returns false for a
+// block beyond the last real tile (the same answer in the whole workgroup: the caller returns before its first DMA and barrier).
+// Otherwise p is the plain kernel's block for expert g alone: vals / meta / w_scale / the per-out bias advanced by g * grows rows
+// (vrow: bytes of a blob row in one plane), p.tokens = hi (the token clamp and the store bound), n0 the tile's first token; Y, R,
+// x_scale and a per-token bias stay in global token coordinates.  Everything is wave-uniform and held in SGPRs.
+template <int BN, class Args>
+__device__ __forceinline__ bool linear24_group_view(Args& p, const int* off, int groups, unsigned bid, unsigned grows, unsigned vrow, unsigned& tile_m,
+                                                    unsigned& n0) {
+  const int tokens = p.tokens;
+  const unsigned tiles_m = (unsigned)p.tiles_m;
+  auto clamp = [&](int v) { return v < 0 ? 0 : (v > tokens ? tokens : v); };
+  unsigned total = 0;
+  {
+    int cur = 0, next = clamp(off[0]);
+    for (int g = 0; g < groups; ++g) {
+      const int lo = next > cur ? next : cur;
+      next = clamp(off[g + 1]);
+      cur = next > lo ? next : lo;
+      total += ((unsigned)(cur - lo) + (unsigned)BN - 1u) / (unsigned)BN;
+    }
+  }
+  total *= tiles_m;  // <= tiles_m * slots = gridDim.x
+  if (bid >= total) return false;
+  const unsigned lid = xcd_remap(bid, total);  // (a bijection on [0, total) for any total: every real tile has a block)
+  int cur = 0, next = clamp(off[0]);
+  unsigned base = 0;
+  for (int g = 0; g < groups; ++g) {
+    const int lo = next > cur ? next : cur;
+    next = clamp(off[g + 1]);
+    const int hi = next > lo ? next : lo;
+    const unsigned nt = ((unsigned)(hi - lo) + (unsigned)BN - 1u) / (unsigned)BN;
+    if (lid - base < nt * tiles_m) {
+      const unsigned within = lid - base;
+      tile_m = (unsigned)__builtin_amdgcn_readfirstlane((int)(within / nt));
+      const unsigned local = within - tile_m * nt;
+      const size_t r0 = (size_t)__builtin_amdgcn_readfirstlane(g) * grows;
+      p.vals += r0 * vrow;
+      p.meta += r0 * 8;
+      if (p.w_scale) p.w_scale += r0;
+      if (p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_COL) p.e.bias += r0;
+      p.tokens = __builtin_amdgcn_readfirstlane(hi);
+      n0 = (unsigned)__builtin_amdgcn_readfirstlane(lo) + local * (unsigned)BN;
+      return true;
+    }
+    base += nt * tiles_m;
+    cur = hi;
+  }
+  return false;
 }
 
 // The X image of a stage: [tokens][128 B], 16-byte chunk c of token row t at slot c ^ ((t >> 1) & 7).  A ds_read_b128 access group is

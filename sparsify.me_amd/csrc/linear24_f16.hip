@@ -23,6 +23,8 @@ namespace sm {
 constexpr size_t LINEAR24_F16_CUS = 256;
 static const char* const LINEAR24_F16_WHO = "sm_linear24_{f16,bf16}";
 static const char* const LINEAR24_GLU16_WHO = "sm_linear24_glu_{f16,bf16}";
+static const char* const LINEAR24_GROUPED16_WHO = "sm_linear24_grouped_{f16,bf16}";
+static const char* const LINEAR24_GROUPED_GLU16_WHO = "sm_linear24_grouped_glu_{f16,bf16}";
 
 struct Linear24Args : Linear24Core {  // vals stage-major [in/64][out][64 B]
   const half_t* X;
@@ -82,8 +84,12 @@ __device__ __forceinline__ void linear24_stage(const char* As, const char* Ms, c
 // ---------------------------------------------------------------------------------------------------------------------------
 // GLU: the tile's BM rows are BM / 2 gate rows and the BM / 2 up rows of the same hidden features, interleaved by 16-row fragment; p.out
 // is `hidden`, the width of Y, and the blob has 2 * p.out rows.
-template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU = false>
-__global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linear24Args p) {
+// GROUPED (sm_linear24_grouped_*): tiles_n counts token-tile SLOTS, the grid's bound; the workgroup finds its expert, out tile and token
+// tile in group_offsets (linear24_group_view), returns when it is past the last real tile, and else runs this body on the block cut down
+// to its expert.
+template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU = false, bool GROUPED = false>
+__global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const typename Linear24ArgsSel<Linear24Args, GROUPED>::type pk) {
+  typename Linear24ArgsSel<Linear24Args, GROUPED>::view_t p = pk;
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
   static_assert(FM >= 1 && FN >= 1 && BM % 32 == 0 && BN % 8 == 0, "tile");
@@ -101,12 +107,17 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const Linea
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned wm = wave / WN, wn = wave % WN;
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
-  const unsigned tile_m = lid / (unsigned)p.tiles_n, tile_n = lid - tile_m * (unsigned)p.tiles_n;
+  const unsigned tm = lid / (unsigned)p.tiles_n, tile_n = lid - tm * (unsigned)p.tiles_n;  // (a grouped workgroup's come from its view)
   // row and token indices are unsigned: an edge tile's origin plus its extent may pass 2^31 - 1 (never 2^32)
-  const unsigned m0 = tile_m * BM, n0 = tile_n * BN;
+  unsigned tile_m = tm, n0 = tile_n * BN;
+  size_t rows = GLU ? 2 * (size_t)p.out : (size_t)p.out;             // rows of the blob: the plane stride
+  if constexpr (GROUPED) {
+    if (!linear24_group_view<BN>(p, pk.group_offsets, pk.groups, blockIdx.x, (unsigned)rows, 64u, tile_m, n0)) return;  // (workgroup-uniform)
+    rows *= (size_t)pk.groups;
+  }
+  const unsigned m0 = tile_m * BM;
   const unsigned mlast = (unsigned)p.out - 1u, tlast = (unsigned)p.tokens - 1u;
   const unsigned hid0 = tile_m * (BM / 2);                           // GLU: the tile's first hidden feature
-  const size_t rows = GLU ? 2 * (size_t)p.out : (size_t)p.out;       // rows of the blob: the plane stride
 
   // the lane's bias values, fetched ahead of the K loop (plain loads, older than every DMA piece: the counted waits cover them)
   const bool bias_out = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_COL, bias_tok = p.e.bias != nullptr && p.e.bias_dim == SM_BIAS_ROW;
@@ -300,6 +311,13 @@ static int launch_linear24_tile16(const Linear24Args& a, hipStream_t st) {
                               (size_t)NS * (BM * 72 + BN * 128)>(a, st, GLU ? LINEAR24_GLU16_WHO : LINEAR24_F16_WHO, "linear24_tile_kernel");
 }
 
+template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU>
+static int launch_linear24_tile16_grouped(const Linear24Args& a, const Linear24Groups& grp, hipStream_t st) {
+  return launch_linear24_tile_grouped<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF, GLU, true>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                                      (size_t)NS * (BM * 72 + BN * 128)>(a, grp, st, GLU ? LINEAR24_GROUPED_GLU16_WHO : LINEAR24_GROUPED16_WHO,
+                                                                         "linear24_tile_kernel");
+}
+
 }  // namespace sm
 
 using namespace sm;
@@ -361,4 +379,67 @@ extern "C" int sm_linear24_glu_f16(const void* blob, const void* X, void* Y, siz
 extern "C" int sm_linear24_glu_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
                                     int act, const float* bias, sm_stream_t stream) {
   return linear24_glu<true>(blob, X, Y, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+}
+
+// ---- the grouped layers: `groups` experts of one shape behind one launch (the GROUPED instantiations of the tile kernels) ----------
+template <bool BF>
+static int linear24_grouped(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t out, size_t in,
+                            size_t ldx, size_t ldy, float alpha, float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
+  Linear24Args a = {};
+  const Linear24Groups grp = {group_offsets, groups};
+  bool run;
+  const int rc = linear24_core_args(a, &run, LINEAR24_GROUPED16_WHO, true, "null group_offsets, ", blob, X, Y, tokens, out, in, ldx, ldy, 2, 8, alpha, beta,
+                                    ep, &grp);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.X = (const half_t*)X;
+  a.nkt = (int)(in / 64);
+  hipStream_t st = (hipStream_t)stream;
+  switch (linear24_grouped_form(tokens, groups, out, in, LINEAR24_F16_CUS)) {
+    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, false>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, false>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, false>(a, grp, st);
+  }
+  set_error("%s: grid too large", LINEAR24_GROUPED16_WHO);
+  return SM_STATUS_NOT_SUPPORTED;
+}
+
+extern "C" int sm_linear24_grouped_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
+                                       size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha, float beta,
+                                       const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return linear24_grouped<false>(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue, stream);
+}
+extern "C" int sm_linear24_grouped_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
+                                        size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha, float beta,
+                                        const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return linear24_grouped<true>(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue, stream);
+}
+
+template <bool BF>
+static int linear24_grouped_glu(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
+                                size_t in, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
+  Linear24Args a = {};
+  const Linear24Groups grp = {group_offsets, groups};
+  bool run;
+  const int rc = linear24_glu_args(a, &run, LINEAR24_GROUPED_GLU16_WHO, true, "null group_offsets, ", blob, X, Y, tokens, hidden, in, ldx, ldy, 2, 8, act,
+                                   bias, &grp);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.X = (const half_t*)X;
+  a.nkt = (int)(in / 64);
+  hipStream_t st = (hipStream_t)stream;
+  switch (linear24_grouped_glu_form(tokens, groups, hidden, in, LINEAR24_F16_CUS)) {
+    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, true>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, true>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, true>(a, grp, st);
+  }
+  set_error("%s: grid too large", LINEAR24_GROUPED_GLU16_WHO);
+  return SM_STATUS_NOT_SUPPORTED;
+}
+
+extern "C" int sm_linear24_grouped_glu_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
+                                           size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
+  return linear24_grouped_glu<false>(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+}
+extern "C" int sm_linear24_grouped_glu_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
+                                            size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
+  return linear24_grouped_glu<true>(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
 }

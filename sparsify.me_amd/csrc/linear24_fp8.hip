@@ -26,6 +26,8 @@ namespace sm {
 
 static const char* const LINEAR24_FP8_WHO = "sm_linear24_fp8";
 static const char* const LINEAR24_GLU8_WHO = "sm_linear24_glu_fp8";
+static const char* const LINEAR24_GROUPED8_WHO = "sm_linear24_grouped_fp8";
+static const char* const LINEAR24_GROUPED_GLU8_WHO = "sm_linear24_grouped_glu_fp8";
 
 struct Linear8Args : Linear24Core {  // vals plane-major [in/64][out][32 B]
   size_t Mtot;  // rows of the blob (= out; the gated kernels: 2 * out)
@@ -66,8 +68,11 @@ __device__ __forceinline__ void linear8_store_glu_any(const Linear8Args& p, cons
 // ---------------------------------------------------------------------------------------------------------------------------
 // GLU: the tile's BM rows are BM / 2 gate rows and the BM / 2 up rows of the same hidden features, interleaved by 16-row fragment; p.out
 // is `hidden`, the width of Y, and the blob has p.Mtot = 2 * p.out rows.
-template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU = false>
-__global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const Linear8Args p) {
+// GROUPED (sm_linear24_grouped_*fp8): as in linear24_tile_kernel -- slots for tiles_n (the grid's bound), linear24_group_view, then this body on expert
+// g's own rows of the stacked blob (p.Mtot = groups * rows of one expert: the plane stride).
+template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU = false, bool GROUPED = false>
+__global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const typename Linear24ArgsSel<Linear8Args, GROUPED>::type pk) {
+  typename Linear24ArgsSel<Linear8Args, GROUPED>::view_t p = pk;
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;
   static_assert(FM >= 1 && FN >= 1 && BM % 32 == 0 && BN % 8 == 0, "tile");
@@ -86,9 +91,13 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const L
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned wm = wave / WN, wn = wave % WN;
   const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
-  const unsigned tile_m = lid / (unsigned)p.tiles_n, tile_n = lid - tile_m * (unsigned)p.tiles_n;
+  const unsigned tm = lid / (unsigned)p.tiles_n, tile_n = lid - tm * (unsigned)p.tiles_n;  // (a grouped workgroup's come from its view)
   // row and token indices are unsigned: an edge tile's origin plus its extent may pass 2^31 - 1 (never 2^32)
-  const unsigned m0 = tile_m * BM, n0 = tile_n * BN;
+  unsigned tile_m = tm, n0 = tile_n * BN;
+  if constexpr (GROUPED) {
+    if (!linear24_group_view<BN>(p, pk.group_offsets, pk.groups, blockIdx.x, (GLU ? 2u : 1u) * (unsigned)p.out, 32u, tile_m, n0)) return;  // (workgroup-uniform)
+  }
+  const unsigned m0 = tile_m * BM;
   const unsigned mlast = (unsigned)p.out - 1u, tlast = (unsigned)p.tokens - 1u;
   const unsigned hid0 = tile_m * (BM / 2);  // GLU: the tile's first hidden feature
 
@@ -311,6 +320,32 @@ static int launch_linear8_tile(const Linear8Args& a, hipStream_t st) {
                               (size_t)NS * (BM * 80 + BN * 128)>(a, st, GLU ? LINEAR24_GLU8_WHO : LINEAR24_FP8_WHO, "linear24_fp8_tile_kernel");
 }
 
+template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU>
+static int launch_linear8_tile_grouped(const Linear8Args& a, const Linear24Groups& grp, hipStream_t st) {
+  return launch_linear24_tile_grouped<Linear8Args, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS, GLU, true>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                                      (size_t)NS * (BM * 80 + BN * 128)>(a, grp, st, GLU ? LINEAR24_GROUPED_GLU8_WHO : LINEAR24_GROUPED8_WHO,
+                                                                         "linear24_fp8_tile_kernel");
+}
+
+template <int FW, int FX, bool GLU>
+static int linear8_launch_grouped(const Linear8Args& a, const Linear24Groups& grp, int form, hipStream_t st) {
+  typedef MmaF8<FW, FX> MM;
+  switch (form) {
+    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile_grouped<MM, 128, 128, 2, 2, 3, GLU>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile_grouped<MM, 128, 64, 4, 1, 3, GLU>(a, grp, st);
+    default: return launch_linear8_tile_grouped<MM, 64, 64, 2, 2, 3, GLU>(a, grp, st);
+  }
+}
+
+template <bool GLU>
+static int linear8_launch_grouped_fmt(const Linear8Args& a, const Linear24Groups& grp, int fmt_w, int fmt_x, int form, hipStream_t st) {
+  if (fmt_w == SM_FP8_E4M3)
+    return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E4M3, GLU>(a, grp, form, st)
+                                : linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E5M2, GLU>(a, grp, form, st);
+  return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E4M3, GLU>(a, grp, form, st)
+                              : linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E5M2, GLU>(a, grp, form, st);
+}
+
 template <int FW, int FX, bool GLU>
 static int linear8_launch(const Linear8Args& a, int form, hipStream_t st) {
   typedef MmaF8<FW, FX> MM;
@@ -397,4 +432,63 @@ extern "C" int sm_linear24_glu_fp8(const void* blob, const void* X, void* Y, siz
     return SM_STATUS_NOT_SUPPORTED;
   }
   return linear8_launch_fmt<true>(a, fmt_w, fmt_x, form, (hipStream_t)stream);
+}
+
+// ---- the grouped layers: `groups` experts of one shape behind one launch (the GROUPED instantiations of the tile kernels) ----------
+extern "C" int sm_linear24_grouped_form(size_t tokens, size_t groups, size_t out_features, size_t in_features, size_t cus, int* form) {
+  if (!form) {
+    set_error("sm_linear24_grouped_form: invalid argument (form is NULL)");
+    return SM_STATUS_INVALID_VALUE;
+  }
+  *form = linear24_grouped_form(tokens, groups, out_features, in_features, cus ? cus : (size_t)device_cu_count());
+  return SM_STATUS_SUCCESS;
+}
+
+extern "C" int sm_linear24_grouped_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
+                                       size_t out_features, size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, float alpha,
+                                       float beta, const float* w_scale, const float* x_scale, const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  const size_t out = out_features, in = in_features;
+  Linear8Args a = {};
+  const Linear24Groups grp = {group_offsets, groups};
+  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
+  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
+  bool run;
+  const int rc = linear24_core_args(a, &run, LINEAR24_GROUPED8_WHO, fmt_ok && out_ok, "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob, X,
+                                    Y, tokens, out, in, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, alpha, beta, epilogue, &grp);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.Mtot = groups * out;
+  a.X = (const uint8_t*)X;
+  a.nplanes = (int)(in / 64);
+  a.out_type = out_type;
+  a.w_scale = w_scale; a.x_scale = x_scale;
+  const int form = linear24_grouped_form(tokens, groups, out, in, (size_t)device_cu_count());
+  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
+    set_error("%s: grid too large", LINEAR24_GROUPED8_WHO);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  return linear8_launch_grouped_fmt<false>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream);
+}
+
+extern "C" int sm_linear24_grouped_glu_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
+                                           size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, int act, const float* w_scale,
+                                           const float* x_scale, const float* bias, sm_stream_t stream) {
+  Linear8Args a = {};
+  const Linear24Groups grp = {group_offsets, groups};
+  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
+  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
+  bool run;
+  const int rc = linear24_glu_args(a, &run, LINEAR24_GROUPED_GLU8_WHO, fmt_ok && out_ok, "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob,
+                                   X, Y, tokens, hidden, in_features, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, act, bias, &grp);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.Mtot = groups * 2 * hidden;
+  a.X = (const uint8_t*)X;
+  a.nplanes = (int)(in_features / 64);
+  a.out_type = out_type;
+  a.w_scale = w_scale; a.x_scale = x_scale;
+  const int form = linear24_grouped_glu_form(tokens, groups, hidden, in_features, (size_t)device_cu_count());
+  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
+    set_error("%s: grid too large", LINEAR24_GROUPED_GLU8_WHO);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  return linear8_launch_grouped_fmt<true>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream);
 }
