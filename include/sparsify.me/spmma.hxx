@@ -94,6 +94,20 @@ struct spmma_fns_f16 {
                                    std::size_t in, std::size_t ldx, std::size_t ldy, int act, const float* bias, hipStream_t st) {
     return sm_linear24_grouped_glu_f16(blob, X, Y, off, groups, tokens, hidden, in, ldx, ldy, act, bias, st);
   }
+  static int linear_grouped_gather_on(const void* blob, const void* X, void* Y, const int* off, const int* xi, std::size_t xr, std::size_t groups,
+                                      std::size_t tokens, std::size_t out, std::size_t in, std::size_t ldx, std::size_t ldy, float al, float be,
+                                      const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_linear24_grouped_gather_f16(blob, X, Y, off, xi, xr, groups, tokens, out, in, ldx, ldy, al, be, ep, st);
+  }
+  static int linear_glu_grouped_gather_on(const void* blob, const void* X, void* Y, const int* off, const int* xi, std::size_t xr, std::size_t groups,
+                                          std::size_t tokens, std::size_t hidden, std::size_t in, std::size_t ldx, std::size_t ldy, int act,
+                                          const float* bias, hipStream_t st) {
+    return sm_linear24_grouped_glu_gather_f16(blob, X, Y, off, xi, xr, groups, tokens, hidden, in, ldx, ldy, act, bias, st);
+  }
+  static int moe_combine_on(const void* Yp, const int* pos, const float* w, const void* R, void* out, std::size_t tokens, std::size_t top_k,
+                            std::size_t hidden, std::size_t rows_p, std::size_t ldp, std::size_t ldo, hipStream_t st) {
+    return sm_moe_combine_f16(Yp, pos, w, R, out, tokens, top_k, hidden, rows_p, ldp, ldo, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -150,6 +164,20 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
   static int linear_glu_grouped_on(const void* blob, const void* X, void* Y, const int* off, std::size_t groups, std::size_t tokens, std::size_t hidden,
                                    std::size_t in, std::size_t ldx, std::size_t ldy, int act, const float* bias, hipStream_t st) {
     return sm_linear24_grouped_glu_bf16(blob, X, Y, off, groups, tokens, hidden, in, ldx, ldy, act, bias, st);
+  }
+  static int linear_grouped_gather_on(const void* blob, const void* X, void* Y, const int* off, const int* xi, std::size_t xr, std::size_t groups,
+                                      std::size_t tokens, std::size_t out, std::size_t in, std::size_t ldx, std::size_t ldy, float al, float be,
+                                      const sm_epilogue_t* ep, hipStream_t st) {
+    return sm_linear24_grouped_gather_bf16(blob, X, Y, off, xi, xr, groups, tokens, out, in, ldx, ldy, al, be, ep, st);
+  }
+  static int linear_glu_grouped_gather_on(const void* blob, const void* X, void* Y, const int* off, const int* xi, std::size_t xr, std::size_t groups,
+                                          std::size_t tokens, std::size_t hidden, std::size_t in, std::size_t ldx, std::size_t ldy, int act,
+                                          const float* bias, hipStream_t st) {
+    return sm_linear24_grouped_glu_gather_bf16(blob, X, Y, off, xi, xr, groups, tokens, hidden, in, ldx, ldy, act, bias, st);
+  }
+  static int moe_combine_on(const void* Yp, const int* pos, const float* w, const void* R, void* out, std::size_t tokens, std::size_t top_k,
+                            std::size_t hidden, std::size_t rows_p, std::size_t ldp, std::size_t ldo, hipStream_t st) {
+    return sm_moe_combine_bf16(Yp, pos, w, R, out, tokens, top_k, hidden, rows_p, ldp, ldo, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -561,11 +589,67 @@ class spmma_plan_t {
                                       stream);
   }
 
+  // Extension: the grouped layers with X GATHERED through a row index (sm_linear24_grouped_*gather_*): dX stays in the caller's token
+  // order, x_rows rows of it; row t of Y, a sorted row, reads row d_x_index[t] of X (tokens int32 values in DEVICE memory: moe_route's
+  // sorted_token).  Y, the residual and an SM_BIAS_ROW bias stay in Y's sorted rows; the bits are those of the overloads above on the
+  // materialised X[d_x_index].
+  int linear_grouped(type_t* dX, type_t* dY, const int* d_offsets, const int* d_x_index, std::size_t x_rows, std::size_t groups, std::size_t tokens,
+                     float alpha = 1.0f, float beta = 0.0f, hipStream_t stream = nullptr, std::size_t ldx = 0, std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1 || groups == 0 || m_ % groups != 0) return SM_STATUS_INVALID_VALUE;
+    const std::size_t out = m_ / groups;
+    return fns::linear_grouped_gather_on(blob_.data().get(), dX, dY, d_offsets, d_x_index, x_rows, groups, tokens, out, k_, ldx ? ldx : k_,
+                                         ldy ? ldy : out, alpha, beta, nullptr, stream);
+  }
+  int linear_grouped(type_t* dX, type_t* dY, const int* d_offsets, const int* d_x_index, std::size_t x_rows, std::size_t groups, std::size_t tokens,
+                     const spmma_epilogue_t& epilogue, float alpha = 1.0f, float beta = 0.0f, hipStream_t stream = nullptr, std::size_t ldx = 0,
+                     std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1 || groups == 0 || m_ % groups != 0) return SM_STATUS_INVALID_VALUE;
+    const std::size_t out = m_ / groups;
+    const sm_epilogue_t e = epilogue.c_struct(dY, tokens, out, beta);
+    return fns::linear_grouped_gather_on(blob_.data().get(), dX, dY, d_offsets, d_x_index, x_rows, groups, tokens, out, k_, ldx ? ldx : k_,
+                                         ldy ? ldy : out, alpha, beta, &e, stream);
+  }
+  int linear_glu_grouped(type_t* dX, type_t* dY, const int* d_offsets, const int* d_x_index, std::size_t x_rows, std::size_t groups, std::size_t tokens,
+                         int act = SM_GLU_ACT_SILU, const float* bias = nullptr, hipStream_t stream = nullptr, std::size_t ldx = 0, std::size_t ldy = 0) {
+    using fns = detail::spmma_fns<type_t>;
+    if (!ready_ || batch_ != 1 || groups == 0 || m_ % (2 * groups) != 0) return SM_STATUS_INVALID_VALUE;
+    const std::size_t hidden = m_ / (2 * groups);
+    return fns::linear_glu_grouped_gather_on(blob_.data().get(), dX, dY, d_offsets, d_x_index, x_rows, groups, tokens, hidden, k_, ldx ? ldx : k_,
+                                             ldy ? ldy : hidden, act, bias, stream);
+  }
+
  private:
   std::size_t m_, k_, batch_;
   device_vector<unsigned char> blob_;
   bool ready_ = false;
 };
+
+// Extension: MoE routing on the device (sm_moe_route).  d_expert_ids: tokens * top_k int32 ids, pair p = t * top_k + j; a stable counting
+// sort by expert, ids outside [0, groups) dropped.  d_offsets: groups + 1 values (the grouped layers' offsets); d_sorted_token /
+// d_sorted_pair: P values, -1 behind the kept pairs (d_sorted_token is the gathered layers' x_index); d_pair_pos: P values, the slot of
+// every pair or -1 (moe_combine's).  workspace: moe_route_workspace(...) bytes, null where that is 0.  Enqueue only.
+inline std::size_t moe_route_workspace(std::size_t tokens, std::size_t top_k, std::size_t groups) {
+  std::size_t bytes = 0;
+  (void)sm_moe_route_workspace_size(tokens, top_k, groups, &bytes);
+  return bytes;
+}
+inline int moe_route(const int* d_expert_ids, std::size_t tokens, std::size_t top_k, std::size_t groups, int* d_offsets, int* d_sorted_token,
+                     int* d_sorted_pair, int* d_pair_pos, void* workspace = nullptr, std::size_t workspace_bytes = 0, hipStream_t stream = nullptr) {
+  return sm_moe_route(d_expert_ids, tokens, top_k, groups, d_offsets, d_sorted_token, d_sorted_pair, d_pair_pos, workspace, workspace_bytes, stream);
+}
+
+// Extension (fp16 / bfloat16): the un-permute and weighted sum over top_k that close the block (sm_moe_combine_*):
+// out[t] = round(residual[t] + sum_j weights[t top_k + j] * Yp[d_pair_pos[t top_k + j]]), fp32, j ascending, multiply and add not
+// contracted, one rounding.  d_weights (fp32, pair order) and d_residual (out's shape and ldo; out itself: in place) may be null;
+// ldp / ldo: 0 = hidden.
+template <typename type_t>
+int moe_combine(const type_t* dYp, const int* d_pair_pos, const float* d_weights, const type_t* d_residual, type_t* d_out, std::size_t tokens,
+                std::size_t top_k, std::size_t hidden, std::size_t rows_p, hipStream_t stream = nullptr, std::size_t ldp = 0, std::size_t ldo = 0) {
+  return detail::spmma_fns<type_t>::moe_combine_on(dYp, d_pair_pos, d_weights, d_residual, d_out, tokens, top_k, hidden, rows_p, ldp ? ldp : hidden,
+                                                   ldo ? ldo : hidden, stream);
+}
 
 // Extension (round 5; float only): the bfloat16 planes of a B that stays the same across calls -- the weights of a layer -- for the product on the
 // sparse matrix instruction (spmma_options().f32_planes, sm_spmma_fused_f32_split): prepare() splits B once, multiply() then runs the same kernels

@@ -563,9 +563,9 @@ int sm_linear24_glu_form(size_t tokens, size_t hidden, size_t in_features, size_
  *      groups * 2 * hidden) > 2^31 - 1, a grid beyond 2^31 - 1 workgroups: SM_STATUS_NOT_SUPPORTED; in_features % 64 != 0, X rows not
  *      16-byte aligned: SM_STATUS_NOT_SUPPORTED; tokens == 0, out_features == 0 or groups == 0: success, nothing enqueued.
  *      Enqueue only: no allocation, no synchronisation, no workspace, no memset node; capturable into a hipGraph.
- *      Not covered: a grouped decode form (few tokens per expert run the 64 x 64 tile form: DESIGN.md 8), a per-token gather / scatter
- *      index (un-permuted tokens), a top-k combine weight on the 16-bit path, experts of differing shapes, an fp8-quantised Y; the
- *      plain layers' rules and kernels are unchanged. */
+ *      Not covered: a grouped decode form (few tokens per expert run the 64 x 64 tile form: DESIGN.md 8), experts of differing shapes,
+ *      an fp8-quantised Y; the plain layers' rules and kernels are unchanged.  (Un-permuted tokens: the _gather forms below; the top-k
+ *      combine weight: sm_moe_combine_*.) */
 #define SM_LINEAR24_MAX_GROUPS 1024
 int sm_linear24_grouped_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t out_features,
                             size_t in_features, size_t ldx, size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
@@ -582,6 +582,99 @@ int sm_linear24_grouped_glu_fp8(const void* blob, const void* X, void* Y, const 
                                 size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, int act, const float* w_scale,
                                 const float* x_scale, const float* bias, sm_stream_t stream);
 int sm_linear24_grouped_form(size_t tokens, size_t groups, size_t out_features, size_t in_features, size_t cus, int* form);
+
+/* ---- GATHERED X in the grouped layers (extension): the grouped entry points above with `const int* x_index, size_t x_rows` directly
+ *      after group_offsets.  X stays in the caller's TOKEN order and is never copied into the sorted order:
+ *
+ *          row t of Y (a sorted row)  reads  row clamp(x_index[t], 0, x_rows - 1) of X          (X has x_rows rows)
+ *
+ *      x_index  `tokens` int32 values in DEVICE memory (sm_moe_route's sorted_token), read on the device only, once per workgroup,
+ *               ahead of its first load of X.  Whatever the array holds, no byte outside the x_rows rows of X is touched.
+ *      fp8      x_scale holds x_rows floats and is read at the same source row: the scale belongs to the token that was quantised.
+ *      Y, R and an SM_BIAS_ROW bias stay in Y's sorted rows; group_offsets, the blob, the per-out-feature vectors and `tokens` (the
+ *      row count of Y and of x_index) keep their meaning.  Rows no group owns are not written: with sm_moe_route's outputs that is
+ *      every row s >= V of a routing with dropped pairs.
+ *      Arithmetic: group g's rows are bit for bit what sm_linear24_grouped_* gives on the materialised X' = X[x_index] (the GATHER
+ *      instantiations of the same tile kernels; only the source row of the X loads differs).  Form: sm_linear24_grouped_form.
+ *      Status: the twin's list in its order; a null x_index or x_rows == 0 belongs to its first SM_STATUS_INVALID_VALUE test,
+ *      x_rows >= 2^31 to its dimension test (SM_STATUS_NOT_SUPPORTED).  Enqueue only, capturable, as the twins. */
+int sm_linear24_grouped_gather_f16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                   size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha,
+                                   float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_linear24_grouped_gather_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                    size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha,
+                                    float beta, const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_linear24_grouped_gather_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                   size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, int fmt_w,
+                                   int fmt_x, int out_type, float alpha, float beta, const float* w_scale, const float* x_scale,
+                                   const sm_epilogue_t* epilogue, sm_stream_t stream);
+int sm_linear24_grouped_glu_gather_f16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                       size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act,
+                                       const float* bias, sm_stream_t stream);
+int sm_linear24_grouped_glu_gather_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                        size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act,
+                                        const float* bias, sm_stream_t stream);
+int sm_linear24_grouped_glu_gather_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                       size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int fmt_w,
+                                       int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale, const float* bias,
+                                       sm_stream_t stream);
+
+/* ---- MoE routing on the device (extension): from the router's ids to what the grouped layers and sm_moe_combine_* read.
+ *      P = tokens * top_k pairs; pair p = t * top_k + j is token t's j-th choice, expert_ids[p] its expert (int32, device).
+ *      The result is a STABLE COUNTING SORT of the pairs by expert id -- fully defined, the same integers from every form, every run:
+ *        a pair whose id lies outside [0, groups) is DROPPED (padding, an expert of another rank);
+ *        group_offsets[g]  (groups + 1 values) the number of kept pairs with id < g; V = group_offsets[groups] kept pairs in all;
+ *        sorted_pair[s]    for s in [off[e], off[e + 1]): the (s - off[e])-th pair with id e in ascending p;  -1 for s in [V, P);
+ *        sorted_token[s]   sorted_pair[s] / top_k (the x_index of the gathered layers);                       -1 for s in [V, P);
+ *        pair_pos[p]       s for a kept pair, -1 for a dropped one (the inverse permutation sm_moe_combine_* reads).
+ *      Forms (sm_moe_route_form; the entry point switches on it):
+ *        SM_MOE_ROUTE_FORM_SINGLE  P <= SM_MOE_ROUTE_SINGLE_MAX_PAIRS: one launch, the whole sort in one workgroup's LDS; no
+ *                                  workspace (size 0, NULL accepted).  The decode case.
+ *        SM_MOE_ROUTE_FORM_MULTI   else: per chunk of SM_MOE_ROUTE_CHUNK pairs a histogram, one scan, a stable scatter per chunk
+ *                                  (three launches); workspace = ceil(P / SM_MOE_ROUTE_CHUNK) * groups * 4 bytes
+ *                                  (sm_moe_route_workspace_size), 4-byte aligned, contents irrelevant on entry.
+ *        SM_MOE_ROUTE_FORM_EMPTY   P == 0 or groups == 0;  SM_MOE_ROUTE_FORM_INVALID  P > 2^31 - 1 or groups > SM_LINEAR24_MAX_GROUPS.
+ *        The threshold is a choice (what one workgroup's LDS pass holds), NOT measured.
+ *      Enqueue only: no allocation, no synchronisation, no memset node (the kernels zero what they count in); capturable into a
+ *      hipGraph, and a captured graph stays valid when the ids change.  Nothing outside the four outputs and workspace_bytes of
+ *      the workspace is written.
+ *      Status, decided before any device work: a null pointer (a null workspace only when the size is non-zero) or
+ *      workspace_bytes below the size: SM_STATUS_INVALID_VALUE; P > 2^31 - 1 or groups > SM_LINEAR24_MAX_GROUPS:
+ *      SM_STATUS_NOT_SUPPORTED; groups == 0: success, nothing enqueued; tokens == 0 or top_k == 0: the groups + 1 zeros are written,
+ *      nothing else.  Not covered: int64 ids, capacity limits that drop overflow tokens. */
+#define SM_MOE_ROUTE_FORM_INVALID 0
+#define SM_MOE_ROUTE_FORM_EMPTY 1
+#define SM_MOE_ROUTE_FORM_SINGLE 2
+#define SM_MOE_ROUTE_FORM_MULTI 3
+#define SM_MOE_ROUTE_SINGLE_MAX_PAIRS 4096
+#define SM_MOE_ROUTE_CHUNK 4096
+int sm_moe_route_workspace_size(size_t tokens, size_t top_k, size_t groups, size_t* bytes);
+int sm_moe_route(const int* expert_ids, size_t tokens, size_t top_k, size_t groups, int* group_offsets, int* sorted_token, int* sorted_pair,
+                 int* pair_pos, void* workspace, size_t workspace_bytes, sm_stream_t stream);
+int sm_moe_route_form(size_t tokens, size_t top_k, size_t groups, int* form);
+
+/* ---- MoE combine (extension): the un-permute and the weighted sum over top_k, fp16 / bf16.
+ *      Yp[rows_p][hidden] (ldp): one row per routed pair in sorted order (the down projection's output); pair_pos[P], P = tokens * top_k
+ *      (sm_moe_route's); weights[P] fp32 in pair order, or NULL; R[tokens][hidden] (ldo) or NULL; out[tokens][hidden] (ldo).
+ *      Per output element, all in fp32:  s = R[t][h], or +0 without R;  for j = 0 .. top_k - 1 ascending: pos = pair_pos[t * top_k + j],
+ *      the pair is skipped when pos < 0 or pos >= rows_p, else q = w * y (q = y when weights is NULL), s = s + q;  then ONE rounding to
+ *      nearest even to the output type.  q = w * y is one fp32 multiply and s = s + q one fp32 add, never contracted into an fma.  A
+ *      token with every pair dropped gives R, or +0.  No atomics: the same bits on every run.  R == out is allowed (in place).
+ *      Forms (sm_moe_combine_form; the entry points switch on it): SM_MOE_COMBINE_FORM_VEC, 16-byte accesses, when hidden % 8 == 0,
+ *      ldp % 8 == 0, ldo % 8 == 0 and Yp, R and out are 16-byte aligned (a NULL R counts as aligned); _SCALAR otherwise; _EMPTY
+ *      hidden == 0; _INVALID a null Yp or out, ldp < hidden, ldo < hidden or a dimension >= 2^31.
+ *      Status: a null Yp, pair_pos or out, ldp < hidden or ldo < hidden: SM_STATUS_INVALID_VALUE; P or a dimension >= 2^31:
+ *      SM_STATUS_NOT_SUPPORTED; tokens, top_k or hidden == 0: success, nothing enqueued.  Enqueue only, capturable.
+ *      Not covered: an fp32 Yp, an fp8-quantised out. */
+#define SM_MOE_COMBINE_FORM_INVALID 0
+#define SM_MOE_COMBINE_FORM_EMPTY 1
+#define SM_MOE_COMBINE_FORM_SCALAR 2
+#define SM_MOE_COMBINE_FORM_VEC 3
+int sm_moe_combine_f16(const void* Yp, const int* pair_pos, const float* weights, const void* R, void* out, size_t tokens, size_t top_k,
+                       size_t hidden, size_t rows_p, size_t ldp, size_t ldo, sm_stream_t stream);
+int sm_moe_combine_bf16(const void* Yp, const int* pair_pos, const float* weights, const void* R, void* out, size_t tokens, size_t top_k,
+                        size_t hidden, size_t rows_p, size_t ldp, size_t ldo, sm_stream_t stream);
+int sm_moe_combine_form(const void* Yp, const void* R, const void* out, size_t hidden, size_t ldp, size_t ldo, int* form);
 
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +

@@ -182,6 +182,17 @@ for _sfx16 in ("f16", "bf16", "fp8"):
     _SIGS["sm_linear24_grouped_" + _sfx16] = _SIGS["sm_linear24_" + _sfx16][:3] + [_c_ptr, _c_size] + _SIGS["sm_linear24_" + _sfx16][3:]
     _SIGS["sm_linear24_grouped_glu_" + _sfx16] = _SIGS["sm_linear24_glu_" + _sfx16][:3] + [_c_ptr, _c_size] + _SIGS["sm_linear24_glu_" + _sfx16][3:]
 _SIGS["sm_linear24_grouped_form"] = [_c_size] * 5 + [ctypes.POINTER(_c_i)]
+# ... with X gathered through a row index: (x_index, x_rows) directly after group_offsets
+for _sfx16 in ("f16", "bf16", "fp8"):
+    for _g in ("sm_linear24_grouped_", "sm_linear24_grouped_glu_"):
+        _SIGS[_g + "gather_" + _sfx16] = _SIGS[_g + _sfx16][:4] + [_c_ptr, _c_size] + _SIGS[_g + _sfx16][4:]
+# MoE routing (moe_route.hip) and combine (moe_combine.hip)
+_SIGS["sm_moe_route_workspace_size"] = [_c_size] * 3 + [ctypes.POINTER(_c_size)]
+_SIGS["sm_moe_route"] = [_c_ptr] + [_c_size] * 3 + [_c_ptr] * 5 + [_c_size, _c_ptr]
+_SIGS["sm_moe_route_form"] = [_c_size] * 3 + [ctypes.POINTER(_c_i)]
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_moe_combine_" + _sfx16] = [_c_ptr] * 5 + [_c_size] * 6 + [_c_ptr]
+_SIGS["sm_moe_combine_form"] = [_c_ptr] * 3 + [_c_size] * 3 + [ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -599,11 +610,22 @@ def _group_offsets(group_offsets, what):
     return _dev(group_offsets)
 
 
+def _x_index(x_index, x_rows, what):
+    """(x_index, x_rows) of the gathered forms as ctypes arguments; x_rows=None is not guessed (X's buffer may hold guard rows)."""
+    if x_index.dtype != _t().int32:
+        raise SparsifymeError(f"{what}: x_index is int32, not {x_index.dtype}")
+    if x_rows is None:
+        raise SparsifymeError(f"{what}: x_rows (the rows of X) is required with x_index")
+    return [_dev(x_index), x_rows]
+
+
 def linear24_grouped(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, ldx=None, ldy=None, alpha=1.0, beta=0.0,
-                     epilogue=None):
+                     epilogue=None, x_index=None, x_rows=None):
     """linear24 per expert in one launch (sm_linear24_grouped_*): blob is that of the stacked W[groups * out][in], the tokens of X
     and Y are sorted by expert, and group_offsets (groups + 1 int32 values on the device, never copied to the host) says where each
-    expert's rows begin.  A "col" bias holds groups * out values, expert-major; a "row" bias and the residual are in Y's rows."""
+    expert's rows begin.  A "col" bias holds groups * out values, expert-major; a "row" bias and the residual are in Y's rows.
+    x_index (tokens int32 values on the device) with x_rows: the gathered form (sm_linear24_grouped_gather_*), row t of Y reads row
+    x_index[t] of X's x_rows rows; the same for the three grouped wrappers below."""
     torch = _t()
     if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
         raise SparsifymeError(f"linear24_grouped: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
@@ -611,15 +633,16 @@ def linear24_grouped(blob, X, Y, group_offsets, groups, tokens, out_features, in
     ldx = in_features if ldx is None else ldx
     ldy = out_features if ldy is None else ldy
     st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
-    fn = getattr(lib(), "sm_linear24_grouped_" + _sfx(X))
-    _check(fn(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta),
+    gather = _x_index(x_index, x_rows, "linear24_grouped") if x_index is not None else []
+    fn = getattr(lib(), "sm_linear24_grouped_" + ("gather_" if gather else "") + _sfx(X))
+    _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta),
               ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24_grouped")
 
 
 def linear24_grouped_fp8(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, w_dtype=None, ldx=None, ldy=None, alpha=1.0,
-                         beta=0.0, w_scale=None, x_scale=None, epilogue=None):
+                         beta=0.0, w_scale=None, x_scale=None, epilogue=None, x_index=None, x_rows=None):
     """linear24_fp8 per expert in one launch (sm_linear24_grouped_fp8); w_scale: groups * out float32 values, expert-major; x_scale:
-    tokens values in Y's rows."""
+    tokens values in Y's rows (gathered: x_rows values in X's rows)."""
     fx = fp8_format(X.dtype)
     fw = fx if w_dtype is None else fp8_format(w_dtype)
     ot = _fp8_out_type(Y)
@@ -630,13 +653,16 @@ def linear24_grouped_fp8(blob, X, Y, group_offsets, groups, tokens, out_features
     ldx = in_features if ldx is None else ldx
     ldy = out_features if ldy is None else ldy
     st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
-    _check(lib().sm_linear24_grouped_fp8(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, out_features, in_features, ldx, ldy, fw, fx, ot,
-                                         float(alpha), float(beta), _dev(w_scale) if w_scale is not None else None,
-                                         _dev(x_scale) if x_scale is not None else None, ctypes.addressof(st) if st is not None else None,
-                                         _stream()), "sm_linear24_grouped_fp8")
+    gather = _x_index(x_index, x_rows, "linear24_grouped_fp8") if x_index is not None else []
+    fn = lib().sm_linear24_grouped_gather_fp8 if gather else lib().sm_linear24_grouped_fp8
+    _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, out_features, in_features, ldx, ldy, fw, fx, ot,
+              float(alpha), float(beta), _dev(w_scale) if w_scale is not None else None,
+              _dev(x_scale) if x_scale is not None else None, ctypes.addressof(st) if st is not None else None,
+              _stream()), "sm_linear24_grouped_fp8")
 
 
-def linear24_grouped_glu(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, act="silu", bias=None, ldx=None, ldy=None):
+def linear24_grouped_glu(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, act="silu", bias=None, ldx=None, ldy=None,
+                         x_index=None, x_rows=None):
     """linear24_glu per expert in one launch (sm_linear24_grouped_glu_*): blob is that of W[groups][2 hidden][in], each expert's gate
     rows then its up rows; bias: groups * 2 * hidden float32 values in the same order, or None."""
     torch = _t()
@@ -646,12 +672,13 @@ def linear24_grouped_glu(blob, X, Y, group_offsets, groups, tokens, hidden, in_f
     off = _group_offsets(group_offsets, "linear24_grouped_glu")
     ldx = in_features if ldx is None else ldx
     ldy = hidden if ldy is None else ldy
-    fn = getattr(lib(), "sm_linear24_grouped_glu_" + _sfx(X))
-    _check(fn(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, hidden, in_features, ldx, ldy, a, b, _stream()), "sm_linear24_grouped_glu")
+    gather = _x_index(x_index, x_rows, "linear24_grouped_glu") if x_index is not None else []
+    fn = getattr(lib(), "sm_linear24_grouped_glu_" + ("gather_" if gather else "") + _sfx(X))
+    _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, hidden, in_features, ldx, ldy, a, b, _stream()), "sm_linear24_grouped_glu")
 
 
 def linear24_grouped_glu_fp8(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, act="silu", w_dtype=None, w_scale=None,
-                             x_scale=None, bias=None, ldx=None, ldy=None):
+                             x_scale=None, bias=None, ldx=None, ldy=None, x_index=None, x_rows=None):
     """linear24_glu_fp8 per expert in one launch (sm_linear24_grouped_glu_fp8); w_scale and bias: groups * 2 * hidden float32 values."""
     fx = fp8_format(X.dtype)
     fw = fx if w_dtype is None else fp8_format(w_dtype)
@@ -663,9 +690,11 @@ def linear24_grouped_glu_fp8(blob, X, Y, group_offsets, groups, tokens, hidden, 
     off = _group_offsets(group_offsets, "linear24_grouped_glu_fp8")
     ldx = in_features if ldx is None else ldx
     ldy = hidden if ldy is None else ldy
-    _check(lib().sm_linear24_grouped_glu_fp8(_dev(blob), _dev(X), _dev(Y), off, groups, tokens, hidden, in_features, ldx, ldy, fw, fx, ot, a,
-                                             _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None,
-                                             b, _stream()), "sm_linear24_grouped_glu_fp8")
+    gather = _x_index(x_index, x_rows, "linear24_grouped_glu_fp8") if x_index is not None else []
+    fn = lib().sm_linear24_grouped_glu_gather_fp8 if gather else lib().sm_linear24_grouped_glu_fp8
+    _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, hidden, in_features, ldx, ldy, fw, fx, ot, a,
+              _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None,
+              b, _stream()), "sm_linear24_grouped_glu_fp8")
 
 
 def linear24_grouped_form(tokens, groups, out_features, in_features, cus=0):
@@ -674,6 +703,65 @@ def linear24_grouped_form(tokens, groups, out_features, in_features, cus=0):
     form = _c_i(-1)
     _check(lib().sm_linear24_grouped_form(tokens, groups, out_features, in_features, cus, ctypes.byref(form)), "sm_linear24_grouped_form")
     return LINEAR24_FORMS[form.value]
+
+
+# include/sparsifyme.h: SM_MOE_ROUTE_FORM_*, SM_MOE_COMBINE_FORM_* (index = value), the SINGLE limit and the MULTI chunk
+MOE_ROUTE_FORMS = ("invalid", "empty", "single", "multi")
+MOE_COMBINE_FORMS = ("invalid", "empty", "scalar", "vec")
+MOE_ROUTE_SINGLE_MAX_PAIRS = 4096
+MOE_ROUTE_CHUNK = 4096
+
+
+def moe_route_form(tokens, top_k, groups):
+    """The name (MOE_ROUTE_FORMS) of the form moe_route runs -- sm_moe_route_form, the rule the entry point switches on.  Host only."""
+    form = _c_i(-1)
+    _check(lib().sm_moe_route_form(tokens, top_k, groups, ctypes.byref(form)), "sm_moe_route_form")
+    return MOE_ROUTE_FORMS[form.value]
+
+
+def moe_route_workspace_size(tokens, top_k, groups):
+    """Bytes of workspace moe_route needs (0 for the single form).  Host only."""
+    n = _c_size(0)
+    _check(lib().sm_moe_route_workspace_size(tokens, top_k, groups, ctypes.byref(n)), "sm_moe_route_workspace_size")
+    return n.value
+
+
+def moe_route(expert_ids, tokens, top_k, groups, group_offsets, sorted_token, sorted_pair, pair_pos, workspace=None):
+    """The router's ids (int32 [tokens * top_k]) to group_offsets [groups + 1], sorted_token / sorted_pair [P] and pair_pos [P], all int32
+    on the device: a stable counting sort by expert, ids outside [0, groups) dropped (sm_moe_route).  workspace: a device tensor of at
+    least moe_route_workspace_size bytes, or None where that is 0."""
+    for name, v in (("expert_ids", expert_ids), ("group_offsets", group_offsets), ("sorted_token", sorted_token), ("sorted_pair", sorted_pair),
+                    ("pair_pos", pair_pos)):
+        if v.dtype != _t().int32:
+            raise SparsifymeError(f"moe_route: {name} is int32, not {v.dtype}")
+    ws = _dev(workspace) if workspace is not None else None
+    nb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    _check(lib().sm_moe_route(_dev(expert_ids), tokens, top_k, groups, _dev(group_offsets), _dev(sorted_token), _dev(sorted_pair), _dev(pair_pos),
+                              ws, nb, _stream()), "sm_moe_route")
+
+
+def moe_combine(Yp, pair_pos, out, tokens, top_k, hidden, rows_p, weights=None, residual=None, ldp=None, ldo=None):
+    """out[t] = round(residual[t] + sum_j weights[t top_k + j] * Yp[pair_pos[t top_k + j]]) in fp32, j ascending, multiply and add not
+    contracted, one rounding (sm_moe_combine_*): Yp and out both float16 or both bfloat16; weights float32 or None; residual of out's
+    type and ldo (out itself: in place) or None; pairs with pair_pos < 0 or >= rows_p are skipped."""
+    torch = _t()
+    if Yp.dtype not in (torch.float16, torch.bfloat16) or out.dtype != Yp.dtype or (residual is not None and residual.dtype != Yp.dtype):
+        raise SparsifymeError(f"moe_combine: Yp, out and residual are all float16 or all bfloat16, not {Yp.dtype} and {out.dtype}")
+    if pair_pos.dtype != torch.int32 or (weights is not None and weights.dtype != torch.float32):
+        raise SparsifymeError("moe_combine: pair_pos is int32 and weights float32")
+    ldp = hidden if ldp is None else ldp
+    ldo = hidden if ldo is None else ldo
+    fn = getattr(lib(), "sm_moe_combine_" + _sfx(Yp))
+    _check(fn(_dev(Yp), _dev(pair_pos), _dev(weights) if weights is not None else None, _dev(residual) if residual is not None else None,
+              _dev(out), tokens, top_k, hidden, rows_p, ldp, ldo, _stream()), "sm_moe_combine")
+
+
+def moe_combine_form(Yp, residual, out, hidden, ldp, ldo):
+    """The name (MOE_COMBINE_FORMS) of the form moe_combine runs -- sm_moe_combine_form; Yp / residual / out: tensors, addresses or None."""
+    ptr = lambda v: None if v is None else ctypes.c_void_p(v if isinstance(v, int) else v.data_ptr())
+    form = _c_i(-1)
+    _check(lib().sm_moe_combine_form(ptr(Yp), ptr(residual), ptr(out), hidden, ldp, ldo, ctypes.byref(form)), "sm_moe_combine_form")
+    return MOE_COMBINE_FORMS[form.value]
 
 
 def spmma_fused_i8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, accumulate=False, scale=None):

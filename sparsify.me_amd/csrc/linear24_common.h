@@ -74,10 +74,14 @@ inline int linear24_grouped_glu_form(size_t tokens, size_t groups, size_t hidden
   return linear24_grouped_form(tokens, groups, 2 * hidden, in, cus);
 }
 
-// What a grouped entry point adds to the argument checks below: the offsets (device) and the group count.
+// What a grouped entry point adds to the argument checks below: the offsets (device) and the group count; and a gathered one
+// (sm_linear24_grouped_*gather_*) the row index of X (device) and X's row count.
 struct Linear24Groups {
   const int* offsets;
   size_t groups;
+  bool gather;         // x_index / x_rows are read (and checked) only when set
+  const int* x_index;  // tokens values, device
+  size_t x_rows;
 };
 
 // What the shared pieces read of a launch; each front end's argument block adds its X and its K extent.
@@ -107,11 +111,12 @@ inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool 
   *run = false;
   bool plain;  // (not used: a plain epilogue takes the same kernels, whose bias / activation steps are skipped at run time)
   if (const int rc = epilogue_args(ep, Y, 0, out, beta, a.e, &plain, who)) return rc;
-  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < out || (grp && !grp->offsets)) {
+  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < out || (grp && !grp->offsets) ||
+      (grp && grp->gather && (!grp->x_index || grp->x_rows == 0))) {
     set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < out_features)", who, extra);
     return SM_STATUS_INVALID_VALUE;
   }
-  if (tokens > 0x7fffffffull || out > 0x7fffffffull || in > 0x7fffffffull) {
+  if (tokens > 0x7fffffffull || out > 0x7fffffffull || in > 0x7fffffffull || (grp && grp->gather && grp->x_rows > 0x7fffffffull)) {
     set_error("%s: dimension exceeds 2^31-1", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
@@ -146,11 +151,12 @@ inline int linear24_glu_args(Linear24Core& a, bool* run, const char* who, bool e
     set_error("%s: invalid argument (act is not SM_GLU_ACT_*)", who);
     return SM_STATUS_INVALID_VALUE;
   }
-  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < hidden || (grp && !grp->offsets)) {
+  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < hidden || (grp && !grp->offsets) ||
+      (grp && grp->gather && (!grp->x_index || grp->x_rows == 0))) {
     set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < hidden)", who, extra);
     return SM_STATUS_INVALID_VALUE;
   }
-  if (tokens > 0x7fffffffull || hidden > LINEAR24_GLU_MAX_HIDDEN || in > 0x7fffffffull) {
+  if (tokens > 0x7fffffffull || hidden > LINEAR24_GLU_MAX_HIDDEN || in > 0x7fffffffull || (grp && grp->gather && grp->x_rows > 0x7fffffffull)) {
     set_error("%s: dimension exceeds 2^31-1 (tokens, in_features, 2 * hidden)", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
@@ -210,11 +216,14 @@ static int launch_linear24_decode(const Args& a, hipStream_t st, const char* ker
 }
 
 // The argument block of a GROUPED tile kernel: the front end's own block + the offsets.  The plain instantiations keep taking the
-// front end's block itself, so their code is what it was.
+// front end's block itself, so their code is what it was.  x_index / x_rows: read by the GATHER instantiations only (row t of Y reads
+// row clamp(x_index[t], 0, x_rows - 1) of X); the others never load them.
 template <class Args>
 struct Linear24Grouped : Args {
   const int* group_offsets;  // groups + 1 values, device
   int groups;
+  int x_rows;
+  const int* x_index;        // tokens values, device, or null
 };
 template <class Args, bool GROUPED> struct Linear24ArgsSel { typedef Args type; typedef const Args& view_t; };
 template <class Args> struct Linear24ArgsSel<Args, true> { typedef Linear24Grouped<Args> type; typedef Args view_t; };
@@ -226,6 +235,8 @@ static int launch_linear24_tile_grouped(const Args& a0, const Linear24Groups& gr
   static_cast<Args&>(a) = a0;
   a.group_offsets = grp.offsets;
   a.groups = (int)grp.groups;
+  a.x_rows = grp.gather ? (int)grp.x_rows : 0;
+  a.x_index = grp.gather ? grp.x_index : nullptr;
   a.tiles_m = (a.out + BM - 1) / BM;
   a.tiles_n = (int)linear24_grouped_slots((size_t)a.tokens, grp.groups, BN);
   return launch_linear24_grid<Linear24Grouped<Args>, KERNEL, NT, LDS>(a, st, who, kernel_name);
@@ -298,6 +309,13 @@ __device__ __forceinline__ bool linear24_group_view(Args& p, const int* off, int
 // half of the 256-byte bank line and (t >> 1) the slot, the 16 lanes cover 16 different 16-byte slots -- all 64 banks once
 // (4.14 for the same reads over bytes).
 __device__ __forceinline__ unsigned x_swz(unsigned t) { return (t >> 1) & 7u; }
+
+// The row of X behind sorted token row t (< tokens) of a GATHER instantiation: x_index[t] clamped into [0, x_rows), so that whatever
+// the array holds no byte outside the x_rows rows of X (and of the fp8 layers' x_scale) is read.
+__device__ __forceinline__ unsigned linear24_gather_row(const int* x_index, int x_rows, unsigned t) {
+  const int v = x_index[t];
+  return (unsigned)(v < 0 ? 0 : (v < x_rows ? v : x_rows - 1));
+}
 
 // the lane's four per-out-feature values of a vector (bias, w_scale); indices past the edge are clamped, not branched round (their
 // outputs are never stored), so that the loads stay in flight under the K loop

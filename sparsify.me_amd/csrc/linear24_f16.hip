@@ -25,6 +25,8 @@ static const char* const LINEAR24_F16_WHO = "sm_linear24_{f16,bf16}";
 static const char* const LINEAR24_GLU16_WHO = "sm_linear24_glu_{f16,bf16}";
 static const char* const LINEAR24_GROUPED16_WHO = "sm_linear24_grouped_{f16,bf16}";
 static const char* const LINEAR24_GROUPED_GLU16_WHO = "sm_linear24_grouped_glu_{f16,bf16}";
+static const char* const LINEAR24_GATHER16_WHO = "sm_linear24_grouped_gather_{f16,bf16}";
+static const char* const LINEAR24_GATHER_GLU16_WHO = "sm_linear24_grouped_glu_gather_{f16,bf16}";
 
 struct Linear24Args : Linear24Core {  // vals stage-major [in/64][out][64 B]
   const half_t* X;
@@ -87,7 +89,9 @@ __device__ __forceinline__ void linear24_stage(const char* As, const char* Ms, c
 // GROUPED (sm_linear24_grouped_*): tiles_n counts token-tile SLOTS, the grid's bound; the workgroup finds its expert, out tile and token
 // tile in group_offsets (linear24_group_view), returns when it is past the last real tile, and else runs this body on the block cut down
 // to its expert.
-template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU = false, bool GROUPED = false>
+// GATHER (sm_linear24_grouped_*gather_*, GROUPED only): the X rows of the tile are those x_index names (linear24_gather_row), fetched by
+// the lanes that issue the X DMA, once, ahead of the first stage; Y, R and a per-token bias stay in the sorted rows.
+template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU = false, bool GROUPED = false, bool GATHER = false>
 __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const typename Linear24ArgsSel<Linear24Args, GROUPED>::type pk) {
   typename Linear24ArgsSel<Linear24Args, GROUPED>::view_t p = pk;
   constexpr int NW = WM * WN;
@@ -95,6 +99,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const typen
   static_assert(FM >= 1 && FN >= 1 && BM % 32 == 0 && BN % 8 == 0, "tile");
   static_assert(!GLU || FM % 2 == 0, "a wave of a gated tile holds whole (gate, up) fragment pairs");
   static_assert(NS >= 2 && NS <= 4, "ring depth");
+  static_assert(GROUPED || !GATHER, "the gathered layers are grouped layers");
   constexpr int SA = BM * 64, SM_ = BM * 8, SX = BN * 128, STAGE = SA + SM_ + SX;
   constexpr int A_N = BM / 16, M_N = BM / 32, X_N = BN / 8, W = A_N + M_N + X_N;
   constexpr int SL = (W + NW - 1) / NW;  // DMA slots per wave
@@ -168,6 +173,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_tile_kernel(const typen
       const unsigned j = t - (A_N + M_N), row = 8u * j + (lane >> 3), cs = (lane & 7u) ^ x_swz(row);
       unsigned gt = n0 + row;
       gt = gt < tlast ? gt : tlast;
+      if constexpr (GATHER) gt = linear24_gather_row(pk.x_index, pk.x_rows, gt);
       src[i] = reinterpret_cast<const char*>(p.X + (size_t)gt * p.ldx + 8u * cs);
       step[i] = 128;
       loff[i] = SA + SM_ + j * 1024u;
@@ -311,11 +317,10 @@ static int launch_linear24_tile16(const Linear24Args& a, hipStream_t st) {
                               (size_t)NS * (BM * 72 + BN * 128)>(a, st, GLU ? LINEAR24_GLU16_WHO : LINEAR24_F16_WHO, "linear24_tile_kernel");
 }
 
-template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU>
-static int launch_linear24_tile16_grouped(const Linear24Args& a, const Linear24Groups& grp, hipStream_t st) {
-  return launch_linear24_tile_grouped<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF, GLU, true>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
-                                      (size_t)NS * (BM * 72 + BN * 128)>(a, grp, st, GLU ? LINEAR24_GROUPED_GLU16_WHO : LINEAR24_GROUPED16_WHO,
-                                                                         "linear24_tile_kernel");
+template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU, bool GATHER>
+static int launch_linear24_tile16_grouped(const Linear24Args& a, const Linear24Groups& grp, hipStream_t st, const char* who) {
+  return launch_linear24_tile_grouped<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF, GLU, true, GATHER>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                                      (size_t)NS * (BM * 72 + BN * 128)>(a, grp, st, who, "linear24_tile_kernel");
 }
 
 }  // namespace sm
@@ -381,65 +386,94 @@ extern "C" int sm_linear24_glu_bf16(const void* blob, const void* X, void* Y, si
   return linear24_glu<true>(blob, X, Y, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
 }
 
-// ---- the grouped layers: `groups` experts of one shape behind one launch (the GROUPED instantiations of the tile kernels) ----------
-template <bool BF>
-static int linear24_grouped(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t out, size_t in,
-                            size_t ldx, size_t ldy, float alpha, float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
+// ---- the grouped layers: `groups` experts of one shape behind one launch (the GROUPED instantiations of the tile kernels); GATHER: the
+// same with X read through x_index (sm_linear24_grouped_*gather_*: grp.gather set, the GATHER instantiations) -------------------------
+template <bool BF, bool GATHER>
+static int linear24_grouped(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t out, size_t in, size_t ldx,
+                            size_t ldy, float alpha, float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
+  const char* who = GATHER ? LINEAR24_GATHER16_WHO : LINEAR24_GROUPED16_WHO;
+  const size_t groups = grp.groups;
   Linear24Args a = {};
-  const Linear24Groups grp = {group_offsets, groups};
   bool run;
-  const int rc = linear24_core_args(a, &run, LINEAR24_GROUPED16_WHO, true, "null group_offsets, ", blob, X, Y, tokens, out, in, ldx, ldy, 2, 8, alpha, beta,
-                                    ep, &grp);
+  const int rc = linear24_core_args(a, &run, who, true, GATHER ? "null group_offsets, null x_index, x_rows == 0, " : "null group_offsets, ", blob, X, Y, tokens,
+                                    out, in, ldx, ldy, 2, 8, alpha, beta, ep, &grp);
   if (rc != SM_STATUS_SUCCESS || !run) return rc;
   a.X = (const half_t*)X;
   a.nkt = (int)(in / 64);
   hipStream_t st = (hipStream_t)stream;
   switch (linear24_grouped_form(tokens, groups, out, in, LINEAR24_F16_CUS)) {
-    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, false>(a, grp, st);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, false>(a, grp, st);
-    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, false>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, false, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, false, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, false, GATHER>(a, grp, st, who);
   }
-  set_error("%s: grid too large", LINEAR24_GROUPED16_WHO);
+  set_error("%s: grid too large", who);
   return SM_STATUS_NOT_SUPPORTED;
 }
 
 extern "C" int sm_linear24_grouped_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                        size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha, float beta,
                                        const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24_grouped<false>(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue, stream);
+  return linear24_grouped<false, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue,
+                                        stream);
 }
 extern "C" int sm_linear24_grouped_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                         size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha, float beta,
                                         const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24_grouped<true>(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue, stream);
+  return linear24_grouped<true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue,
+                                       stream);
+}
+extern "C" int sm_linear24_grouped_gather_f16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                              size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha,
+                                              float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return linear24_grouped<false, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx, ldy,
+                                       alpha, beta, epilogue, stream);
+}
+extern "C" int sm_linear24_grouped_gather_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                               size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha,
+                                               float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return linear24_grouped<true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx, ldy,
+                                      alpha, beta, epilogue, stream);
 }
 
-template <bool BF>
-static int linear24_grouped_glu(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
-                                size_t in, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
+template <bool BF, bool GATHER>
+static int linear24_grouped_glu(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t hidden, size_t in, size_t ldx,
+                                size_t ldy, int act, const float* bias, sm_stream_t stream) {
+  const char* who = GATHER ? LINEAR24_GATHER_GLU16_WHO : LINEAR24_GROUPED_GLU16_WHO;
+  const size_t groups = grp.groups;
   Linear24Args a = {};
-  const Linear24Groups grp = {group_offsets, groups};
   bool run;
-  const int rc = linear24_glu_args(a, &run, LINEAR24_GROUPED_GLU16_WHO, true, "null group_offsets, ", blob, X, Y, tokens, hidden, in, ldx, ldy, 2, 8, act,
-                                   bias, &grp);
+  const int rc = linear24_glu_args(a, &run, who, true, GATHER ? "null group_offsets, null x_index, x_rows == 0, " : "null group_offsets, ", blob, X, Y, tokens,
+                                   hidden, in, ldx, ldy, 2, 8, act, bias, &grp);
   if (rc != SM_STATUS_SUCCESS || !run) return rc;
   a.X = (const half_t*)X;
   a.nkt = (int)(in / 64);
   hipStream_t st = (hipStream_t)stream;
   switch (linear24_grouped_glu_form(tokens, groups, hidden, in, LINEAR24_F16_CUS)) {
-    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, true>(a, grp, st);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, true>(a, grp, st);
-    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, true>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, true, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, true, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, true, GATHER>(a, grp, st, who);
   }
-  set_error("%s: grid too large", LINEAR24_GROUPED_GLU16_WHO);
+  set_error("%s: grid too large", who);
   return SM_STATUS_NOT_SUPPORTED;
 }
 
 extern "C" int sm_linear24_grouped_glu_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                            size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
-  return linear24_grouped_glu<false>(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+  return linear24_grouped_glu<false, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
 }
 extern "C" int sm_linear24_grouped_glu_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                             size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
-  return linear24_grouped_glu<true>(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+  return linear24_grouped_glu<true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+}
+extern "C" int sm_linear24_grouped_glu_gather_f16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                                  size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act,
+                                                  const float* bias, sm_stream_t stream) {
+  return linear24_grouped_glu<false, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy,
+                                           act, bias, stream);
+}
+extern "C" int sm_linear24_grouped_glu_gather_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                                   size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act,
+                                                   const float* bias, sm_stream_t stream) {
+  return linear24_grouped_glu<true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy,
+                                          act, bias, stream);
 }

@@ -28,6 +28,8 @@ static const char* const LINEAR24_FP8_WHO = "sm_linear24_fp8";
 static const char* const LINEAR24_GLU8_WHO = "sm_linear24_glu_fp8";
 static const char* const LINEAR24_GROUPED8_WHO = "sm_linear24_grouped_fp8";
 static const char* const LINEAR24_GROUPED_GLU8_WHO = "sm_linear24_grouped_glu_fp8";
+static const char* const LINEAR24_GATHER8_WHO = "sm_linear24_grouped_gather_fp8";
+static const char* const LINEAR24_GATHER_GLU8_WHO = "sm_linear24_grouped_glu_gather_fp8";
 
 struct Linear8Args : Linear24Core {  // vals plane-major [in/64][out][32 B]
   size_t Mtot;  // rows of the blob (= out; the gated kernels: 2 * out)
@@ -70,7 +72,9 @@ __device__ __forceinline__ void linear8_store_glu_any(const Linear8Args& p, cons
 // is `hidden`, the width of Y, and the blob has p.Mtot = 2 * p.out rows.
 // GROUPED (sm_linear24_grouped_*fp8): as in linear24_tile_kernel -- slots for tiles_n (the grid's bound), linear24_group_view, then this body on expert
 // g's own rows of the stacked blob (p.Mtot = groups * rows of one expert: the plane stride).
-template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU = false, bool GROUPED = false>
+// GATHER (sm_linear24_grouped_*gather_fp8, GROUPED only): as in linear24_tile_kernel, the X rows are those x_index names; x_scale is read
+// at the same source row (the scale belongs to the token that was quantised), a per-token bias stays in Y's sorted rows.
+template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU = false, bool GROUPED = false, bool GATHER = false>
 __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const typename Linear24ArgsSel<Linear8Args, GROUPED>::type pk) {
   typename Linear24ArgsSel<Linear8Args, GROUPED>::view_t p = pk;
   constexpr int NW = WM * WN;
@@ -78,6 +82,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const t
   static_assert(FM >= 1 && FN >= 1 && BM % 32 == 0 && BN % 8 == 0, "tile");
   static_assert(!GLU || FM % 2 == 0, "a wave of a gated tile holds whole (gate, up) fragment pairs");
   static_assert(NS >= 2 && NS <= 4, "ring depth");
+  static_assert(GROUPED || !GATHER, "the gathered layers are grouped layers");
   constexpr int SA = BM * 64, SM_ = 2 * BM * 8, SX = BN * 128, STAGE = SA + SM_ + SX;
   constexpr int MB = BM / 32;  // metadata instructions per plane
   constexpr int A_N = BM / 16, M_N = 2 * MB, X_N = BN / 8, W = A_N + M_N + X_N;
@@ -120,7 +125,8 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const t
   for (int j = 0; j < FN; ++j) {
     const unsigned t = n0 + (wn * TN + j * 16 + r), tc = t < tlast ? t : tlast;
     bt[j] = bias_tok ? p.e.bias[tc] : 0.f;
-    xs[j] = has_xs ? p.x_scale[tc] : 1.f;
+    if constexpr (GATHER) xs[j] = has_xs ? p.x_scale[linear24_gather_row(pk.x_index, pk.x_rows, tc)] : 1.f;
+    else xs[j] = has_xs ? p.x_scale[tc] : 1.f;
   }
 
   // per slot: source of stage 0, LDS offset, and whether the lane's piece belongs to the stage's second plane / half.  Slot i of
@@ -153,6 +159,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear24_fp8_tile_kernel(const t
       const unsigned j = t - (A_N + M_N), row = 8u * j + (lane >> 3), cs = (lane & 7u) ^ x_swz(row);
       unsigned gt = n0 + row;
       gt = gt < tlast ? gt : tlast;
+      if constexpr (GATHER) gt = linear24_gather_row(pk.x_index, pk.x_rows, gt);
       src[i] = reinterpret_cast<const char*>(p.X + (size_t)gt * p.ldx) + 16u * cs;
       loff[i] = SA + SM_ + j * 1024u;
       second[i] = cs >= 4u;  // k 64 .. 127 of the stage
@@ -320,30 +327,29 @@ static int launch_linear8_tile(const Linear8Args& a, hipStream_t st) {
                               (size_t)NS * (BM * 80 + BN * 128)>(a, st, GLU ? LINEAR24_GLU8_WHO : LINEAR24_FP8_WHO, "linear24_fp8_tile_kernel");
 }
 
-template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU>
-static int launch_linear8_tile_grouped(const Linear8Args& a, const Linear24Groups& grp, hipStream_t st) {
-  return launch_linear24_tile_grouped<Linear8Args, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS, GLU, true>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
-                                      (size_t)NS * (BM * 80 + BN * 128)>(a, grp, st, GLU ? LINEAR24_GROUPED_GLU8_WHO : LINEAR24_GROUPED8_WHO,
-                                                                         "linear24_fp8_tile_kernel");
+template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU, bool GATHER>
+static int launch_linear8_tile_grouped(const Linear8Args& a, const Linear24Groups& grp, hipStream_t st, const char* who) {
+  return launch_linear24_tile_grouped<Linear8Args, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS, GLU, true, GATHER>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                                      (size_t)NS * (BM * 80 + BN * 128)>(a, grp, st, who, "linear24_fp8_tile_kernel");
 }
 
-template <int FW, int FX, bool GLU>
-static int linear8_launch_grouped(const Linear8Args& a, const Linear24Groups& grp, int form, hipStream_t st) {
+template <int FW, int FX, bool GLU, bool GATHER>
+static int linear8_launch_grouped(const Linear8Args& a, const Linear24Groups& grp, int form, hipStream_t st, const char* who) {
   typedef MmaF8<FW, FX> MM;
   switch (form) {
-    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile_grouped<MM, 128, 128, 2, 2, 3, GLU>(a, grp, st);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile_grouped<MM, 128, 64, 4, 1, 3, GLU>(a, grp, st);
-    default: return launch_linear8_tile_grouped<MM, 64, 64, 2, 2, 3, GLU>(a, grp, st);
+    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile_grouped<MM, 128, 128, 2, 2, 3, GLU, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile_grouped<MM, 128, 64, 4, 1, 3, GLU, GATHER>(a, grp, st, who);
+    default: return launch_linear8_tile_grouped<MM, 64, 64, 2, 2, 3, GLU, GATHER>(a, grp, st, who);
   }
 }
 
-template <bool GLU>
-static int linear8_launch_grouped_fmt(const Linear8Args& a, const Linear24Groups& grp, int fmt_w, int fmt_x, int form, hipStream_t st) {
+template <bool GLU, bool GATHER>
+static int linear8_launch_grouped_fmt(const Linear8Args& a, const Linear24Groups& grp, int fmt_w, int fmt_x, int form, hipStream_t st, const char* who) {
   if (fmt_w == SM_FP8_E4M3)
-    return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E4M3, GLU>(a, grp, form, st)
-                                : linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E5M2, GLU>(a, grp, form, st);
-  return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E4M3, GLU>(a, grp, form, st)
-                              : linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E5M2, GLU>(a, grp, form, st);
+    return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E4M3, GLU, GATHER>(a, grp, form, st, who)
+                                : linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E5M2, GLU, GATHER>(a, grp, form, st, who);
+  return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E4M3, GLU, GATHER>(a, grp, form, st, who)
+                              : linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E5M2, GLU, GATHER>(a, grp, form, st, who);
 }
 
 template <int FW, int FX, bool GLU>
@@ -444,51 +450,84 @@ extern "C" int sm_linear24_grouped_form(size_t tokens, size_t groups, size_t out
   return SM_STATUS_SUCCESS;
 }
 
-extern "C" int sm_linear24_grouped_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
-                                       size_t out_features, size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, float alpha,
-                                       float beta, const float* w_scale, const float* x_scale, const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  const size_t out = out_features, in = in_features;
+template <bool GATHER>
+static int linear8_grouped(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy,
+                           int fmt_w, int fmt_x, int out_type, float alpha, float beta, const float* w_scale, const float* x_scale,
+                           const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  const char* who = GATHER ? LINEAR24_GATHER8_WHO : LINEAR24_GROUPED8_WHO;
   Linear8Args a = {};
-  const Linear24Groups grp = {group_offsets, groups};
   const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
   const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
   bool run;
-  const int rc = linear24_core_args(a, &run, LINEAR24_GROUPED8_WHO, fmt_ok && out_ok, "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob, X,
-                                    Y, tokens, out, in, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, alpha, beta, epilogue, &grp);
+  const int rc = linear24_core_args(a, &run, who, fmt_ok && out_ok,
+                                    GATHER ? "null group_offsets, null x_index, x_rows == 0, fmt not SM_FP8_*, out_type not SM_OUT_*, "
+                                           : "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ",
+                                    blob, X, Y, tokens, out, in, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, alpha, beta, epilogue, &grp);
   if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.Mtot = groups * out;
+  a.Mtot = grp.groups * out;
   a.X = (const uint8_t*)X;
   a.nplanes = (int)(in / 64);
   a.out_type = out_type;
   a.w_scale = w_scale; a.x_scale = x_scale;
-  const int form = linear24_grouped_form(tokens, groups, out, in, (size_t)device_cu_count());
+  const int form = linear24_grouped_form(tokens, grp.groups, out, in, (size_t)device_cu_count());
   if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
-    set_error("%s: grid too large", LINEAR24_GROUPED8_WHO);
+    set_error("%s: grid too large", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
-  return linear8_launch_grouped_fmt<false>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream);
+  return linear8_launch_grouped_fmt<false, GATHER>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream, who);
+}
+
+extern "C" int sm_linear24_grouped_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
+                                       size_t out_features, size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, float alpha,
+                                       float beta, const float* w_scale, const float* x_scale, const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return linear8_grouped<false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy, fmt_w, fmt_x, out_type, alpha,
+                                beta, w_scale, x_scale, epilogue, stream);
+}
+extern "C" int sm_linear24_grouped_gather_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                              size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, int fmt_w,
+                                              int fmt_x, int out_type, float alpha, float beta, const float* w_scale, const float* x_scale,
+                                              const sm_epilogue_t* epilogue, sm_stream_t stream) {
+  return linear8_grouped<true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx, ldy, fmt_w,
+                               fmt_x, out_type, alpha, beta, w_scale, x_scale, epilogue, stream);
+}
+
+template <bool GATHER>
+static int linear8_grouped_glu(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t hidden, size_t in_features,
+                               size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale,
+                               const float* bias, sm_stream_t stream) {
+  const char* who = GATHER ? LINEAR24_GATHER_GLU8_WHO : LINEAR24_GROUPED_GLU8_WHO;
+  Linear8Args a = {};
+  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
+  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
+  bool run;
+  const int rc = linear24_glu_args(a, &run, who, fmt_ok && out_ok,
+                                   GATHER ? "null group_offsets, null x_index, x_rows == 0, fmt not SM_FP8_*, out_type not SM_OUT_*, "
+                                          : "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ",
+                                   blob, X, Y, tokens, hidden, in_features, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, act, bias, &grp);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.Mtot = grp.groups * 2 * hidden;
+  a.X = (const uint8_t*)X;
+  a.nplanes = (int)(in_features / 64);
+  a.out_type = out_type;
+  a.w_scale = w_scale; a.x_scale = x_scale;
+  const int form = linear24_grouped_glu_form(tokens, grp.groups, hidden, in_features, (size_t)device_cu_count());
+  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
+    set_error("%s: grid too large", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  return linear8_launch_grouped_fmt<true, GATHER>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream, who);
 }
 
 extern "C" int sm_linear24_grouped_glu_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
                                            size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, int act, const float* w_scale,
                                            const float* x_scale, const float* bias, sm_stream_t stream) {
-  Linear8Args a = {};
-  const Linear24Groups grp = {group_offsets, groups};
-  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
-  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
-  bool run;
-  const int rc = linear24_glu_args(a, &run, LINEAR24_GROUPED_GLU8_WHO, fmt_ok && out_ok, "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob,
-                                   X, Y, tokens, hidden, in_features, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, act, bias, &grp);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.Mtot = groups * 2 * hidden;
-  a.X = (const uint8_t*)X;
-  a.nplanes = (int)(in_features / 64);
-  a.out_type = out_type;
-  a.w_scale = w_scale; a.x_scale = x_scale;
-  const int form = linear24_grouped_glu_form(tokens, groups, hidden, in_features, (size_t)device_cu_count());
-  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
-    set_error("%s: grid too large", LINEAR24_GROUPED_GLU8_WHO);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  return linear8_launch_grouped_fmt<true>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream);
+  return linear8_grouped_glu<false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy, fmt_w, fmt_x, out_type, act,
+                                    w_scale, x_scale, bias, stream);
+}
+extern "C" int sm_linear24_grouped_glu_gather_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
+                                                  size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int fmt_w,
+                                                  int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale, const float* bias,
+                                                  sm_stream_t stream) {
+  return linear8_grouped_glu<true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy, fmt_w,
+                                   fmt_x, out_type, act, w_scale, x_scale, bias, stream);
 }
