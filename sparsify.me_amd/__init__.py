@@ -497,19 +497,52 @@ def spmma(blob, B, C, m, n, k, batch=1, strideB=0, strideC=None, alpha=1.0, beta
            "sm_spmma")
 
 
+def _opt(t):
+    """the device address of an optional tensor"""
+    return _dev(t) if t is not None else None
+
+
+def _linear24_16(X, Y, what):
+    """what the eight linear24* wrappers share: the 16-bit layers' dtype check ..."""
+    torch = _t()
+    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
+        raise SparsifymeError(f"{what}: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+
+
+def _linear24_8(X, Y, w_dtype, w_scale, x_scale, what):
+    """... the fp8 layers' (fmt_w, fmt_x, out_type) from the dtypes and their two optional scale addresses ..."""
+    fx = fp8_format(X.dtype)
+    fw = fx if w_dtype is None else fp8_format(w_dtype)
+    ot = _fp8_out_type(Y)
+    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
+        if v is not None and v.dtype != _t().float32:
+            raise SparsifymeError(f"{what}: {name} is float32, not {v.dtype}")
+    return fw, fx, ot, _opt(w_scale), _opt(x_scale)
+
+
+def _linear24_ld(ldx, ldy, in_features, width):
+    """... the leading dimensions' defaults (width: out_features, or hidden) ..."""
+    return in_features if ldx is None else ldx, width if ldy is None else ldy
+
+
+def _linear24_epilogue(epilogue, Y, beta):
+    """... and (struct, its address) of an optional Epilogue: the caller holds the struct until the call has returned."""
+    if epilogue is None:
+        return None, None
+    st = epilogue.struct_for(Y, 0, float(beta))
+    return st, ctypes.addressof(st)
+
+
 def linear24(blob, X, Y, tokens, out_features, in_features, ldx=None, ldy=None, alpha=1.0, beta=0.0, epilogue=None):
     """Y[tokens][out] = act(alpha * X[tokens][in] . W^T + beta * R + bias) with W[out][in] the 2:4 blob of
     compress24(W, m=out_features, k=in_features) (sm_linear24_*): token-major in and out, one launch.  epilogue: an Epilogue read in
     Y's coordinates (bias_dim "col": one value per out feature, "row": one per token; residual of Y's shape and ldy)."""
-    torch = _t()
-    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
-        raise SparsifymeError(f"linear24: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
-    ldx = in_features if ldx is None else ldx
-    ldy = out_features if ldy is None else ldy
-    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
+    _linear24_16(X, Y, "linear24")
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, out_features)
+    st, ep = _linear24_epilogue(epilogue, Y, beta)
     fn = getattr(lib(), "sm_linear24_" + _sfx(X))
-    _check(fn(_dev(blob), _dev(X), _dev(Y), tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta),
-              ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24")
+    _check(fn(_dev(blob), _dev(X), _dev(Y), tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta), ep,
+              _stream()), "sm_linear24")
 
 
 # include/sparsifyme.h: SM_LINEAR24_FORM_* (index = value)
@@ -522,18 +555,11 @@ def linear24_fp8(blob, X, Y, tokens, out_features, in_features, w_dtype=None, ld
     of compress24_fp8 / quantize_compress24_fp8 and X fp8 tokens (sm_linear24_fp8): token-major in and out, one launch.  The formats
     come from the dtypes (w_dtype: W's fp8 dtype, the blob does not carry it; None = X's), the output type from Y's (float32 / float16 /
     bfloat16).  w_scale / x_scale: float32 device vectors or None.  epilogue: an Epilogue read in Y's coordinates, as linear24 reads it."""
-    fx = fp8_format(X.dtype)
-    fw = fx if w_dtype is None else fp8_format(w_dtype)
-    ot = _fp8_out_type(Y)
-    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
-        if v is not None and v.dtype != _t().float32:
-            raise SparsifymeError(f"linear24_fp8: {name} is float32, not {v.dtype}")
-    ldx = in_features if ldx is None else ldx
-    ldy = out_features if ldy is None else ldy
-    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
+    fw, fx, ot, ws, xs = _linear24_8(X, Y, w_dtype, w_scale, x_scale, "linear24_fp8")
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, out_features)
+    st, ep = _linear24_epilogue(epilogue, Y, beta)
     _check(lib().sm_linear24_fp8(_dev(blob), _dev(X), _dev(Y), tokens, out_features, in_features, ldx, ldy, fw, fx, ot, float(alpha), float(beta),
-                                 _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None,
-                                 ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24_fp8")
+                                 ws, xs, ep, _stream()), "sm_linear24_fp8")
 
 
 def linear24_fp8_form(tokens, out_features, in_features, cus=0):
@@ -557,19 +583,16 @@ def _glu_act(act, what):
 def _glu_bias(bias, what):
     if bias is not None and bias.dtype != _t().float32:
         raise SparsifymeError(f"{what}: bias is float32, not {bias.dtype}")
-    return _dev(bias) if bias is not None else None
+    return _opt(bias)
 
 
 def linear24_glu(blob, X, Y, tokens, hidden, in_features, act="silu", bias=None, ldx=None, ldy=None):
     """Y[tokens][hidden] = act(g) * u, g = X . W[:hidden]^T + bias[:hidden], u = X . W[hidden:]^T + bias[hidden:], with W[2 hidden][in]
     the 2:4 blob of compress24(W, m=2 * hidden, k=in_features): a fused gate/up projection and its gate in one launch
     (sm_linear24_glu_*).  act: "silu" (SwiGLU), "relu" (ReGLU) or "none" (bilinear); bias: 2 * hidden float32 values or None."""
-    torch = _t()
-    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
-        raise SparsifymeError(f"linear24_glu: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+    _linear24_16(X, Y, "linear24_glu")
     a, b = _glu_act(act, "linear24_glu"), _glu_bias(bias, "linear24_glu")
-    ldx = in_features if ldx is None else ldx
-    ldy = hidden if ldy is None else ldy
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, hidden)
     fn = getattr(lib(), "sm_linear24_glu_" + _sfx(X))
     _check(fn(_dev(blob), _dev(X), _dev(Y), tokens, hidden, in_features, ldx, ldy, a, b, _stream()), "sm_linear24_glu")
 
@@ -578,18 +601,11 @@ def linear24_glu_fp8(blob, X, Y, tokens, hidden, in_features, act="silu", w_dtyp
                      ldy=None):
     """linear24_glu on fp8 operands (sm_linear24_glu_fp8): g and u are (w_scale[row] * x_scale[t]) * acc + bias[row] with row = h and
     hidden + h.  The formats come from the dtypes as in linear24_fp8; w_scale: 2 * hidden float32 values, x_scale: tokens, or None."""
-    fx = fp8_format(X.dtype)
-    fw = fx if w_dtype is None else fp8_format(w_dtype)
-    ot = _fp8_out_type(Y)
-    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
-        if v is not None and v.dtype != _t().float32:
-            raise SparsifymeError(f"linear24_glu_fp8: {name} is float32, not {v.dtype}")
+    fw, fx, ot, ws, xs = _linear24_8(X, Y, w_dtype, w_scale, x_scale, "linear24_glu_fp8")
     a, b = _glu_act(act, "linear24_glu_fp8"), _glu_bias(bias, "linear24_glu_fp8")
-    ldx = in_features if ldx is None else ldx
-    ldy = hidden if ldy is None else ldy
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, hidden)
     _check(lib().sm_linear24_glu_fp8(_dev(blob), _dev(X), _dev(Y), tokens, hidden, in_features, ldx, ldy, fw, fx, ot, a,
-                                     _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None, b,
-                                     _stream()), "sm_linear24_glu_fp8")
+                                     ws, xs, b, _stream()), "sm_linear24_glu_fp8")
 
 
 def linear24_glu_form(tokens, hidden, in_features, cus=0):
@@ -611,7 +627,10 @@ def _group_offsets(group_offsets, what):
 
 
 def _x_index(x_index, x_rows, what):
-    """(x_index, x_rows) of the gathered forms as ctypes arguments; x_rows=None is not guessed (X's buffer may hold guard rows)."""
+    """(x_index, x_rows) of the gathered forms as ctypes arguments, [] without x_index; x_rows=None is not guessed (X's buffer may hold
+    guard rows)."""
+    if x_index is None:
+        return []
     if x_index.dtype != _t().int32:
         raise SparsifymeError(f"{what}: x_index is int32, not {x_index.dtype}")
     if x_rows is None:
@@ -626,53 +645,39 @@ def linear24_grouped(blob, X, Y, group_offsets, groups, tokens, out_features, in
     expert's rows begin.  A "col" bias holds groups * out values, expert-major; a "row" bias and the residual are in Y's rows.
     x_index (tokens int32 values on the device) with x_rows: the gathered form (sm_linear24_grouped_gather_*), row t of Y reads row
     x_index[t] of X's x_rows rows; the same for the three grouped wrappers below."""
-    torch = _t()
-    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
-        raise SparsifymeError(f"linear24_grouped: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+    _linear24_16(X, Y, "linear24_grouped")
     off = _group_offsets(group_offsets, "linear24_grouped")
-    ldx = in_features if ldx is None else ldx
-    ldy = out_features if ldy is None else ldy
-    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
-    gather = _x_index(x_index, x_rows, "linear24_grouped") if x_index is not None else []
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, out_features)
+    st, ep = _linear24_epilogue(epilogue, Y, beta)
+    gather = _x_index(x_index, x_rows, "linear24_grouped")
     fn = getattr(lib(), "sm_linear24_grouped_" + ("gather_" if gather else "") + _sfx(X))
-    _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta),
-              ctypes.addressof(st) if st is not None else None, _stream()), "sm_linear24_grouped")
+    _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, out_features, in_features, ldx, ldy, float(alpha), float(beta), ep,
+              _stream()), "sm_linear24_grouped")
 
 
 def linear24_grouped_fp8(blob, X, Y, group_offsets, groups, tokens, out_features, in_features, w_dtype=None, ldx=None, ldy=None, alpha=1.0,
                          beta=0.0, w_scale=None, x_scale=None, epilogue=None, x_index=None, x_rows=None):
     """linear24_fp8 per expert in one launch (sm_linear24_grouped_fp8); w_scale: groups * out float32 values, expert-major; x_scale:
     tokens values in Y's rows (gathered: x_rows values in X's rows)."""
-    fx = fp8_format(X.dtype)
-    fw = fx if w_dtype is None else fp8_format(w_dtype)
-    ot = _fp8_out_type(Y)
-    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
-        if v is not None and v.dtype != _t().float32:
-            raise SparsifymeError(f"linear24_grouped_fp8: {name} is float32, not {v.dtype}")
+    fw, fx, ot, ws, xs = _linear24_8(X, Y, w_dtype, w_scale, x_scale, "linear24_grouped_fp8")
     off = _group_offsets(group_offsets, "linear24_grouped_fp8")
-    ldx = in_features if ldx is None else ldx
-    ldy = out_features if ldy is None else ldy
-    st = epilogue.struct_for(Y, 0, float(beta)) if epilogue is not None else None
-    gather = _x_index(x_index, x_rows, "linear24_grouped_fp8") if x_index is not None else []
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, out_features)
+    st, ep = _linear24_epilogue(epilogue, Y, beta)
+    gather = _x_index(x_index, x_rows, "linear24_grouped_fp8")
     fn = lib().sm_linear24_grouped_gather_fp8 if gather else lib().sm_linear24_grouped_fp8
     _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, out_features, in_features, ldx, ldy, fw, fx, ot,
-              float(alpha), float(beta), _dev(w_scale) if w_scale is not None else None,
-              _dev(x_scale) if x_scale is not None else None, ctypes.addressof(st) if st is not None else None,
-              _stream()), "sm_linear24_grouped_fp8")
+              float(alpha), float(beta), ws, xs, ep, _stream()), "sm_linear24_grouped_fp8")
 
 
 def linear24_grouped_glu(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, act="silu", bias=None, ldx=None, ldy=None,
                          x_index=None, x_rows=None):
     """linear24_glu per expert in one launch (sm_linear24_grouped_glu_*): blob is that of W[groups][2 hidden][in], each expert's gate
     rows then its up rows; bias: groups * 2 * hidden float32 values in the same order, or None."""
-    torch = _t()
-    if X.dtype not in (torch.float16, torch.bfloat16) or Y.dtype != X.dtype:
-        raise SparsifymeError(f"linear24_grouped_glu: X and Y are both float16 or both bfloat16, not {X.dtype} and {Y.dtype}")
+    _linear24_16(X, Y, "linear24_grouped_glu")
     a, b = _glu_act(act, "linear24_grouped_glu"), _glu_bias(bias, "linear24_grouped_glu")
     off = _group_offsets(group_offsets, "linear24_grouped_glu")
-    ldx = in_features if ldx is None else ldx
-    ldy = hidden if ldy is None else ldy
-    gather = _x_index(x_index, x_rows, "linear24_grouped_glu") if x_index is not None else []
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, hidden)
+    gather = _x_index(x_index, x_rows, "linear24_grouped_glu")
     fn = getattr(lib(), "sm_linear24_grouped_glu_" + ("gather_" if gather else "") + _sfx(X))
     _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, hidden, in_features, ldx, ldy, a, b, _stream()), "sm_linear24_grouped_glu")
 
@@ -680,21 +685,14 @@ def linear24_grouped_glu(blob, X, Y, group_offsets, groups, tokens, hidden, in_f
 def linear24_grouped_glu_fp8(blob, X, Y, group_offsets, groups, tokens, hidden, in_features, act="silu", w_dtype=None, w_scale=None,
                              x_scale=None, bias=None, ldx=None, ldy=None, x_index=None, x_rows=None):
     """linear24_glu_fp8 per expert in one launch (sm_linear24_grouped_glu_fp8); w_scale and bias: groups * 2 * hidden float32 values."""
-    fx = fp8_format(X.dtype)
-    fw = fx if w_dtype is None else fp8_format(w_dtype)
-    ot = _fp8_out_type(Y)
-    for name, v in (("w_scale", w_scale), ("x_scale", x_scale)):
-        if v is not None and v.dtype != _t().float32:
-            raise SparsifymeError(f"linear24_grouped_glu_fp8: {name} is float32, not {v.dtype}")
+    fw, fx, ot, ws, xs = _linear24_8(X, Y, w_dtype, w_scale, x_scale, "linear24_grouped_glu_fp8")
     a, b = _glu_act(act, "linear24_grouped_glu_fp8"), _glu_bias(bias, "linear24_grouped_glu_fp8")
     off = _group_offsets(group_offsets, "linear24_grouped_glu_fp8")
-    ldx = in_features if ldx is None else ldx
-    ldy = hidden if ldy is None else ldy
-    gather = _x_index(x_index, x_rows, "linear24_grouped_glu_fp8") if x_index is not None else []
+    ldx, ldy = _linear24_ld(ldx, ldy, in_features, hidden)
+    gather = _x_index(x_index, x_rows, "linear24_grouped_glu_fp8")
     fn = lib().sm_linear24_grouped_glu_gather_fp8 if gather else lib().sm_linear24_grouped_glu_fp8
     _check(fn(_dev(blob), _dev(X), _dev(Y), off, *gather, groups, tokens, hidden, in_features, ldx, ldy, fw, fx, ot, a,
-              _dev(w_scale) if w_scale is not None else None, _dev(x_scale) if x_scale is not None else None,
-              b, _stream()), "sm_linear24_grouped_glu_fp8")
+              ws, xs, b, _stream()), "sm_linear24_grouped_glu_fp8")
 
 
 def linear24_grouped_form(tokens, groups, out_features, in_features, cus=0):

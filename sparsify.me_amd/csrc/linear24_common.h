@@ -1,8 +1,9 @@
 // linear24_common.h -- the core of the token-major 2:4 linear layer, shared by its two operand front ends: linear24_f16.hip
 // (sm_linear24_{f16,bf16}, 64 dense k per stage) and linear24_fp8.hip (sm_linear24_fp8, 128).  The front ends keep what depends on
 // the operand type -- the stage layout, the K loops, the matrix instruction; everything else is here, once: the dispatch rule, the
-// argument checks, the X-image swizzle, the fragment epilogue and store, the decode form's combine, the tile launcher -- and what the
-// grouped (per-expert) entry points add: their rule, the slot bound, the workgroup's view of its expert, the grouped launcher.
+// argument checks (linear24_args, one function for plain, gated, grouped and gathered calls), the X-image swizzle, the fragment
+// epilogue and store, the decode form's combine, the tile launcher (launch_linear24_tile, plain or GROUPED) -- and what the grouped
+// (per-expert) entry points add: their rule, the slot bound, the workgroup's view of its expert.
 #pragma once
 #include "spmma_args.h"
 
@@ -100,28 +101,50 @@ struct Linear24Core {
                      // the gated kernels: bias = 2 * hidden values (gate's, then up's) or null, act = SM_GLU_ACT_*, nothing else read
 };
 
+// What follows the product, as an entry point states it: alpha, beta and the epilogue of a plain one; of a gated one (alpha = 1,
+// beta = 0, no epilogue struct) the activation and the bias.
+struct Linear24Tail {
+  float alpha, beta;
+  const sm_epilogue_t* ep;
+  int act;            // SM_GLU_ACT_*
+  const float* bias;  // 2 * hidden values (gate's, then up's) or null
+};
+inline Linear24Tail linear24_glu_tail(int act, const float* bias) { return Linear24Tail{1.0f, 0.0f, nullptr, act, bias}; }
+
 // The entry points' argument checks, in their order and with their statuses, and the fields of Linear24Core they settle.  `who`
-// names the entry point in every message; extra_ok / extra: checks of the entry point's own that belong to the first test, and
+// names the entry point in every message; extra_ok / extra: checks of the entry point's own that belong to the second test, and
 // their words in its message.  x_elt: bytes of an element of X (the blob's element too); piece: bytes of four elements of Y.
-// *run = false with SM_STATUS_SUCCESS: an empty problem, nothing to launch.  grp (the grouped entry points): `out` is then ONE
-// expert's row count and the blob that of W[groups * out][in]; the checks gain the offsets, the group limit and groups * out.
-inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool extra_ok, const char* extra, const void* blob, const void* X, void* Y,
-                              size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, float alpha, float beta,
-                              const sm_epilogue_t* ep, const Linear24Groups* grp = nullptr) {
+// *run = false with SM_STATUS_SUCCESS: an empty problem, nothing to launch.  grp (the grouped entry points, else null): `out` is then
+// ONE expert's row count and the blob that of the stacked weight; the checks gain the offsets, the group limit and groups * rows.
+// glu (sm_linear24_*glu_*), in the order include/sparsifyme.h states: the activation first where a plain call checks its epilogue, then
+// the plain layer's list read on out = `hidden`; the blob is that of W[2 * hidden][in], so hidden <= LINEAR24_GLU_MAX_HIDDEN.
+inline int linear24_args(Linear24Core& a, bool* run, bool glu, const char* who, bool extra_ok, const char* extra, const void* blob, const void* X, void* Y,
+                         size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, const Linear24Tail& t,
+                         const Linear24Groups* grp) {
   *run = false;
-  bool plain;  // (not used: a plain epilogue takes the same kernels, whose bias / activation steps are skipped at run time)
-  if (const int rc = epilogue_args(ep, Y, 0, out, beta, a.e, &plain, who)) return rc;
+  const size_t max_out = glu ? LINEAR24_GLU_MAX_HIDDEN : 0x7fffffffull;
+  if (glu) {
+    if (t.act != SM_GLU_ACT_NONE && t.act != SM_GLU_ACT_RELU && t.act != SM_GLU_ACT_SILU) {
+      set_error("%s: invalid argument (act is not SM_GLU_ACT_*)", who);
+      return SM_STATUS_INVALID_VALUE;
+    }
+    a.e = EpiArgs{t.bias, (const half_t*)Y, 0, SM_BIAS_COL, t.act, 0.0f, 1};
+  } else {
+    bool plain;  // (not used: a plain epilogue takes the same kernels, whose bias / activation steps are skipped at run time)
+    if (const int rc = epilogue_args(t.ep, Y, 0, out, t.beta, a.e, &plain, who)) return rc;
+  }
   if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < out || (grp && !grp->offsets) ||
       (grp && grp->gather && (!grp->x_index || grp->x_rows == 0))) {
-    set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < out_features)", who, extra);
+    set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %s%sldx < in_features or ldy < %s)", who,
+              !grp ? "" : (grp->gather ? "null group_offsets, null x_index, x_rows == 0, " : "null group_offsets, "), extra, glu ? "hidden" : "out_features");
     return SM_STATUS_INVALID_VALUE;
   }
-  if (tokens > 0x7fffffffull || out > 0x7fffffffull || in > 0x7fffffffull || (grp && grp->gather && grp->x_rows > 0x7fffffffull)) {
-    set_error("%s: dimension exceeds 2^31-1", who);
+  if (tokens > 0x7fffffffull || out > max_out || in > 0x7fffffffull || (grp && grp->gather && grp->x_rows > 0x7fffffffull)) {
+    set_error("%s: dimension exceeds 2^31-1%s", who, glu ? " (tokens, in_features, 2 * hidden)" : "");
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (grp && (grp->groups > LINEAR24_MAX_GROUPS || (grp->groups != 0 && out > 0x7fffffffull / grp->groups))) {
-    set_error("%s: groups exceeds SM_LINEAR24_MAX_GROUPS or groups * out_features exceeds 2^31-1", who);
+  if (grp && (grp->groups > LINEAR24_MAX_GROUPS || (grp->groups != 0 && out > max_out / grp->groups))) {
+    set_error("%s: groups exceeds SM_LINEAR24_MAX_GROUPS or groups * %s exceeds 2^31-1", who, glu ? "2 * hidden" : "out_features");
     return SM_STATUS_NOT_SUPPORTED;
   }
   if (in % 64 != 0 || !aligned16(X) || ldx % (16 / x_elt) != 0) {
@@ -130,55 +153,22 @@ inline int linear24_core_args(Linear24Core& a, bool* run, const char* who, bool 
   }
   if (tokens == 0 || out == 0 || (grp && grp->groups == 0)) return SM_STATUS_SUCCESS;
   a.vals = (const char*)blob;
-  a.meta = (const char*)blob + blob_layout(out, in, x_elt, grp ? grp->groups : 1).meta_off;
+  a.meta = (const char*)blob + blob_layout(glu ? 2 * out : out, in, x_elt, grp ? grp->groups : 1).meta_off;
   a.Y = Y;
   a.ldx = ldx; a.ldy = ldy;
   a.out = (int)out; a.tokens = (int)tokens;
-  a.alpha = alpha; a.beta = beta;
-  const bool r_ok = beta == 0.0f || (reinterpret_cast<uintptr_t>(a.e.R) & (piece - 1)) == 0;
+  a.alpha = t.alpha; a.beta = t.beta;
+  const bool r_ok = t.beta == 0.0f || (reinterpret_cast<uintptr_t>(a.e.R) & (piece - 1)) == 0;
   a.packed = (out % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (piece - 1)) == 0 && r_ok) ? 1 : 0;
   *run = true;
   return SM_STATUS_SUCCESS;
 }
 
-// The same for the gated entry points (sm_linear24_glu_*), in the order include/sparsifyme.h states: the activation first, then the
-// plain layer's list read on `hidden`.  The blob is that of W[2 * hidden][in]; alpha = 1, beta = 0, no residual.
-inline int linear24_glu_args(Linear24Core& a, bool* run, const char* who, bool extra_ok, const char* extra, const void* blob, const void* X, void* Y,
-                             size_t tokens, size_t hidden, size_t in, size_t ldx, size_t ldy, size_t x_elt, size_t piece, int act, const float* bias,
-                             const Linear24Groups* grp = nullptr) {
-  *run = false;
-  if (act != SM_GLU_ACT_NONE && act != SM_GLU_ACT_RELU && act != SM_GLU_ACT_SILU) {
-    set_error("%s: invalid argument (act is not SM_GLU_ACT_*)", who);
-    return SM_STATUS_INVALID_VALUE;
-  }
-  if (!blob || !X || !Y || !aligned16(blob) || !extra_ok || ldx < in || ldy < hidden || (grp && !grp->offsets) ||
-      (grp && grp->gather && (!grp->x_index || grp->x_rows == 0))) {
-    set_error("%s: invalid argument (null operand, blob not 16-byte aligned, %sldx < in_features or ldy < hidden)", who, extra);
-    return SM_STATUS_INVALID_VALUE;
-  }
-  if (tokens > 0x7fffffffull || hidden > LINEAR24_GLU_MAX_HIDDEN || in > 0x7fffffffull || (grp && grp->gather && grp->x_rows > 0x7fffffffull)) {
-    set_error("%s: dimension exceeds 2^31-1 (tokens, in_features, 2 * hidden)", who);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  if (grp && (grp->groups > LINEAR24_MAX_GROUPS || (grp->groups != 0 && hidden > LINEAR24_GLU_MAX_HIDDEN / grp->groups))) {
-    set_error("%s: groups exceeds SM_LINEAR24_MAX_GROUPS or groups * 2 * hidden exceeds 2^31-1", who);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  if (in % 64 != 0 || !aligned16(X) || ldx % (16 / x_elt) != 0) {
-    set_error("%s: in_features %% 64 == 0 and 16-byte aligned rows of X (pointer, ldx %% %d) are required", who, (int)(16 / x_elt));
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  if (tokens == 0 || hidden == 0 || (grp && grp->groups == 0)) return SM_STATUS_SUCCESS;
-  a.vals = (const char*)blob;
-  a.meta = (const char*)blob + blob_layout(2 * hidden, in, x_elt, grp ? grp->groups : 1).meta_off;
-  a.Y = Y;
-  a.ldx = ldx; a.ldy = ldy;
-  a.out = (int)hidden; a.tokens = (int)tokens;
-  a.alpha = 1.0f; a.beta = 0.0f;
-  a.packed = (hidden % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & (piece - 1)) == 0) ? 1 : 0;
-  a.e = EpiArgs{bias, (const half_t*)Y, 0, SM_BIAS_COL, act, 0.0f, 1};
-  *run = true;
-  return SM_STATUS_SUCCESS;
+// The rule an entry point switches on, by its kind (groups: read by the grouped kinds only)
+template <bool GLU, bool GROUPED>
+inline int linear24_rule(size_t tokens, size_t groups, size_t out, size_t in, size_t cus) {
+  if constexpr (GROUPED) return GLU ? linear24_grouped_glu_form(tokens, groups, out, in, cus) : linear24_grouped_form(tokens, groups, out, in, cus);
+  else return GLU ? linear24_glu_form(tokens, out, in, cus) : linear24_form(tokens, out, in, cus);
 }
 
 // The tile forms' launch, one per kernel: the 2^31 - 1 grid limit on tiles_m * tiles_n, the opt-in to more than 64 KiB of dynamic LDS
@@ -198,23 +188,6 @@ static int launch_linear24_grid(const A& a, hipStream_t st, const char* who, con
   return check_launch(kernel_name);
 }
 
-// The tile form's launcher: the tile counts, then the launch.  BM: the features of Y (a.out) a workgroup covers -- the kernel's tile
-// rows, or half of them for a gated kernel, whose tile is BM gate rows + BM up rows.
-template <class Args, void (*KERNEL)(Args), int BM, int BN, int NT, size_t LDS>
-static int launch_linear24_tile(const Args& a0, hipStream_t st, const char* who, const char* kernel_name) {
-  Args a = a0;
-  a.tiles_m = (a.out + BM - 1) / BM;
-  a.tiles_n = (a.tokens + BN - 1) / BN;
-  return launch_linear24_grid<Args, KERNEL, NT, LDS>(a, st, who, kernel_name);
-}
-
-// ... and the decode form's: one workgroup of NT threads per 16 out features
-template <class Args, void (*KERNEL)(Args), int NT>
-static int launch_linear24_decode(const Args& a, hipStream_t st, const char* kernel_name) {
-  KERNEL<<<dim3((unsigned)ceil_div((size_t)a.out, 16)), dim3(NT), 0, st>>>(a);
-  return check_launch(kernel_name);
-}
-
 // The argument block of a GROUPED tile kernel: the front end's own block + the offsets.  The plain instantiations keep taking the
 // front end's block itself, so their code is what it was.  x_index / x_rows: read by the GATHER instantiations only (row t of Y reads
 // row clamp(x_index[t], 0, x_rows - 1) of X); the others never load them.
@@ -228,18 +201,31 @@ struct Linear24Grouped : Args {
 template <class Args, bool GROUPED> struct Linear24ArgsSel { typedef Args type; typedef const Args& view_t; };
 template <class Args> struct Linear24ArgsSel<Args, true> { typedef Linear24Grouped<Args> type; typedef Args view_t; };
 
-// The grouped launcher: the plain one with tiles_n = the slot bound (linear24_grouped_slots) and the offsets handed on.
-template <class Args, void (*KERNEL)(Linear24Grouped<Args>), int BM, int BN, int NT, size_t LDS>
-static int launch_linear24_tile_grouped(const Args& a0, const Linear24Groups& grp, hipStream_t st, const char* who, const char* kernel_name) {
-  Linear24Grouped<Args> a;
+// The tile form's launcher: the tile counts, then the launch.  BM: the features of Y (a.out) a workgroup covers -- the kernel's tile
+// rows, or half of them for a gated kernel, whose tile is BM gate rows + BM up rows.  GROUPED: tiles_n is the slot bound
+// (linear24_grouped_slots) and the offsets (and what a gathered call adds) are handed on; grp is not read otherwise.
+template <class Args, bool GROUPED, void (*KERNEL)(typename Linear24ArgsSel<Args, GROUPED>::type), int BM, int BN, int NT, size_t LDS>
+static int launch_linear24_tile(const Args& a0, const Linear24Groups& grp, hipStream_t st, const char* who, const char* kernel_name) {
+  typename Linear24ArgsSel<Args, GROUPED>::type a;
   static_cast<Args&>(a) = a0;
-  a.group_offsets = grp.offsets;
-  a.groups = (int)grp.groups;
-  a.x_rows = grp.gather ? (int)grp.x_rows : 0;
-  a.x_index = grp.gather ? grp.x_index : nullptr;
   a.tiles_m = (a.out + BM - 1) / BM;
-  a.tiles_n = (int)linear24_grouped_slots((size_t)a.tokens, grp.groups, BN);
-  return launch_linear24_grid<Linear24Grouped<Args>, KERNEL, NT, LDS>(a, st, who, kernel_name);
+  if constexpr (GROUPED) {
+    a.group_offsets = grp.offsets;
+    a.groups = (int)grp.groups;
+    a.x_rows = grp.gather ? (int)grp.x_rows : 0;
+    a.x_index = grp.gather ? grp.x_index : nullptr;
+    a.tiles_n = (int)linear24_grouped_slots((size_t)a.tokens, grp.groups, BN);
+  } else {
+    a.tiles_n = (a.tokens + BN - 1) / BN;
+  }
+  return launch_linear24_grid<typename Linear24ArgsSel<Args, GROUPED>::type, KERNEL, NT, LDS>(a, st, who, kernel_name);
+}
+
+// ... and the decode form's: one workgroup of NT threads per 16 out features
+template <class Args, void (*KERNEL)(Args), int NT>
+static int launch_linear24_decode(const Args& a, hipStream_t st, const char* kernel_name) {
+  KERNEL<<<dim3((unsigned)ceil_div((size_t)a.out, 16)), dim3(NT), 0, st>>>(a);
+  return check_launch(kernel_name);
 }
 
 // A grouped workgroup's view of the launch: from its block id to (group, out tile, local token tile), then the argument block cut down

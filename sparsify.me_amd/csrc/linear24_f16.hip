@@ -15,18 +15,17 @@
 //           LDS in wave order: deterministic, no workspace.  Other K order than the tile form: held to the arithmetic's bound.
 // The gated layer (sm_linear24_glu_{f16,bf16}: Y = act(gate) * up of a fused gate/up weight) is the GLU instantiation of the same two
 // kernels: only the blob rows a fragment is fetched from (linear24_glu_row) and the store (linear24_store_glu) differ.
+// Below the kernels: one host template, linear24<BF, GLU, GROUPED, GATHER>, behind all twelve launching entry points of this file.
 #include "linear24_common.h"
 
 namespace sm {
 
 // the compute-unit count the rule is asked with: a constant, not the device's, so the dispatch is the same everywhere
 constexpr size_t LINEAR24_F16_CUS = 256;
-static const char* const LINEAR24_F16_WHO = "sm_linear24_{f16,bf16}";
-static const char* const LINEAR24_GLU16_WHO = "sm_linear24_glu_{f16,bf16}";
-static const char* const LINEAR24_GROUPED16_WHO = "sm_linear24_grouped_{f16,bf16}";
-static const char* const LINEAR24_GROUPED_GLU16_WHO = "sm_linear24_grouped_glu_{f16,bf16}";
-static const char* const LINEAR24_GATHER16_WHO = "sm_linear24_grouped_gather_{f16,bf16}";
-static const char* const LINEAR24_GATHER_GLU16_WHO = "sm_linear24_grouped_glu_gather_{f16,bf16}";
+// the entry points' names in their messages: [GLU][plain, grouped, gathered]
+static const char* const LINEAR24_16_WHO[2][3] = {
+    {"sm_linear24_{f16,bf16}", "sm_linear24_grouped_{f16,bf16}", "sm_linear24_grouped_gather_{f16,bf16}"},
+    {"sm_linear24_glu_{f16,bf16}", "sm_linear24_grouped_glu_{f16,bf16}", "sm_linear24_grouped_glu_gather_{f16,bf16}"}};
 
 struct Linear24Args : Linear24Core {  // vals stage-major [in/64][out][64 B]
   const half_t* X;
@@ -311,169 +310,109 @@ __global__ __launch_bounds__(64 * NWV) void linear24_decode_kernel(const Linear2
   else linear24_decode_tail<Linear24Core, linear24_store_frag<Elt16<BF>, false>, false, FN, NWV>(p, acc, m0);
 }
 
-template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU = false>
-static int launch_linear24_tile16(const Linear24Args& a, hipStream_t st) {
-  return launch_linear24_tile<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF, GLU>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
-                              (size_t)NS * (BM * 72 + BN * 128)>(a, st, GLU ? LINEAR24_GLU16_WHO : LINEAR24_F16_WHO, "linear24_tile_kernel");
-}
-
-template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU, bool GATHER>
-static int launch_linear24_tile16_grouped(const Linear24Args& a, const Linear24Groups& grp, hipStream_t st, const char* who) {
-  return launch_linear24_tile_grouped<Linear24Args, linear24_tile_kernel<BM, BN, WM, WN, NS, BF, GLU, true, GATHER>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
-                                      (size_t)NS * (BM * 72 + BN * 128)>(a, grp, st, who, "linear24_tile_kernel");
+template <int BM, int BN, int WM, int WN, int NS, bool BF, bool GLU, bool GROUPED, bool GATHER>
+static int launch_linear24_tile16(const Linear24Args& a, const Linear24Groups& grp, hipStream_t st, const char* who) {
+  return launch_linear24_tile<Linear24Args, GROUPED, linear24_tile_kernel<BM, BN, WM, WN, NS, BF, GLU, GROUPED, GATHER>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                              (size_t)NS * (BM * 72 + BN * 128)>(a, grp, st, who, "linear24_tile_kernel");
 }
 
 }  // namespace sm
 
 using namespace sm;
 
-template <bool BF>
-static int linear24(const void* blob, const void* X, void* Y, size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy, float alpha,
-                    float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
+// Every entry point of this file: the checks, the rule, the launch.  GLU: `out` is `hidden` and t holds act / bias; GROUPED: grp is read
+// (the tile forms only: no grouped decode kernel, and the grouped rule never answers DECODE); GATHER (GROUPED only): X through grp.x_index.
+template <bool BF, bool GLU, bool GROUPED, bool GATHER>
+static int linear24(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy,
+                    const Linear24Tail& t, sm_stream_t stream) {
+  static_assert(GROUPED || !GATHER, "only a grouped layer gathers");
+  const char* who = LINEAR24_16_WHO[GLU][GROUPED + GATHER];
   Linear24Args a = {};
   bool run;
-  const int rc = linear24_core_args(a, &run, LINEAR24_F16_WHO, true, "", blob, X, Y, tokens, out, in, ldx, ldy, 2, 8, alpha, beta, ep);
+  const int rc = linear24_args(a, &run, GLU, who, true, "", blob, X, Y, tokens, out, in, ldx, ldy, 2, 8, t, GROUPED ? &grp : nullptr);
   if (rc != SM_STATUS_SUCCESS || !run) return rc;
   a.X = (const half_t*)X;
   a.nkt = (int)(in / 64);
   hipStream_t st = (hipStream_t)stream;
-  switch (linear24_form(tokens, out, in, LINEAR24_F16_CUS)) {
-    case SM_LINEAR24_FORM_DECODE: return launch_linear24_decode<Linear24Args, linear24_decode_kernel<1, 16, 4, BF>, 64 * 16>(a, st, "linear24_decode_kernel");
-    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16<128, 128, 2, 2, 3, BF>(a, st);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16<128, 64, 4, 1, 3, BF>(a, st);
-    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16<64, 64, 2, 2, 3, BF>(a, st);
+  const int form = linear24_rule<GLU, GROUPED>(tokens, grp.groups, out, in, LINEAR24_F16_CUS);
+  if constexpr (!GROUPED)
+    if (form == SM_LINEAR24_FORM_DECODE)
+      return launch_linear24_decode<Linear24Args, linear24_decode_kernel<1, 16, 4, BF, GLU>, 64 * 16>(a, st, "linear24_decode_kernel");
+  switch (form) {
+    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16<128, 128, 2, 2, 3, BF, GLU, GROUPED, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16<128, 64, 4, 1, 3, BF, GLU, GROUPED, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16<64, 64, 2, 2, 3, BF, GLU, GROUPED, GATHER>(a, grp, st, who);
   }
-  set_error("%s: grid too large", LINEAR24_F16_WHO);
+  set_error("%s: grid too large", who);
   return SM_STATUS_NOT_SUPPORTED;
 }
 
 extern "C" int sm_linear24_f16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
                                size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24<false>(blob, X, Y, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue, stream);
+  return linear24<false, false, false, false>(blob, X, Y, Linear24Groups{}, tokens, out_features, in_features, ldx, ldy, Linear24Tail{alpha, beta, epilogue},
+                                              stream);
 }
 extern "C" int sm_linear24_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
                                 size_t ldy, float alpha, float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24<true>(blob, X, Y, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue, stream);
-}
-
-template <bool BF>
-static int linear24_glu(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in, size_t ldx, size_t ldy, int act,
-                        const float* bias, sm_stream_t stream) {
-  Linear24Args a = {};
-  bool run;
-  const int rc = linear24_glu_args(a, &run, LINEAR24_GLU16_WHO, true, "", blob, X, Y, tokens, hidden, in, ldx, ldy, 2, 8, act, bias);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.X = (const half_t*)X;
-  a.nkt = (int)(in / 64);
-  hipStream_t st = (hipStream_t)stream;
-  switch (linear24_glu_form(tokens, hidden, in, LINEAR24_F16_CUS)) {
-    case SM_LINEAR24_FORM_DECODE:
-      return launch_linear24_decode<Linear24Args, linear24_decode_kernel<1, 16, 4, BF, true>, 64 * 16>(a, st, "linear24_decode_kernel");
-    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16<128, 128, 2, 2, 3, BF, true>(a, st);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16<128, 64, 4, 1, 3, BF, true>(a, st);
-    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16<64, 64, 2, 2, 3, BF, true>(a, st);
-  }
-  set_error("%s: grid too large", LINEAR24_GLU16_WHO);
-  return SM_STATUS_NOT_SUPPORTED;
+  return linear24<true, false, false, false>(blob, X, Y, Linear24Groups{}, tokens, out_features, in_features, ldx, ldy, Linear24Tail{alpha, beta, epilogue},
+                                             stream);
 }
 
 extern "C" int sm_linear24_glu_f16(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
                                    int act, const float* bias, sm_stream_t stream) {
-  return linear24_glu<false>(blob, X, Y, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+  return linear24<false, true, false, false>(blob, X, Y, Linear24Groups{}, tokens, hidden, in_features, ldx, ldy, linear24_glu_tail(act, bias), stream);
 }
 extern "C" int sm_linear24_glu_bf16(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
                                     int act, const float* bias, sm_stream_t stream) {
-  return linear24_glu<true>(blob, X, Y, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+  return linear24<true, true, false, false>(blob, X, Y, Linear24Groups{}, tokens, hidden, in_features, ldx, ldy, linear24_glu_tail(act, bias), stream);
 }
 
 // ---- the grouped layers: `groups` experts of one shape behind one launch (the GROUPED instantiations of the tile kernels); GATHER: the
 // same with X read through x_index (sm_linear24_grouped_*gather_*: grp.gather set, the GATHER instantiations) -------------------------
-template <bool BF, bool GATHER>
-static int linear24_grouped(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t out, size_t in, size_t ldx,
-                            size_t ldy, float alpha, float beta, const sm_epilogue_t* ep, sm_stream_t stream) {
-  const char* who = GATHER ? LINEAR24_GATHER16_WHO : LINEAR24_GROUPED16_WHO;
-  const size_t groups = grp.groups;
-  Linear24Args a = {};
-  bool run;
-  const int rc = linear24_core_args(a, &run, who, true, GATHER ? "null group_offsets, null x_index, x_rows == 0, " : "null group_offsets, ", blob, X, Y, tokens,
-                                    out, in, ldx, ldy, 2, 8, alpha, beta, ep, &grp);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.X = (const half_t*)X;
-  a.nkt = (int)(in / 64);
-  hipStream_t st = (hipStream_t)stream;
-  switch (linear24_grouped_form(tokens, groups, out, in, LINEAR24_F16_CUS)) {
-    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, false, GATHER>(a, grp, st, who);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, false, GATHER>(a, grp, st, who);
-    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, false, GATHER>(a, grp, st, who);
-  }
-  set_error("%s: grid too large", who);
-  return SM_STATUS_NOT_SUPPORTED;
-}
-
 extern "C" int sm_linear24_grouped_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                        size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha, float beta,
                                        const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24_grouped<false, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue,
-                                        stream);
+  return linear24<false, false, true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy,
+                                             Linear24Tail{alpha, beta, epilogue}, stream);
 }
 extern "C" int sm_linear24_grouped_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                         size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha, float beta,
                                         const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24_grouped<true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy, alpha, beta, epilogue,
-                                       stream);
+  return linear24<true, false, true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy,
+                                            Linear24Tail{alpha, beta, epilogue}, stream);
 }
 extern "C" int sm_linear24_grouped_gather_f16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
                                               size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha,
                                               float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24_grouped<false, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx, ldy,
-                                       alpha, beta, epilogue, stream);
+  return linear24<false, false, true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx,
+                                            ldy, Linear24Tail{alpha, beta, epilogue}, stream);
 }
 extern "C" int sm_linear24_grouped_gather_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
                                                size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, float alpha,
                                                float beta, const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear24_grouped<true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx, ldy,
-                                      alpha, beta, epilogue, stream);
-}
-
-template <bool BF, bool GATHER>
-static int linear24_grouped_glu(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t hidden, size_t in, size_t ldx,
-                                size_t ldy, int act, const float* bias, sm_stream_t stream) {
-  const char* who = GATHER ? LINEAR24_GATHER_GLU16_WHO : LINEAR24_GROUPED_GLU16_WHO;
-  const size_t groups = grp.groups;
-  Linear24Args a = {};
-  bool run;
-  const int rc = linear24_glu_args(a, &run, who, true, GATHER ? "null group_offsets, null x_index, x_rows == 0, " : "null group_offsets, ", blob, X, Y, tokens,
-                                   hidden, in, ldx, ldy, 2, 8, act, bias, &grp);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.X = (const half_t*)X;
-  a.nkt = (int)(in / 64);
-  hipStream_t st = (hipStream_t)stream;
-  switch (linear24_grouped_glu_form(tokens, groups, hidden, in, LINEAR24_F16_CUS)) {
-    case SM_LINEAR24_FORM_TILE128: return launch_linear24_tile16_grouped<128, 128, 2, 2, 3, BF, true, GATHER>(a, grp, st, who);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear24_tile16_grouped<128, 64, 4, 1, 3, BF, true, GATHER>(a, grp, st, who);
-    case SM_LINEAR24_FORM_TILE64: return launch_linear24_tile16_grouped<64, 64, 2, 2, 3, BF, true, GATHER>(a, grp, st, who);
-  }
-  set_error("%s: grid too large", who);
-  return SM_STATUS_NOT_SUPPORTED;
+  return linear24<true, false, true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx,
+                                           ldy, Linear24Tail{alpha, beta, epilogue}, stream);
 }
 
 extern "C" int sm_linear24_grouped_glu_f16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                            size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
-  return linear24_grouped_glu<false, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+  return linear24<false, true, true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy,
+                                            linear24_glu_tail(act, bias), stream);
 }
 extern "C" int sm_linear24_grouped_glu_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                             size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act, const float* bias, sm_stream_t stream) {
-  return linear24_grouped_glu<true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy, act, bias, stream);
+  return linear24<true, true, true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy,
+                                           linear24_glu_tail(act, bias), stream);
 }
 extern "C" int sm_linear24_grouped_glu_gather_f16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
                                                   size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act,
                                                   const float* bias, sm_stream_t stream) {
-  return linear24_grouped_glu<false, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy,
-                                           act, bias, stream);
+  return linear24<false, true, true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy,
+                                           linear24_glu_tail(act, bias), stream);
 }
 extern "C" int sm_linear24_grouped_glu_gather_bf16(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
                                                    size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int act,
                                                    const float* bias, sm_stream_t stream) {
-  return linear24_grouped_glu<true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy,
-                                          act, bias, stream);
+  return linear24<true, true, true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy,
+                                          linear24_glu_tail(act, bias), stream);
 }

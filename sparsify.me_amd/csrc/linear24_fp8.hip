@@ -19,17 +19,16 @@
 //           form: held to the arithmetic's bound.
 // The gated layer (sm_linear24_glu_fp8: Y = act(gate) * up of a fused gate/up weight) is the GLU instantiation of the same two
 // kernels: only the blob rows a fragment is fetched from (linear24_glu_row) and the store (linear24_store_glu) differ.
+// Below the kernels: one host template, linear8<GLU, GROUPED, GATHER>, behind all six launching entry points of this file, with the
+// one format switch; linear8_launch<FW, FX, ...> is the one form switch.
 #include "spmma_b8.h"
 #include "linear24_common.h"
 
 namespace sm {
 
-static const char* const LINEAR24_FP8_WHO = "sm_linear24_fp8";
-static const char* const LINEAR24_GLU8_WHO = "sm_linear24_glu_fp8";
-static const char* const LINEAR24_GROUPED8_WHO = "sm_linear24_grouped_fp8";
-static const char* const LINEAR24_GROUPED_GLU8_WHO = "sm_linear24_grouped_glu_fp8";
-static const char* const LINEAR24_GATHER8_WHO = "sm_linear24_grouped_gather_fp8";
-static const char* const LINEAR24_GATHER_GLU8_WHO = "sm_linear24_grouped_glu_gather_fp8";
+// the entry points' names in their messages: [GLU][plain, grouped, gathered]
+static const char* const LINEAR24_8_WHO[2][3] = {{"sm_linear24_fp8", "sm_linear24_grouped_fp8", "sm_linear24_grouped_gather_fp8"},
+                                                 {"sm_linear24_glu_fp8", "sm_linear24_grouped_glu_fp8", "sm_linear24_grouped_glu_gather_fp8"}};
 
 struct Linear8Args : Linear24Core {  // vals plane-major [in/64][out][32 B]
   size_t Mtot;  // rows of the blob (= out; the gated kernels: 2 * out)
@@ -321,53 +320,56 @@ __global__ __launch_bounds__(64 * NWV) void linear24_fp8_decode_kernel(const Lin
   else linear24_decode_tail<Linear8Args, linear8_store_frag_any, true, FN, NWV>(p, acc, m0);
 }
 
-template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU>
-static int launch_linear8_tile(const Linear8Args& a, hipStream_t st) {
-  return launch_linear24_tile<Linear8Args, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS, GLU>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
-                              (size_t)NS * (BM * 80 + BN * 128)>(a, st, GLU ? LINEAR24_GLU8_WHO : LINEAR24_FP8_WHO, "linear24_fp8_tile_kernel");
+template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU, bool GROUPED, bool GATHER>
+static int launch_linear8_tile(const Linear8Args& a, const Linear24Groups& grp, hipStream_t st, const char* who) {
+  return launch_linear24_tile<Linear8Args, GROUPED, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS, GLU, GROUPED, GATHER>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
+                              (size_t)NS * (BM * 80 + BN * 128)>(a, grp, st, who, "linear24_fp8_tile_kernel");
 }
 
-template <class MM, int BM, int BN, int WM, int WN, int NS, bool GLU, bool GATHER>
-static int launch_linear8_tile_grouped(const Linear8Args& a, const Linear24Groups& grp, hipStream_t st, const char* who) {
-  return launch_linear24_tile_grouped<Linear8Args, linear24_fp8_tile_kernel<MM, BM, BN, WM, WN, NS, GLU, true, GATHER>, GLU ? BM / 2 : BM, BN, 64 * WM * WN,
-                                      (size_t)NS * (BM * 80 + BN * 128)>(a, grp, st, who, "linear24_fp8_tile_kernel");
-}
-
-template <int FW, int FX, bool GLU, bool GATHER>
-static int linear8_launch_grouped(const Linear8Args& a, const Linear24Groups& grp, int form, hipStream_t st, const char* who) {
+// the form switch, per operand format pair (no grouped decode kernel: the grouped rule never answers DECODE)
+template <int FW, int FX, bool GLU, bool GROUPED, bool GATHER>
+static int linear8_launch(const Linear8Args& a, const Linear24Groups& grp, int form, hipStream_t st, const char* who) {
   typedef MmaF8<FW, FX> MM;
-  switch (form) {
-    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile_grouped<MM, 128, 128, 2, 2, 3, GLU, GATHER>(a, grp, st, who);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile_grouped<MM, 128, 64, 4, 1, 3, GLU, GATHER>(a, grp, st, who);
-    default: return launch_linear8_tile_grouped<MM, 64, 64, 2, 2, 3, GLU, GATHER>(a, grp, st, who);
-  }
-}
-
-template <bool GLU, bool GATHER>
-static int linear8_launch_grouped_fmt(const Linear8Args& a, const Linear24Groups& grp, int fmt_w, int fmt_x, int form, hipStream_t st, const char* who) {
-  if (fmt_w == SM_FP8_E4M3)
-    return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E4M3, GLU, GATHER>(a, grp, form, st, who)
-                                : linear8_launch_grouped<SM_FP8_E4M3, SM_FP8_E5M2, GLU, GATHER>(a, grp, form, st, who);
-  return fmt_x == SM_FP8_E4M3 ? linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E4M3, GLU, GATHER>(a, grp, form, st, who)
-                              : linear8_launch_grouped<SM_FP8_E5M2, SM_FP8_E5M2, GLU, GATHER>(a, grp, form, st, who);
-}
-
-template <int FW, int FX, bool GLU>
-static int linear8_launch(const Linear8Args& a, int form, hipStream_t st) {
-  typedef MmaF8<FW, FX> MM;
-  switch (form) {
-    case SM_LINEAR24_FORM_DECODE:
+  if constexpr (!GROUPED)
+    if (form == SM_LINEAR24_FORM_DECODE)
       return launch_linear24_decode<Linear8Args, linear24_fp8_decode_kernel<MM, 1, 16, 4, GLU>, 64 * 16>(a, st, "linear24_fp8_decode_kernel");
-    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile<MM, 128, 128, 2, 2, 3, GLU>(a, st);
-    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile<MM, 128, 64, 4, 1, 3, GLU>(a, st);
-    default: return launch_linear8_tile<MM, 64, 64, 2, 2, 3, GLU>(a, st);
+  switch (form) {
+    case SM_LINEAR24_FORM_TILE128: return launch_linear8_tile<MM, 128, 128, 2, 2, 3, GLU, GROUPED, GATHER>(a, grp, st, who);
+    case SM_LINEAR24_FORM_TILE128x64: return launch_linear8_tile<MM, 128, 64, 4, 1, 3, GLU, GROUPED, GATHER>(a, grp, st, who);
+    default: return launch_linear8_tile<MM, 64, 64, 2, 2, 3, GLU, GROUPED, GATHER>(a, grp, st, who);
   }
 }
 
-template <bool GLU>
-static int linear8_launch_fmt(const Linear8Args& a, int fmt_w, int fmt_x, int form, hipStream_t st) {
-  if (fmt_w == SM_FP8_E4M3) return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E4M3, SM_FP8_E4M3, GLU>(a, form, st) : linear8_launch<SM_FP8_E4M3, SM_FP8_E5M2, GLU>(a, form, st);
-  return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E5M2, SM_FP8_E4M3, GLU>(a, form, st) : linear8_launch<SM_FP8_E5M2, SM_FP8_E5M2, GLU>(a, form, st);
+// Every launching entry point of this file: the checks, the rule (asked with the device's compute-unit count), the format switch.
+// GLU: `out` is `hidden` and t holds act / bias; GROUPED: grp is read; GATHER (GROUPED only): X through grp.x_index.
+template <bool GLU, bool GROUPED, bool GATHER>
+static int linear8(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy,
+                   int fmt_w, int fmt_x, int out_type, const Linear24Tail& t, const float* w_scale, const float* x_scale, sm_stream_t stream) {
+  static_assert(GROUPED || !GATHER, "only a grouped layer gathers");
+  const char* who = LINEAR24_8_WHO[GLU][GROUPED + GATHER];
+  Linear8Args a = {};
+  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
+  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
+  bool run;
+  const int rc = linear24_args(a, &run, GLU, who, fmt_ok && out_ok, "fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob, X, Y, tokens, out, in, ldx, ldy, 1,
+                               out_type == SM_OUT_F32 ? 16 : 8, t, GROUPED ? &grp : nullptr);
+  if (rc != SM_STATUS_SUCCESS || !run) return rc;
+  a.Mtot = (GROUPED ? grp.groups : 1) * (GLU ? 2 * out : out);
+  a.X = (const uint8_t*)X;
+  a.nplanes = (int)(in / 64);
+  a.out_type = out_type;
+  a.w_scale = w_scale; a.x_scale = x_scale;
+  hipStream_t st = (hipStream_t)stream;
+  const int form = linear24_rule<GLU, GROUPED>(tokens, grp.groups, out, in, (size_t)device_cu_count());
+  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
+    set_error("%s: grid too large", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  if (fmt_w == SM_FP8_E4M3)
+    return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E4M3, SM_FP8_E4M3, GLU, GROUPED, GATHER>(a, grp, form, st, who)
+                                : linear8_launch<SM_FP8_E4M3, SM_FP8_E5M2, GLU, GROUPED, GATHER>(a, grp, form, st, who);
+  return fmt_x == SM_FP8_E4M3 ? linear8_launch<SM_FP8_E5M2, SM_FP8_E4M3, GLU, GROUPED, GATHER>(a, grp, form, st, who)
+                              : linear8_launch<SM_FP8_E5M2, SM_FP8_E5M2, GLU, GROUPED, GATHER>(a, grp, form, st, who);
 }
 
 }  // namespace sm
@@ -386,26 +388,8 @@ extern "C" int sm_linear24_fp8_form(size_t tokens, size_t out_features, size_t i
 extern "C" int sm_linear24_fp8(const void* blob, const void* X, void* Y, size_t tokens, size_t out_features, size_t in_features, size_t ldx,
                                size_t ldy, int fmt_w, int fmt_x, int out_type, float alpha, float beta, const float* w_scale, const float* x_scale,
                                const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  const size_t out = out_features, in = in_features;
-  Linear8Args a = {};
-  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
-  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
-  bool run;
-  const int rc = linear24_core_args(a, &run, LINEAR24_FP8_WHO, fmt_ok && out_ok, "fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob, X, Y, tokens, out, in, ldx,
-                                    ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, alpha, beta, epilogue);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.Mtot = out;
-  a.X = (const uint8_t*)X;
-  a.nplanes = (int)(in / 64);
-  a.out_type = out_type;
-  a.w_scale = w_scale; a.x_scale = x_scale;
-  hipStream_t st = (hipStream_t)stream;
-  const int form = linear24_form(tokens, out, in, (size_t)device_cu_count());
-  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
-    set_error("%s: grid too large", LINEAR24_FP8_WHO);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  return linear8_launch_fmt<false>(a, fmt_w, fmt_x, form, st);
+  return linear8<false, false, false>(blob, X, Y, Linear24Groups{}, tokens, out_features, in_features, ldx, ldy, fmt_w, fmt_x, out_type,
+                                      Linear24Tail{alpha, beta, epilogue}, w_scale, x_scale, stream);
 }
 
 extern "C" int sm_linear24_glu_form(size_t tokens, size_t hidden, size_t in_features, size_t cus, int* form) {
@@ -420,24 +404,8 @@ extern "C" int sm_linear24_glu_form(size_t tokens, size_t hidden, size_t in_feat
 extern "C" int sm_linear24_glu_fp8(const void* blob, const void* X, void* Y, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy,
                                    int fmt_w, int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale, const float* bias,
                                    sm_stream_t stream) {
-  Linear8Args a = {};
-  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
-  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
-  bool run;
-  const int rc = linear24_glu_args(a, &run, LINEAR24_GLU8_WHO, fmt_ok && out_ok, "fmt not SM_FP8_*, out_type not SM_OUT_*, ", blob, X, Y, tokens, hidden,
-                                   in_features, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, act, bias);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.Mtot = 2 * hidden;
-  a.X = (const uint8_t*)X;
-  a.nplanes = (int)(in_features / 64);
-  a.out_type = out_type;
-  a.w_scale = w_scale; a.x_scale = x_scale;
-  const int form = linear24_glu_form(tokens, hidden, in_features, (size_t)device_cu_count());
-  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
-    set_error("%s: grid too large", LINEAR24_GLU8_WHO);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  return linear8_launch_fmt<true>(a, fmt_w, fmt_x, form, (hipStream_t)stream);
+  return linear8<true, false, false>(blob, X, Y, Linear24Groups{}, tokens, hidden, in_features, ldx, ldy, fmt_w, fmt_x, out_type, linear24_glu_tail(act, bias),
+                                     w_scale, x_scale, stream);
 }
 
 // ---- the grouped layers: `groups` experts of one shape behind one launch (the GROUPED instantiations of the tile kernels) ----------
@@ -450,84 +418,30 @@ extern "C" int sm_linear24_grouped_form(size_t tokens, size_t groups, size_t out
   return SM_STATUS_SUCCESS;
 }
 
-template <bool GATHER>
-static int linear8_grouped(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t out, size_t in, size_t ldx, size_t ldy,
-                           int fmt_w, int fmt_x, int out_type, float alpha, float beta, const float* w_scale, const float* x_scale,
-                           const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  const char* who = GATHER ? LINEAR24_GATHER8_WHO : LINEAR24_GROUPED8_WHO;
-  Linear8Args a = {};
-  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
-  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
-  bool run;
-  const int rc = linear24_core_args(a, &run, who, fmt_ok && out_ok,
-                                    GATHER ? "null group_offsets, null x_index, x_rows == 0, fmt not SM_FP8_*, out_type not SM_OUT_*, "
-                                           : "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ",
-                                    blob, X, Y, tokens, out, in, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, alpha, beta, epilogue, &grp);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.Mtot = grp.groups * out;
-  a.X = (const uint8_t*)X;
-  a.nplanes = (int)(in / 64);
-  a.out_type = out_type;
-  a.w_scale = w_scale; a.x_scale = x_scale;
-  const int form = linear24_grouped_form(tokens, grp.groups, out, in, (size_t)device_cu_count());
-  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
-    set_error("%s: grid too large", who);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  return linear8_launch_grouped_fmt<false, GATHER>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream, who);
-}
-
 extern "C" int sm_linear24_grouped_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens,
                                        size_t out_features, size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, float alpha,
                                        float beta, const float* w_scale, const float* x_scale, const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear8_grouped<false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy, fmt_w, fmt_x, out_type, alpha,
-                                beta, w_scale, x_scale, epilogue, stream);
+  return linear8<false, true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, out_features, in_features, ldx, ldy, fmt_w, fmt_x, out_type,
+                                     Linear24Tail{alpha, beta, epilogue}, w_scale, x_scale, stream);
 }
 extern "C" int sm_linear24_grouped_gather_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
                                               size_t groups, size_t tokens, size_t out_features, size_t in_features, size_t ldx, size_t ldy, int fmt_w,
                                               int fmt_x, int out_type, float alpha, float beta, const float* w_scale, const float* x_scale,
                                               const sm_epilogue_t* epilogue, sm_stream_t stream) {
-  return linear8_grouped<true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx, ldy, fmt_w,
-                               fmt_x, out_type, alpha, beta, w_scale, x_scale, epilogue, stream);
-}
-
-template <bool GATHER>
-static int linear8_grouped_glu(const void* blob, const void* X, void* Y, const Linear24Groups& grp, size_t tokens, size_t hidden, size_t in_features,
-                               size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale,
-                               const float* bias, sm_stream_t stream) {
-  const char* who = GATHER ? LINEAR24_GATHER_GLU8_WHO : LINEAR24_GROUPED_GLU8_WHO;
-  Linear8Args a = {};
-  const bool fmt_ok = (fmt_w == SM_FP8_E4M3 || fmt_w == SM_FP8_E5M2) && (fmt_x == SM_FP8_E4M3 || fmt_x == SM_FP8_E5M2);
-  const bool out_ok = out_type == SM_OUT_F32 || out_type == SM_OUT_F16 || out_type == SM_OUT_BF16;
-  bool run;
-  const int rc = linear24_glu_args(a, &run, who, fmt_ok && out_ok,
-                                   GATHER ? "null group_offsets, null x_index, x_rows == 0, fmt not SM_FP8_*, out_type not SM_OUT_*, "
-                                          : "null group_offsets, fmt not SM_FP8_*, out_type not SM_OUT_*, ",
-                                   blob, X, Y, tokens, hidden, in_features, ldx, ldy, 1, out_type == SM_OUT_F32 ? 16 : 8, act, bias, &grp);
-  if (rc != SM_STATUS_SUCCESS || !run) return rc;
-  a.Mtot = grp.groups * 2 * hidden;
-  a.X = (const uint8_t*)X;
-  a.nplanes = (int)(in_features / 64);
-  a.out_type = out_type;
-  a.w_scale = w_scale; a.x_scale = x_scale;
-  const int form = linear24_grouped_glu_form(tokens, grp.groups, hidden, in_features, (size_t)device_cu_count());
-  if (form == SM_LINEAR24_FORM_NOT_TAKEN) {
-    set_error("%s: grid too large", who);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  return linear8_launch_grouped_fmt<true, GATHER>(a, grp, fmt_w, fmt_x, form, (hipStream_t)stream, who);
+  return linear8<false, true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, out_features, in_features, ldx, ldy,
+                                    fmt_w, fmt_x, out_type, Linear24Tail{alpha, beta, epilogue}, w_scale, x_scale, stream);
 }
 
 extern "C" int sm_linear24_grouped_glu_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, size_t groups, size_t tokens, size_t hidden,
                                            size_t in_features, size_t ldx, size_t ldy, int fmt_w, int fmt_x, int out_type, int act, const float* w_scale,
                                            const float* x_scale, const float* bias, sm_stream_t stream) {
-  return linear8_grouped_glu<false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy, fmt_w, fmt_x, out_type, act,
-                                    w_scale, x_scale, bias, stream);
+  return linear8<true, true, false>(blob, X, Y, Linear24Groups{group_offsets, groups}, tokens, hidden, in_features, ldx, ldy, fmt_w, fmt_x, out_type,
+                                    linear24_glu_tail(act, bias), w_scale, x_scale, stream);
 }
 extern "C" int sm_linear24_grouped_glu_gather_fp8(const void* blob, const void* X, void* Y, const int* group_offsets, const int* x_index, size_t x_rows,
                                                   size_t groups, size_t tokens, size_t hidden, size_t in_features, size_t ldx, size_t ldy, int fmt_w,
                                                   int fmt_x, int out_type, int act, const float* w_scale, const float* x_scale, const float* bias,
                                                   sm_stream_t stream) {
-  return linear8_grouped_glu<true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy, fmt_w,
-                                   fmt_x, out_type, act, w_scale, x_scale, bias, stream);
+  return linear8<true, true, true>(blob, X, Y, Linear24Groups{group_offsets, groups, true, x_index, x_rows}, tokens, hidden, in_features, ldx, ldy, fmt_w,
+                                   fmt_x, out_type, linear24_glu_tail(act, bias), w_scale, x_scale, stream);
 }

@@ -12,13 +12,13 @@ import subprocess
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import DEV
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT = {False: torch.float16, True: torch.bfloat16}
 ROUND = {False: 2.0 ** -11, True: 2.0 ** -8}
-DEV = "cuda:0"
 
 
 def table():

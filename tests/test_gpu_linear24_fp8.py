@@ -12,56 +12,13 @@ import os
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import DEV, FMTS, NAN_BYTE, ODT, OUTS, PAIRS, ROUND, TDT, TINY, U_OPS, decode8, dev8, encode8, f32dev
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-FMTS = ["e4m3", "e5m2"]
-PAIRS = [(w, x) for w in FMTS for x in FMTS]          # (W's format, X's format)
-OUTS = ["f32", "f16", "bf16"]
-TDT = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
-ODT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 IDT = {"f32": torch.int32, "f16": torch.int16, "bf16": torch.int16}
-ROUND = {"f32": 2.0 ** -24, "f16": 2.0 ** -11, "bf16": 2.0 ** -8}
-TINY = {"f32": 2.0 ** -149, "f16": 2.0 ** -24, "bf16": 2.0 ** -133}
-NAN_BYTE = {"e4m3": 0x7F, "e5m2": 0x7E}
 ACTS = [("none", 0.0), ("relu", 0.0), ("relu6", 6.0), ("leaky_relu", 0.1), ("hardswish", 0.0)]
-# fp32 operations between the accumulator and the one rounding, for the widest activation (hardswish), each at most half an ulp of a
-# value no larger than S: alpha * w_scale (1), * x_scale (2), s * acc (3), beta * R (4), their sum (5; the two are one fused step when
-# contracted), + bias (6), x + 3 (7), x * t (8), the rounded constant 1/6 (9) and the multiply by it (10).  The clamps are exact.
-U_OPS = 10
-
-
-def _lut(fmt):
-    b = np.arange(256)
-    sign = np.where(b & 0x80, -1.0, 1.0)
-    if fmt == "e4m3":
-        e, m = (b >> 3) & 15, b & 7
-        v = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e.astype(np.float64) - 10))
-        v = np.where((e == 15) & (m == 7), np.nan, v)
-    else:
-        e, m = (b >> 2) & 31, b & 3
-        v = np.where(e == 0, m * 2.0 ** -16, (4 + m) * 2.0 ** (e.astype(np.float64) - 17))
-        v = np.where(e == 31, np.where(m == 0, np.inf, np.nan), v)
-    return sign * v
-
-
-LUT = {f: _lut(f) for f in FMTS}
-
-
-def decode8(a, fmt):
-    """fp8 bytes -> fp64 values (this file's own statement of the two OCP encodings)."""
-    return LUT[fmt][np.asarray(a, dtype=np.uint8)]
-
-
-def encode8(x, fmt):
-    """fp32 values -> fp8 bytes, rounded to nearest even (what a caller's cast does)."""
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(TDT[fmt]).view(torch.uint8).numpy().copy()
-
-
-def dev8(a, fmt):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(DEV).view(TDT[fmt])
 
 
 def mask24(rng, out, inf):
@@ -85,10 +42,6 @@ def bits(t):
 
 def form_of(pkg, tokens, out, inf):
     return pkg.linear24_fp8_form(tokens, out, inf)
-
-
-def f32dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
 
 
 MARGINS = {}

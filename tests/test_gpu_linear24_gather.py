@@ -18,52 +18,25 @@ import subprocess
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import BN, CID, CUS, DEV, DT, GUARD, SENTINEL, TYPES, f32dev, indices, layout, mask24, ranges, sizes, todev
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-TYPES = ["f16", "bf16"]
-DT = {"f16": torch.float16, "bf16": torch.bfloat16}
-CUS = 256
-SENTINEL = 7.0
-GUARD = 4          # rows before and behind the rows of X and of Y, inside the allocation
-BN = {"tile64": 64, "tile128x64": 64, "tile128": 128}
-
-
-def sizes(bn):
-    """0 first, in the middle and last; 1, BN - 1, BN, BN + 1, several tiles"""
-    return [0, 1, bn - 1, 0, bn, bn + 1, 3 * bn + 8, 0]
 
 
 # form, out of the plain case (odd: per-element stores; % 4 == 0: packed), hidden of the gated one, in.  The sizes() of a 64-token tile are
 # 401 tokens in 7 tiles, mean 51; those of a 128-token tile 785 tokens in 7 tiles, mean 99: 37 tile rows (> 4608 blob rows) reach 256 workgroups
 CASES = [("tile64", 77, 41, 64), ("tile64", 84, 44, 192), ("tile128x64", 4613, 2307, 64), ("tile128x64", 4612, 2308, 320),
          ("tile128", 4613, 2307, 64), ("tile128", 4612, 2308, 192)]
-CID = lambda c: f"{c[0]}-{c[1]}x{c[3]}"
 
 
 def bits(t):
     return t.contiguous().view(torch.int16)
 
 
-def todev(a, ty):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DT[ty]).to(DEV)
-
-
-def f32dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
 def i32dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
-
-
-def mask24(rng, rows, inf):
-    keep = np.argsort(rng.random((rows, inf // 4, 4)), axis=2)[:, :, :2]
-    m = np.zeros((rows, inf // 4, 4), dtype=bool)
-    np.put_along_axis(m, keep, True, axis=2)
-    return m.reshape(rows, inf)
 
 
 def compress(pkg, W):
@@ -71,20 +44,6 @@ def compress(pkg, W):
     blob = torch.empty(pkg.compress24_size(rows, inf, 2, 1), dtype=torch.uint8, device=DEV)
     pkg.compress24(W.contiguous(), rows, inf, inf, 1, rows * inf, blob)
     return blob
-
-
-def layout(counts, head=3, tail=5):
-    off = head + np.concatenate([[0], np.cumsum(counts)])
-    return off, int(off[-1]) + tail
-
-
-def ranges(off, tokens):
-    """the contract's [lo_g, hi_g) of include/sparsifyme.h"""
-    out = []
-    for g in range(len(off) - 1):
-        lo = min(max(int(off[g]), 0), tokens)
-        out.append((lo, min(max(int(off[g + 1]), lo), tokens)))
-    return out
 
 
 class Problem:
@@ -129,15 +88,6 @@ class Problem:
 def assert_bits(got, ref, what):
     bad = torch.nonzero(bits(got) != bits(ref))
     assert bad.numel() == 0, f"{what}: first mismatch at (row, column) {bad[0].tolist()}, {len(bad)} of {got.numel()}"
-
-
-def indices(rng, tokens):
-    """(name, x_rows, x_index)"""
-    half = tokens // 2
-    return [("permutation", tokens, rng.permutation(tokens)),
-            ("identity", tokens, np.arange(tokens)),
-            ("repeated, x_rows < tokens", half, rng.permutation(tokens) % half),
-            ("x_rows > tokens", 2 * tokens + 3, rng.permutation(2 * tokens + 3)[:tokens])]
 
 
 # ------------------------------------------------------------------------------------------------ 1. every tile instantiation

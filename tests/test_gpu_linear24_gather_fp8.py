@@ -15,59 +15,26 @@ fp8 layers do -- which form it runs."""
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import (BN, CID, DEV, GUARD, NAN_BYTE, ODT, OUTS, PAIRS, SENTINEL, TDT, dev8, encode8, f32dev, indices, layout, mask24,
+                              ranges, sizes)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-FMTS = ["e4m3", "e5m2"]
-PAIRS = [(w, x) for w in FMTS for x in FMTS]          # (W's format, X's format)
-OUTS = ["f32", "f16", "bf16"]
-TDT = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
-ODT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 IDT = {torch.float32: torch.int32, torch.float16: torch.int16, torch.bfloat16: torch.int16}
-NAN_BYTE = {"e4m3": 0x7F, "e5m2": 0x7E}
-SENTINEL = 7.0
-GUARD = 4
-BN = {"tile64": 64, "tile128x64": 64, "tile128": 128}
-
-
-def sizes(bn):
-    """0 first, in the middle and last; 1, BN - 1, BN, BN + 1, several tiles"""
-    return [0, 1, bn - 1, 0, bn, bn + 1, 3 * bn + 8, 0]
 
 
 # form, out of the plain case (odd: per-element stores; % 4 == 0: packed), hidden of the gated one, in.  The sizes() of a 64-token tile are
 # 401 tokens in 7 tiles, mean 51; those of a 128-token tile 785 tokens in 7 tiles, mean 99: 37 tile rows (> 4608 blob rows) reach 256 workgroups
 CASES = [("tile64", 77, 41, 64), ("tile64", 84, 44, 192), ("tile128x64", 4613, 2307, 64), ("tile128x64", 4612, 2308, 320),
          ("tile128", 4613, 2307, 128), ("tile128", 4612, 2308, 192)]
-CID = lambda c: f"{c[0]}-{c[1]}x{c[3]}"
 
 
 def bits(t):
     return t.contiguous().view(IDT[t.dtype])
 
 
-def encode8(x, fmt):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(TDT[fmt]).view(torch.uint8).numpy().copy()
-
-
-def dev8(a, fmt):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(DEV).view(TDT[fmt])
-
-
-def f32dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
 def i32dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
-
-
-def mask24(rng, rows, inf):
-    keep = np.argsort(rng.random((rows, inf // 4, 4)), axis=2)[:, :, :2]
-    m = np.zeros((rows, inf // 4, 4), dtype=bool)
-    np.put_along_axis(m, keep, True, axis=2)
-    return m.reshape(rows, inf)
 
 
 def compress(pkg, W8):
@@ -75,20 +42,6 @@ def compress(pkg, W8):
     blob = torch.empty(pkg.compress24_size(rows, inf, 1, 1), dtype=torch.uint8, device=DEV)
     pkg.compress24_fp8(W8.contiguous(), rows, inf, inf, 1, rows * inf, blob)
     return blob
-
-
-def layout(counts, head=3, tail=5):
-    off = head + np.concatenate([[0], np.cumsum(counts)])
-    return off, int(off[-1]) + tail
-
-
-def ranges(off, tokens):
-    """the contract's [lo_g, hi_g) of include/sparsifyme.h"""
-    out = []
-    for g in range(len(off) - 1):
-        lo = min(max(int(off[g]), 0), tokens)
-        out.append((lo, min(max(int(off[g + 1]), lo), tokens)))
-    return out
 
 
 class Problem:
@@ -135,15 +88,6 @@ class Problem:
 def assert_bits(got, ref, what):
     bad = torch.nonzero(bits(got) != bits(ref))
     assert bad.numel() == 0, f"{what}: first mismatch at (row, column) {bad[0].tolist()}, {len(bad)} of {got.numel()}"
-
-
-def indices(rng, tokens):
-    """(name, x_rows, x_index)"""
-    half = tokens // 2
-    return [("permutation", tokens, rng.permutation(tokens)),
-            ("identity", tokens, np.arange(tokens)),
-            ("repeated, x_rows < tokens", half, rng.permutation(tokens) % half),
-            ("x_rows > tokens", 2 * tokens + 3, rng.permutation(2 * tokens + 3)[:tokens])]
 
 
 def epilogue_kw(pkg, rng, gated, G, rows, tokens):

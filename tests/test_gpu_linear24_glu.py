@@ -18,48 +18,19 @@ import subprocess
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import CUS, DEV, DT, INT_SHAPES, SENTINEL, SHAPES, SID, TYPES, act64, f32dev, mask24, todev
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-TYPES = ["f16", "bf16"]
-DT = {"f16": torch.float16, "bf16": torch.bfloat16}
 ROUND = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8}
 TINY = {"f16": 2.0 ** -24, "bf16": 2.0 ** -133}
 ACTS = ["none", "relu", "silu"]
 U_OPS = 1      # fp32 operations between an accumulator and the gate: the bias add (s = 1)
-CUS = 256      # the constant the 16-bit layer asks the rule with
-SENTINEL = 7.0
-
-SHAPES = [  # tokens, hidden, in, the form
-    (17, 32, 64, "tile64"), (200, 164, 192, "tile64"), (77, 65, 256, "tile64"),      # 65: odd hidden, the up block starts at an odd row
-    (260, 4099, 128, "tile128x64"), (260, 4100, 192, "tile128x64"),
-    (300, 8195, 128, "tile128"), (300, 8196, 192, "tile128"),
-    (1, 16, 64, "decode"), (9, 1011, 192, "decode"), (16, 8192, 64, "decode"),       # 8192: on the limit
-    (5, 40, 4160, "decode"),                                                         # 65 stages: a second trip round the K loop
-    (16, 8193, 64, "tile64"),                                                        # a tile form at <= 16 tokens
-]
-SID = lambda s: "x".join(map(str, s[:3]))
 
 
 def bits(t):
     return t.contiguous().view(torch.int16)
-
-
-def todev(a, ty):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DT[ty]).to(DEV)
-
-
-def f32dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
-def mask24(rng, rows, inf):
-    keep = np.argsort(rng.random((rows, inf // 4, 4)), axis=2)[:, :, :2]
-    m = np.zeros((rows, inf // 4, 4), dtype=bool)
-    np.put_along_axis(m, keep, True, axis=2)
-    return m.reshape(rows, inf)
 
 
 def compress(pkg, W):
@@ -137,10 +108,6 @@ def test_each_half_equals_the_plain_layer_bit_for_bit(gpu, ty, shape):
 
 
 # ------------------------------------------------------------------------------------------------ 3. integer-exact
-INT_SHAPES = [(17, 32, "tile64"), (77, 65, "tile64"), (260, 4099, "tile128x64"), (300, 8195, "tile128"), (1, 16, "decode"), (9, 1011, "decode"),
-              (16, 8192, "decode"), (16, 8193, "tile64")]
-
-
 @pytest.mark.parametrize("ty", TYPES)
 @pytest.mark.parametrize("shape", INT_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_integer_operands_give_the_fp64_product_rounded_once(gpu, shape, ty):
@@ -192,17 +159,6 @@ def _margin_report():
 
 
 # ------------------------------------------------------------------------------------------------ 5. all acts against fp64
-def silu64(g):
-    with np.errstate(over="ignore", invalid="ignore"):
-        return g / (1.0 + np.exp(-g))
-
-
-def act64(g, act):
-    if act == "relu":
-        return np.maximum(g, 0.0)
-    return silu64(g) if act == "silu" else g
-
-
 @pytest.mark.parametrize("ty", TYPES)
 @pytest.mark.parametrize("tokens,want", [(8, "decode"), (200, "tile64")])
 def test_all_acts_against_fp64_with_bias(gpu, tokens, want, ty):

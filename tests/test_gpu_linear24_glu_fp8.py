@@ -17,73 +17,13 @@ import os
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import (DEV, INT_SHAPES, NAN_BYTE, ODT, OUTS, PAIRS, ROUND, SENTINEL, SHAPES, SID, TDT, TINY, U_OPS, act64,
+                              decode8, dev8, encode8, f32dev, mask24, silu64)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-FMTS = ["e4m3", "e5m2"]
-PAIRS = [(w, x) for w in FMTS for x in FMTS]          # (W's format, X's format)
-OUTS = ["f32", "f16", "bf16"]
-TDT = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
-ODT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 IDT = {"f32": torch.int32, "f16": torch.int16, "bf16": torch.int16}
-ROUND = {"f32": 2.0 ** -24, "f16": 2.0 ** -11, "bf16": 2.0 ** -8}
-TINY = {"f32": 2.0 ** -149, "f16": 2.0 ** -24, "bf16": 2.0 ** -133}
-NAN_BYTE = {"e4m3": 0x7F, "e5m2": 0x7E}
 ACTS = ["none", "relu", "silu"]
-U_OPS = 10   # tests/test_gpu_linear24_fp8.py: the fp32 operations between an accumulator and the rounding (here 3: both scales, the bias)
-SENTINEL = 7.0
-
-SHAPES = [  # tokens, hidden, in, the form
-    (17, 32, 64, "tile64"), (200, 164, 192, "tile64"), (77, 65, 256, "tile64"),      # 65: odd hidden, the up block starts at an odd row
-    (260, 4099, 128, "tile128x64"), (260, 4100, 192, "tile128x64"),
-    (300, 8195, 128, "tile128"), (300, 8196, 192, "tile128"),
-    (1, 16, 64, "decode"), (9, 1011, 192, "decode"), (16, 8192, 64, "decode"),       # 8192: on the limit
-    (5, 40, 4160, "decode"),                                                         # 65 planes: a second trip round the K loop, odd tail
-    (16, 8193, 64, "tile64"),                                                        # a tile form at <= 16 tokens
-]
-SID = lambda s: "x".join(map(str, s[:3]))
-
-
-def _lut(fmt):
-    b = np.arange(256)
-    sign = np.where(b & 0x80, -1.0, 1.0)
-    if fmt == "e4m3":
-        e, m = (b >> 3) & 15, b & 7
-        v = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e.astype(np.float64) - 10))
-        v = np.where((e == 15) & (m == 7), np.nan, v)
-    else:
-        e, m = (b >> 2) & 31, b & 3
-        v = np.where(e == 0, m * 2.0 ** -16, (4 + m) * 2.0 ** (e.astype(np.float64) - 17))
-        v = np.where(e == 31, np.where(m == 0, np.inf, np.nan), v)
-    return sign * v
-
-
-LUT = {f: _lut(f) for f in FMTS}
-
-
-def decode8(a, fmt):
-    """fp8 bytes -> fp64 values (this file's own statement of the two OCP encodings)."""
-    return LUT[fmt][np.asarray(a, dtype=np.uint8)]
-
-
-def encode8(x, fmt):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(TDT[fmt]).view(torch.uint8).numpy().copy()
-
-
-def dev8(a, fmt):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(DEV).view(TDT[fmt])
-
-
-def f32dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
-def mask24(rng, rows, inf):
-    keep = np.argsort(rng.random((rows, inf // 4, 4)), axis=2)[:, :, :2]
-    m = np.zeros((rows, inf // 4, 4), dtype=bool)
-    np.put_along_axis(m, keep, True, axis=2)
-    return m.reshape(rows, inf)
 
 
 def compress(pkg, wb, fmt):
@@ -197,10 +137,6 @@ def test_fp32_out_is_the_float32_product_of_the_plain_halves(gpu, shape):
 
 
 # ------------------------------------------------------------------------------------------------ 3. integer-exact
-INT_SHAPES = [(17, 32, "tile64"), (77, 65, "tile64"), (260, 4099, "tile128x64"), (300, 8195, "tile128"), (1, 16, "decode"), (9, 1011, "decode"),
-              (16, 8192, "decode"), (16, 8193, "tile64")]
-
-
 @pytest.mark.parametrize("o", OUTS)
 @pytest.mark.parametrize("shape", INT_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_integer_operands_give_the_fp64_product_rounded_once(gpu, shape, o):
@@ -255,11 +191,6 @@ def _margin_report():
 
 
 # ------------------------------------------------------------------------------------------------ 4. SiLU alone
-def silu64(g):
-    with np.errstate(over="ignore", invalid="ignore"):
-        return g / (1.0 + np.exp(-g))
-
-
 def test_silu_alone_is_inside_its_derived_bound(gpu):
     """hidden 16, in 64, 65536 tokens, fp32 out.  Gate row: weights 1 at columns 2 and 3; X[t] = (0, 0, 0, 1, 0, ..): acc_g = 1 and
     g = x_scale[t] exactly (the gate bias is 0).  u is held at exactly 1 by the up BIAS over a zero accumulator (up rows: weights 1 at
@@ -305,12 +236,6 @@ def test_silu_alone_is_inside_its_derived_bound(gpu):
 
 
 # ------------------------------------------------------------------------------------------------ 5. all acts against fp64
-def act64(g, act):
-    if act == "relu":
-        return np.maximum(g, 0.0)
-    return silu64(g) if act == "silu" else g
-
-
 @pytest.mark.parametrize("o", OUTS)
 @pytest.mark.parametrize("tokens,want", [(8, "decode"), (200, "tile64")])
 def test_all_acts_against_fp64_with_bias_and_scales(gpu, tokens, want, o):

@@ -17,52 +17,25 @@ import subprocess
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import BN, CID, CUS, DEV, DT, GUARD, SENTINEL, TID, TIGHT, TYPES, f32dev, layout, mask24, ranges, sizes, tight_layout, todev
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-TYPES = ["f16", "bf16"]
-DT = {"f16": torch.float16, "bf16": torch.bfloat16}
-CUS = 256
-SENTINEL = 7.0
-GUARD = 4          # rows before and behind the tokens, inside the allocation
-BN = {"tile64": 64, "tile128x64": 64, "tile128": 128}
-
-
-def sizes(bn):
-    """0 first, in the middle and last; 1, BN - 1, BN, BN + 1, several tiles"""
-    return [0, 1, bn - 1, 0, bn, bn + 1, 3 * bn + 8, 0]
 
 
 # form, out of the plain case (odd: per-element stores; % 4 == 0: packed), hidden of the gated one, in.  The sizes() of a 64-token tile are
 # 401 tokens in 7 tiles, mean 51; those of a 128-token tile 785 tokens in 7 tiles, mean 99: 37 tile rows (> 4608 blob rows) reach 256 workgroups
 CASES = [("tile64", 77, 41, 64), ("tile64", 84, 44, 192), ("tile128x64", 4613, 2307, 64), ("tile128x64", 4612, 2308, 320),
          ("tile128", 4613, 2307, 64), ("tile128", 4612, 2308, 192)]
-CID = lambda c: f"{c[0]}-{c[1]}x{c[3]}"
 
 
 def bits(t):
     return t.contiguous().view(torch.int16)
 
 
-def todev(a, ty):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DT[ty]).to(DEV)
-
-
-def f32dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
 def i32dev(a):
     return torch.tensor([int(v) for v in a], dtype=torch.int32, device=DEV)
-
-
-def mask24(rng, rows, inf):
-    keep = np.argsort(rng.random((rows, inf // 4, 4)), axis=2)[:, :, :2]
-    m = np.zeros((rows, inf // 4, 4), dtype=bool)
-    np.put_along_axis(m, keep, True, axis=2)
-    return m.reshape(rows, inf)
 
 
 def compress(pkg, W):
@@ -70,11 +43,6 @@ def compress(pkg, W):
     blob = torch.empty(pkg.compress24_size(rows, inf, 2, 1), dtype=torch.uint8, device=DEV)
     pkg.compress24(W.contiguous(), rows, inf, inf, 1, rows * inf, blob)
     return blob
-
-
-def layout(counts, head=3, tail=5):
-    off = head + np.concatenate([[0], np.cumsum(counts)])
-    return off, int(off[-1]) + tail
 
 
 class Problem:
@@ -107,15 +75,6 @@ class Problem:
         Xs[:hi - lo] = self.X[lo:hi]
         Xs[:, self.inf:] = float("nan")
         return Xs, n
-
-
-def ranges(off, tokens):
-    """the contract's [lo_g, hi_g) of include/sparsifyme.h"""
-    out = []
-    for g in range(len(off) - 1):
-        lo = min(max(int(off[g]), 0), tokens)
-        out.append((lo, min(max(int(off[g + 1]), lo), tokens)))
-    return out
 
 
 def check_untouched(pr, Yb, width, tokens, owned):
@@ -216,18 +175,6 @@ def test_gated_groups_equal_the_gated_layer_bit_for_bit(gpu, ty, case):
 # Routings that ATTAIN the slot bound min(tokens, ceil(tokens / 64) + groups - 1) -- no block of the grid is spare -- with a real-tile
 # count T = tiles_m * slots that is no multiple of 8 (the XCD remap's unit): one group; one token per group; counts = 1 mod 64.
 # (counts, out of the plain case, hidden of the gated one): tiles_m = ceil(out / 64) = ceil(hidden / 32)
-TIGHT = [([300], 77, 41), ([1, 1, 298], 130, 65), ([1, 1, 1, 1, 1], 77, 41), ([65, 129, 1], 130, 65), ([1], 77, 41)]
-TID = lambda c: "-".join(map(str, c[0])) + f"x{c[1]}"
-
-
-def tight_layout(pkg, counts, rows, inf, cus):
-    off, tokens = layout(counts, head=0, tail=0)
-    G = len(counts)
-    assert pkg.linear24_grouped_form(tokens, G, rows, inf, cus=cus) == "tile64"
-    slots = min(tokens, -(-tokens // 64) + G - 1)
-    T = -(-rows // 64) * slots
-    assert sum(-(-c // 64) for c in counts) == slots and T % 8 != 0, "the case must attain the bound off the remap's unit"
-    return off, tokens, G
 
 
 @pytest.mark.parametrize("case", TIGHT, ids=TID)

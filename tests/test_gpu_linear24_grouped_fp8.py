@@ -14,59 +14,26 @@ compute units, as the fp8 layers do -- which form it runs."""
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import (BN, CID, DEV, GUARD, NAN_BYTE, ODT, OUTS, PAIRS, SENTINEL, TDT, TID, TIGHT, dev8, encode8, f32dev, layout,
+                              mask24, ranges, sizes, tight_layout)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-FMTS = ["e4m3", "e5m2"]
-PAIRS = [(w, x) for w in FMTS for x in FMTS]          # (W's format, X's format)
-OUTS = ["f32", "f16", "bf16"]
-TDT = {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
-ODT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 IDT = {torch.float32: torch.int32, torch.float16: torch.int16, torch.bfloat16: torch.int16}
-NAN_BYTE = {"e4m3": 0x7F, "e5m2": 0x7E}
-SENTINEL = 7.0
-GUARD = 4
-BN = {"tile64": 64, "tile128x64": 64, "tile128": 128}
-
-
-def sizes(bn):
-    """0 first, in the middle and last; 1, BN - 1, BN, BN + 1, several tiles"""
-    return [0, 1, bn - 1, 0, bn, bn + 1, 3 * bn + 8, 0]
 
 
 # form, out of the plain case (odd: per-element stores; % 4 == 0: packed), hidden of the gated one, in.  The sizes() of a 64-token tile are
 # 401 tokens in 7 tiles, mean 51; those of a 128-token tile 785 tokens in 7 tiles, mean 99: 37 tile rows (> 4608 blob rows) reach 256 workgroups
 CASES = [("tile64", 77, 41, 64), ("tile64", 84, 44, 192), ("tile128x64", 4613, 2307, 64), ("tile128x64", 4612, 2308, 320),
          ("tile128", 4613, 2307, 128), ("tile128", 4612, 2308, 192)]
-CID = lambda c: f"{c[0]}-{c[1]}x{c[3]}"
 
 
 def bits(t):
     return t.contiguous().view(IDT[t.dtype])
 
 
-def encode8(x, fmt):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(TDT[fmt]).view(torch.uint8).numpy().copy()
-
-
-def dev8(a, fmt):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(DEV).view(TDT[fmt])
-
-
-def f32dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
 def i32dev(a):
     return torch.tensor([int(v) for v in a], dtype=torch.int32, device=DEV)
-
-
-def mask24(rng, rows, inf):
-    keep = np.argsort(rng.random((rows, inf // 4, 4)), axis=2)[:, :, :2]
-    m = np.zeros((rows, inf // 4, 4), dtype=bool)
-    np.put_along_axis(m, keep, True, axis=2)
-    return m.reshape(rows, inf)
 
 
 def compress(pkg, W8):
@@ -74,20 +41,6 @@ def compress(pkg, W8):
     blob = torch.empty(pkg.compress24_size(rows, inf, 1, 1), dtype=torch.uint8, device=DEV)
     pkg.compress24_fp8(W8.contiguous(), rows, inf, inf, 1, rows * inf, blob)
     return blob
-
-
-def layout(counts, head=3, tail=5):
-    off = head + np.concatenate([[0], np.cumsum(counts)])
-    return off, int(off[-1]) + tail
-
-
-def ranges(off, tokens):
-    """the contract's [lo_g, hi_g) of include/sparsifyme.h"""
-    out = []
-    for g in range(len(off) - 1):
-        lo = min(max(int(off[g]), 0), tokens)
-        out.append((lo, min(max(int(off[g + 1]), lo), tokens)))
-    return out
 
 
 class Problem:
@@ -243,18 +196,6 @@ def test_every_format_pair_and_output_type(gpu, gated):
 # Routings that ATTAIN the slot bound min(tokens, ceil(tokens / 64) + groups - 1) -- no block of the grid is spare -- with a real-tile
 # count T = tiles_m * slots that is no multiple of 8 (the XCD remap's unit): one group; one token per group; counts = 1 mod 64.
 # (counts, out of the plain case, hidden of the gated one): tiles_m = ceil(out / 64) = ceil(hidden / 32)
-TIGHT = [([300], 77, 41), ([1, 1, 298], 130, 65), ([1, 1, 1, 1, 1], 77, 41), ([65, 129, 1], 130, 65), ([1], 77, 41)]
-TID = lambda c: "-".join(map(str, c[0])) + f"x{c[1]}"
-
-
-def tight_layout(pkg, counts, rows, inf, cus):
-    off, tokens = layout(counts, head=0, tail=0)
-    G = len(counts)
-    assert pkg.linear24_grouped_form(tokens, G, rows, inf, cus=cus) == "tile64"
-    slots = min(tokens, -(-tokens // 64) + G - 1)
-    T = -(-rows // 64) * slots
-    assert sum(-(-c // 64) for c in counts) == slots and T % 8 != 0, "the case must attain the bound off the remap's unit"
-    return off, tokens, G
 
 
 @pytest.mark.parametrize("case", TIGHT, ids=TID)

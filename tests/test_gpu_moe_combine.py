@@ -11,13 +11,10 @@ against torch.sort + index_select + the existing grouped calls + the numpy combi
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import DEV, DT, SENTINEL, TYPES, mask24
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-TYPES = ["f16", "bf16"]
-DT = {"f16": torch.float16, "bf16": torch.bfloat16}
-SENTINEL = 7.0
 GUARD = 3
 
 
@@ -180,13 +177,6 @@ def test_multiply_and_add_are_not_contracted(gpu, ty, form, hidden):
 
 
 # ------------------------------------------------------------------------------------------------ end to end
-def mask24(rng, rows, inf):
-    keep = np.argsort(rng.random((rows, inf // 4, 4)), axis=2)[:, :, :2]
-    m = np.zeros((rows, inf // 4, 4), dtype=bool)
-    np.put_along_axis(m, keep, True, axis=2)
-    return m.reshape(rows, inf)
-
-
 def compress(pkg, W):
     rows, inf = W.shape
     blob = torch.empty(pkg.compress24_size(rows, inf, 2, 1), dtype=torch.uint8, device=DEV)

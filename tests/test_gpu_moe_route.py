@@ -7,10 +7,10 @@ behind it and garbage inside.  Two runs agree; a graph captured once and replaye
 import numpy as np
 import pytest
 import torch
+from linear24_testlib import DEV
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 GUARD = 8                  # int32 words before and behind every output
 SENT = -77777
 SINGLE_MAX, CHUNK = 4096, 4096
