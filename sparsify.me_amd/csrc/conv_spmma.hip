@@ -224,11 +224,9 @@ __global__ __launch_bounds__(256, SMALL ? (BN == 64 ? 4 : 3) : 1) void conv_spmm
 
 template <int BN, bool BF, bool V16 = false, bool SMALL = V16>
 static int launch_conv(const ConvArgs& a, size_t lds, hipStream_t st) {
-  const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.N;
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&conv_spmma_fused_kernel<BN, BF, V16, SMALL>), 160 * 1024, "conv_spmma_fused_kernel")) return rc;
-  conv_spmma_fused_kernel<BN, BF, V16, SMALL><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
-  return check_launch("conv_spmma_fused_kernel");
+  // (the rule has settled the grid -- CONV_WHY_GRID, SM_CONV_FORM_EMPTY -- before any launcher is reached)
+  return launch_grid<&conv_spmma_fused_kernel<BN, BF, V16, SMALL>>((size_t)a.tiles_m * a.tiles_n * a.N, 256, 160 * 1024, lds, st, "sm_conv_spmma_fused",
+                                                                  "conv_spmma_fused_kernel", a);
 }
 
 // The geometry-only part of what the implicit kernel takes (no pointers, no n_out), and the stage plan that follows from it, for

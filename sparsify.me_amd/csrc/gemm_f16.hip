@@ -472,23 +472,13 @@ static int launch_dma(const GemmArgs& a0, hipStream_t st) {
   a.tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("gemm_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds_main = NS * ((size_t)BM * 128 + (size_t)64 * BN * 2);
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   // fewer K stages than ring buffers: the unused buffers are not allocated (more workgroups per CU)
   const size_t used = ((size_t)(a.K / 64) < (size_t)NS ? (size_t)(a.K / 64) : (size_t)NS) * ((size_t)BM * 128 + (size_t)64 * BN * 2);
   const size_t lds_launch = used > lds_epi ? used : lds_epi;
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&gemm_f16_dma_kernel<BM, BN, WM, WN, NS, BF, F32OUT>), lds, "gemm_f16_dma_kernel")) return rc;
-  }
-  gemm_f16_dma_kernel<BM, BN, WM, WN, NS, BF, F32OUT><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds_launch, st>>>(a);
-  return check_launch("gemm_f16_dma_kernel");
+  return launch_grid<&gemm_f16_dma_kernel<BM, BN, WM, WN, NS, BF, F32OUT>>(nwg, 64 * WM * WN, lds, lds_launch, st, "gemm_f16", "gemm_f16_dma_kernel", a);
 }
 
 template <int BM, int BN, int WM, int WN, bool TA = false, bool TB = false, bool BF = false>
@@ -497,21 +487,12 @@ static int launch_cfg(const GemmArgs& a0, int vec, hipStream_t st) {
   a.tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("gemm_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds_main = (size_t)BM * 128 + (size_t)BN * 128;
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  if (vec == 8)
-    gemm_f16_kernel<BM, BN, WM, WN, 8, TA, TB, BF><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
-  else if (vec == 4 && !TA && !TB)
-    gemm_f16_kernel<BM, BN, WM, WN, 4, false, false, BF><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
-  else
-    gemm_f16_kernel<BM, BN, WM, WN, 1, TA, TB, BF><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
-  return check_launch("gemm_f16_kernel");
+  if (vec == 8) return launch_grid<&gemm_f16_kernel<BM, BN, WM, WN, 8, TA, TB, BF>>(nwg, 256, LDS_NO_OPTIN, lds, st, "gemm_f16", "gemm_f16_kernel", a);
+  if (vec == 4 && !TA && !TB) return launch_grid<&gemm_f16_kernel<BM, BN, WM, WN, 4, false, false, BF>>(nwg, 256, LDS_NO_OPTIN, lds, st, "gemm_f16", "gemm_f16_kernel", a);
+  return launch_grid<&gemm_f16_kernel<BM, BN, WM, WN, 1, TA, TB, BF>>(nwg, 256, LDS_NO_OPTIN, lds, st, "gemm_f16", "gemm_f16_kernel", a);
 }
 
 // Tile choice: the streamed dimension gets the long tile edge; narrow problems get a tile as wide

@@ -212,15 +212,9 @@ static int launch32(const Gemm32Args& a0, hipStream_t st) {
   a.tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("gemm_f32: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds_b = (size_t)BK32 * (BN + 16) > (size_t)BN * APITCH ? (size_t)BK32 * (BN + 16) : (size_t)BN * APITCH;
   constexpr size_t lds = ((size_t)BM * APITCH + lds_b) * sizeof(float);
-  gemm_f32_kernel<BM, BN, WM, WN, MODE, ATR><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
-  return check_launch("gemm_f32_kernel");
+  return launch_grid<&gemm_f32_kernel<BM, BN, WM, WN, MODE, ATR>>(nwg, 256, LDS_NO_OPTIN, lds, st, "gemm_f32", "gemm_f32_kernel", a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -414,18 +408,8 @@ static int launch32_dma(const Gemm32Args& a0, hipStream_t st) {
   a.tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("gemm_f32: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds = (size_t)NS * (BM + BN) * 128;
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&gemm_f32_dma_kernel<BM, BN, WM, WN, NS, BKM, P24>), lds, "gemm_f32_dma_kernel")) return rc;
-  }
-  gemm_f32_dma_kernel<BM, BN, WM, WN, NS, BKM, P24><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds, st>>>(a);
-  return check_launch("gemm_f32_dma_kernel");
+  return launch_grid<&gemm_f32_dma_kernel<BM, BN, WM, WN, NS, BKM, P24>>(nwg, 64 * WM * WN, lds, lds, st, "gemm_f32", "gemm_f32_dma_kernel", a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -575,18 +559,8 @@ static int launch_spmma32_dma(const Gemm32Args& a0, hipStream_t st) {
   a.tiles_m = (a.M + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("spmma_f32: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds = 2 * ((size_t)128 * 128 + 128 * 8 + 2 * (size_t)BN * 128);
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f32_dma_kernel<BN, WM, WN>), lds, "spmma_f32_dma_kernel")) return rc;
-  }
-  spmma_f32_dma_kernel<BN, WM, WN><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds, st>>>(a);
-  return check_launch("spmma_f32_dma_kernel");
+  return launch_grid<&spmma_f32_dma_kernel<BN, WM, WN>>(nwg, 64 * WM * WN, lds, lds, st, "spmma_f32", "spmma_f32_dma_kernel", a);
 }
 
 

@@ -171,23 +171,6 @@ inline int linear24_rule(size_t tokens, size_t groups, size_t out, size_t in, si
   else return GLU ? linear24_glu_form(tokens, out, in, cus) : linear24_form(tokens, out, in, cus);
 }
 
-// The tile forms' launch, one per kernel: the 2^31 - 1 grid limit on tiles_m * tiles_n, the opt-in to more than 64 KiB of dynamic LDS
-// (held per instantiation), the launch.  NT threads per workgroup, LDS bytes of the whole ring.
-template <class A, void (*KERNEL)(A), int NT, size_t LDS>
-static int launch_linear24_grid(const A& a, hipStream_t st, const char* who, const char* kernel_name) {
-  const size_t nwg = (size_t)a.tiles_m * (size_t)a.tiles_n;
-  if (nwg > 0x7fffffffu) {
-    set_error("%s: grid too large", who);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  static LdsOptIn lds_optin;
-  if (LDS > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(KERNEL), LDS, kernel_name)) return rc;
-  }
-  KERNEL<<<dim3((unsigned)nwg), dim3(NT), LDS, st>>>(a);
-  return check_launch(kernel_name);
-}
-
 // The argument block of a GROUPED tile kernel: the front end's own block + the offsets.  The plain instantiations keep taking the
 // front end's block itself, so their code is what it was.  x_index / x_rows: read by the GATHER instantiations only (row t of Y reads
 // row clamp(x_index[t], 0, x_rows - 1) of X); the others never load them.
@@ -201,9 +184,11 @@ struct Linear24Grouped : Args {
 template <class Args, bool GROUPED> struct Linear24ArgsSel { typedef Args type; typedef const Args& view_t; };
 template <class Args> struct Linear24ArgsSel<Args, true> { typedef Linear24Grouped<Args> type; typedef Args view_t; };
 
-// The tile form's launcher: the tile counts, then the launch.  BM: the features of Y (a.out) a workgroup covers -- the kernel's tile
-// rows, or half of them for a gated kernel, whose tile is BM gate rows + BM up rows.  GROUPED: tiles_n is the slot bound
-// (linear24_grouped_slots) and the offsets (and what a gathered call adds) are handed on; grp is not read otherwise.
+// The tile form's launcher: the tile counts, then the launch (launch_grid, sm_common.h: the 2^31 - 1 limit on tiles_m * tiles_n, the
+// opt-in to more than 64 KiB of dynamic LDS per kernel instantiation).  NT threads per workgroup, LDS bytes of the whole ring.
+// BM: the features of Y (a.out) a workgroup covers -- the kernel's tile rows, or half of them for a gated kernel, whose tile is BM
+// gate rows + BM up rows.  GROUPED: tiles_n is the slot bound (linear24_grouped_slots) and the offsets (and what a gathered call
+// adds) are handed on; grp is not read otherwise.
 template <class Args, bool GROUPED, void (*KERNEL)(typename Linear24ArgsSel<Args, GROUPED>::type), int BM, int BN, int NT, size_t LDS>
 static int launch_linear24_tile(const Args& a0, const Linear24Groups& grp, hipStream_t st, const char* who, const char* kernel_name) {
   typename Linear24ArgsSel<Args, GROUPED>::type a;
@@ -218,7 +203,7 @@ static int launch_linear24_tile(const Args& a0, const Linear24Groups& grp, hipSt
   } else {
     a.tiles_n = (a.tokens + BN - 1) / BN;
   }
-  return launch_linear24_grid<typename Linear24ArgsSel<Args, GROUPED>::type, KERNEL, NT, LDS>(a, st, who, kernel_name);
+  return launch_grid<KERNEL>((size_t)a.tiles_m * (size_t)a.tiles_n, NT, LDS, LDS, st, who, kernel_name, a);
 }
 
 // ... and the decode form's: one workgroup of NT threads per 16 out features

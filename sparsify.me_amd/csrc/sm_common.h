@@ -46,6 +46,32 @@ int ensure_dyn_lds(LdsOptIn& s, const void* fn, size_t bytes, const char* what);
 // microseconds; launchers that size a grid by the CU count call this on every launch).
 int device_cu_count();
 
+// The tail of every tile-grid launcher, stated once: a 1-D grid of `nwg` workgroups of `threads` threads with `lds` bytes of dynamic
+// LDS.  In this order: an empty grid is SM_STATUS_SUCCESS with nothing touched; more than 2^31 - 1 workgroups is "<who>: grid too
+// large"; the opt-in to `lds_optin` bytes when that is more than 64 KiB; the launch; check_launch.  The kernel is a template
+// parameter, so that the opt-in state below is ONE PER KERNEL INSTANTIATION (a state shared by two kernels would skip the second
+// one's opt-in, and its first launch above 64 KiB would fail).  lds_optin is the most the instantiation can ever ask for (or simply
+// the hardware's 160 KiB), `lds` what this launch touches; LDS_NO_OPTIN for a kernel that never passes 64 KiB: no opt-in, no
+// hipGetDevice.  kernel_name: what ensure_dyn_lds and check_launch call the kernel in their messages.
+constexpr size_t LDS_NO_OPTIN = 0;
+#ifdef __HIPCC__
+template <auto KERNEL, class... Args>
+static int launch_grid(size_t nwg, unsigned threads, size_t lds_optin, size_t lds, hipStream_t st, const char* who, const char* kernel_name,
+                       const Args&... args) {
+  if (nwg == 0) return SM_STATUS_SUCCESS;
+  if (nwg > 0x7fffffffu) {
+    set_error("%s: grid too large", who);
+    return SM_STATUS_NOT_SUPPORTED;
+  }
+  if (lds_optin > 64 * 1024) {
+    static LdsOptIn optin;
+    if (const int rc = ensure_dyn_lds(optin, reinterpret_cast<const void*>(KERNEL), lds_optin, kernel_name)) return rc;
+  }
+  KERNEL<<<dim3((unsigned)nwg), dim3(threads), lds, st>>>(args...);
+  return check_launch(kernel_name);
+}
+#endif
+
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline size_t ceil_div(size_t x, size_t y) { return (x + y - 1) / y; }
 // Raise a device flag from one lane of a wave: the relaxed read first, so that once the flag is up the thousands of waves that also

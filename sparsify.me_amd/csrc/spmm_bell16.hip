@@ -274,18 +274,10 @@ static int bell16_launch_cfg(Bell16Args& a, size_t nb, bool vec, hipStream_t st)
   const size_t table = round_up(nbr_max * (size_t)(a.nkt + 1) * 2, 16);
   a.table = (a.ell_cols <= 65535 && STAGE2 + table <= BELL16_LDS_MAX) ? 1 : 0;
   const size_t lds = STAGE2 + (a.table ? table : 0);
-  const dim3 grid((unsigned)((size_t)a.tiles_m * a.tiles_n * nb));
-  static LdsOptIn optin_v, optin_s;
-  if (vec) {
-    if (const int rc = ensure_dyn_lds(optin_v, reinterpret_cast<const void*>(&spmm_bell16_kernel<TN, WM, WN, BF, true>), BELL16_LDS_MAX, "spmm_bell16_kernel"))
-      return rc;
-    spmm_bell16_kernel<TN, WM, WN, BF, true><<<grid, dim3(64 * BELL16_NW), lds, st>>>(a);
-  } else {
-    if (const int rc = ensure_dyn_lds(optin_s, reinterpret_cast<const void*>(&spmm_bell16_kernel<TN, WM, WN, BF, false>), BELL16_LDS_MAX, "spmm_bell16_kernel"))
-      return rc;
-    spmm_bell16_kernel<TN, WM, WN, BF, false><<<grid, dim3(64 * BELL16_NW), lds, st>>>(a);
-  }
-  return check_launch("spmm_bell16_kernel");
+  const size_t grid = (size_t)a.tiles_m * a.tiles_n * nb;  // (bell16_validate: 0 < grid <= 2^31 - 1 for the narrowest tile, so for this one)
+  const char* const who = "sm_spmm_bell16";
+  if (vec) return launch_grid<&spmm_bell16_kernel<TN, WM, WN, BF, true>>(grid, 64 * BELL16_NW, BELL16_LDS_MAX, lds, st, who, "spmm_bell16_kernel", a);
+  return launch_grid<&spmm_bell16_kernel<TN, WM, WN, BF, false>>(grid, 64 * BELL16_NW, BELL16_LDS_MAX, lds, st, who, "spmm_bell16_kernel", a);
 }
 
 

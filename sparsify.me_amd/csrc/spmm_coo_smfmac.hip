@@ -602,25 +602,17 @@ int coo_smfmac_product(size_t m, size_t k, size_t nnz, size_t nv, const int* row
   coo_smfmac_compress_kernel<<<(unsigned)(a.tiles_m * a.nst), 256, 0, st>>>(a);
   if (const int rc = check_launch("sm_spmm_coo_f32_fast: 2:4 image of A")) return rc;
   constexpr size_t lds = 128 * (128 * 4 + 16);  // the epilogue image; the two B stages (32 KiB) live inside it
-  const unsigned grid = (unsigned)((size_t)a.tiles_m * a.tiles_nv);
+  static_assert(lds > 64 * 1024, "opted in on every launch");
+  const size_t grid = (size_t)a.tiles_m * a.tiles_nv;  // (coo_smfmac_takes: 0 < grid <= 2^31 - 1)
+  const char* const who = "sm_spmm_coo_f32_fast";
   // the producer / consumer kernel (one workgroup per CU) where B is the traffic: few row tiles, several stages; the one-role kernel (two per CU) elsewhere
   if (k % 4 == 0 && a.tiles_m <= 2 && a.nst >= 3) {
     constexpr size_t lds_pc = 2 * 128 * 128 + 3 * 128 * 256;  // two images + the staging ring (the epilogue image fits inside)
-    static LdsOptIn lds_optin_pc;
-    if (const int rc = ensure_dyn_lds(lds_optin_pc, reinterpret_cast<const void*>(&spmm_coo_smfmac_pc_kernel), lds_pc, "spmm_coo_smfmac_pc_kernel")) return rc;
-    spmm_coo_smfmac_pc_kernel<<<grid, 512, lds_pc, st>>>(a);
-    return check_launch("spmm_coo_smfmac_pc_kernel");
+    return launch_grid<&spmm_coo_smfmac_pc_kernel>(grid, 512, lds_pc, lds_pc, st, who, "spmm_coo_smfmac_pc_kernel", a);
   }
   // (four waves of 32 rows; eight of 16 measured the same to 5 % slower on long K, profiles/coo_waves_r05af.txt)
-  static LdsOptIn lds_optin[2];
-  if (k % 4 == 0) {
-    if (const int rc = ensure_dyn_lds(lds_optin[0], reinterpret_cast<const void*>(&spmm_coo_smfmac_kernel<true, 4>), lds, "spmm_coo_smfmac_kernel")) return rc;
-    spmm_coo_smfmac_kernel<true, 4><<<grid, 256, lds, st>>>(a);
-  } else {
-    if (const int rc = ensure_dyn_lds(lds_optin[1], reinterpret_cast<const void*>(&spmm_coo_smfmac_kernel<false, 4>), lds, "spmm_coo_smfmac_kernel")) return rc;
-    spmm_coo_smfmac_kernel<false, 4><<<grid, 256, lds, st>>>(a);
-  }
-  return check_launch("spmm_coo_smfmac_kernel");
+  if (k % 4 == 0) return launch_grid<&spmm_coo_smfmac_kernel<true, 4>>(grid, 256, lds, lds, st, who, "spmm_coo_smfmac_kernel", a);
+  return launch_grid<&spmm_coo_smfmac_kernel<false, 4>>(grid, 256, lds, lds, st, who, "spmm_coo_smfmac_kernel", a);
 }
 
 }  // namespace sm

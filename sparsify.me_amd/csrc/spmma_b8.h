@@ -715,20 +715,10 @@ static int launch_spmma_b8(const Spmma8Args& a0, hipStream_t st, const char* wha
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("%s: grid too large", what);
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds_main = 2 * ((FUSED || MM::kDense ? (size_t)128 * 128 : (size_t)128 * 64 + 2 * 128 * 8) + (size_t)BN * 128);
   constexpr size_t lds_epi = (size_t)128 * (BN * 4 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_b8_kernel<MM, BN, WM, WN, FUSED>), lds, "spmma_b8_kernel")) return rc;
-  }
-  spmma_b8_kernel<MM, BN, WM, WN, FUSED><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds, st>>>(a);
-  return check_launch("spmma_b8_kernel");
+  return launch_grid<&spmma_b8_kernel<MM, BN, WM, WN, FUSED>>(nwg, 64 * WM * WN, lds, lds, st, what, "spmma_b8_kernel", a);
 }
 
 }  // namespace sm

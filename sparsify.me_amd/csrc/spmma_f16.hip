@@ -491,54 +491,28 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void spmma_f16_pc_kernel(const
 // measured in round 2: bit-identical, and 1.4 x SLOWER on every few-tile shape (196x512x4608: 51 vs 37 us,
 // profiles/tune_pc2_r02i.txt), with or without the deeper look-ahead.  Exposed LDS latency in the consumers is therefore
 // not what bounds this kernel; the variant is in the git history, not in the library.)
+// The two ring kernels' launch (pc and dma differ in the kernel and its thread count NT only): the LDS of a ring of NS stages.
+template <auto KERNEL, int BM, int BN, int NS, int NT, class Args>
+static int launch_ring(const Args& a0, hipStream_t st, const char* kernel_name) {
+  Args a = a0;
+  a.tiles_m = (a.Mrows + BM - 1) / BM;
+  a.tiles_n = (a.N + BN - 1) / BN;
+  const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
+  constexpr size_t lds_main = NS * ((size_t)BM * 72 + (size_t)64 * BN * 2);
+  constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
+  constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;  // the most this configuration ever asks for
+  // a K of fewer stages than the ring never touches the ring's other buffers: without them more workgroups share a CU
+  const size_t used = ((size_t)(a.kc / 64) < (size_t)NS ? (size_t)(a.kc / 64) : (size_t)NS) * ((size_t)BM * 72 + (size_t)64 * BN * 2);
+  const size_t lds_launch = used > lds_epi ? used : lds_epi;
+  return launch_grid<KERNEL>(nwg, NT, lds, lds_launch, st, "spmma_f16", kernel_name, a);
+}
 template <int BM, int BN, int WM, int WN, int NL, int NS, bool BF = false, bool EPI = false>
 static int launch_pc(const typename SpmmaArgsSel<EPI>::type& a0, hipStream_t st) {
-  typename SpmmaArgsSel<EPI>::type a = a0;
-  a.tiles_m = (a.Mrows + BM - 1) / BM;
-  a.tiles_n = (a.N + BN - 1) / BN;
-  const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("spmma_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  constexpr size_t lds_main = NS * ((size_t)BM * 72 + (size_t)64 * BN * 2);
-  constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
-  constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;  // the most this configuration ever asks for
-  // a K of fewer stages than the ring never touches the ring's other buffers: without them more workgroups share a CU
-  const size_t used = ((size_t)(a.kc / 64) < (size_t)NS ? (size_t)(a.kc / 64) : (size_t)NS) * ((size_t)BM * 72 + (size_t)64 * BN * 2);
-  const size_t lds_launch = used > lds_epi ? used : lds_epi;
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF, EPI>), lds, "spmma_f16_pc_kernel")) return rc;
-  }
-  spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF, EPI><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + NL)), lds_launch, st>>>(a);
-  return check_launch("spmma_f16_pc_kernel");
+  return launch_ring<&spmma_f16_pc_kernel<BM, BN, WM, WN, NL, NS, BF, EPI>, BM, BN, NS, 64 * (WM * WN + NL)>(a0, st, "spmma_f16_pc_kernel");
 }
-
 template <int BM, int BN, int WM, int WN, int NS, bool BF = false, bool EPI = false>
 static int launch_dma(const typename SpmmaArgsSel<EPI>::type& a0, hipStream_t st) {
-  typename SpmmaArgsSel<EPI>::type a = a0;
-  a.tiles_m = (a.Mrows + BM - 1) / BM;
-  a.tiles_n = (a.N + BN - 1) / BN;
-  const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("spmma_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  constexpr size_t lds_main = NS * ((size_t)BM * 72 + (size_t)64 * BN * 2);
-  constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
-  constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;  // the most this configuration ever asks for
-  // a K of fewer stages than the ring never touches the ring's other buffers: without them more workgroups share a CU
-  const size_t used = ((size_t)(a.kc / 64) < (size_t)NS ? (size_t)(a.kc / 64) : (size_t)NS) * ((size_t)BM * 72 + (size_t)64 * BN * 2);
-  const size_t lds_launch = used > lds_epi ? used : lds_epi;
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF, EPI>), lds, "spmma_f16_dma_kernel")) return rc;
-  }
-  spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF, EPI><<<dim3((unsigned)nwg), dim3(64 * WM * WN), lds_launch, st>>>(a);
-  return check_launch("spmma_f16_dma_kernel");
+  return launch_ring<&spmma_f16_dma_kernel<BM, BN, WM, WN, NS, BF, EPI>, BM, BN, NS, 64 * WM * WN>(a0, st, "spmma_f16_dma_kernel");
 }
 
 template <int BM, int BN, int WM, int WN, bool BF = false, bool EPI = false>
@@ -547,16 +521,10 @@ static int launch_cfg(const typename SpmmaArgsSel<EPI>::type& a0, hipStream_t st
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("spmma_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds_main = (size_t)BM * 144 + (size_t)(BN / 64) * 128 * 128;
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  spmma_f16_kernel<BM, BN, WM, WN, BF, EPI><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
-  return check_launch("spmma_f16_kernel");
+  return launch_grid<&spmma_f16_kernel<BM, BN, WM, WN, BF, EPI>>(nwg, 256, LDS_NO_OPTIN, lds, st, "spmma_f16", "spmma_f16_kernel", a);
 }
 
 }  // namespace sm

@@ -162,24 +162,15 @@ static int launch_fused_direct(const typename FusedArgsSel<EPI>::type& a0, hipSt
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_spmma_fused_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   // a single-stage problem (k = 64) never touches the ring's other buffers: without them more workgroups share a CU
   constexpr size_t stage_bytes = BM * 128 + 64 * BN * 2;
   const size_t lds_main = ((size_t)(a.K / 64) < (size_t)NS ? (size_t)(a.K / 64) : (size_t)NS) * stage_bytes;
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  // the opt-in records the most this instantiation can ever ask for, the launch below only what this K touches
+  // the opt-in records the most this instantiation can ever ask for, the launch only what this K touches
   constexpr size_t lds_max = NS * stage_bytes > lds_epi ? NS * stage_bytes : lds_epi;
-  static LdsOptIn lds_optin;
-  if (lds_max > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE, EPI>), lds_max, "spmma_f16_fused_direct_kernel")) return rc;
-  }
-  spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE, EPI><<<dim3((unsigned)nwg), dim3(64 * NWV), lds, st>>>(a);
-  return check_launch("spmma_f16_fused_direct_kernel");
+  return launch_grid<&spmma_f16_fused_direct_kernel<BN, NS, BF, BM, NWV, ANT, DENSE, EPI>>(nwg, 64 * NWV, lds_max, lds, st, "sm_spmma_fused_f16",
+                                                                                          "spmma_f16_fused_direct_kernel", a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -305,19 +296,11 @@ static int launch_fused_big(const typename FusedArgsSel<EPI>::type& a0, hipStrea
   a.tiles_m = (a.Mrows + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_spmma_fused_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds_main = (size_t)NSA * BM * 128 + (size_t)NSB * 64 * BN * 2;
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  static_assert(lds <= 160 * 1024, "LDS budget of the big direct kernel");
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE, EPI>), lds, "spmma_f16_fused_big_kernel")) return rc;
-  spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE, EPI><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a);
-  return check_launch("spmma_f16_fused_big_kernel");
+  static_assert(lds > 64 * 1024 && lds <= 160 * 1024, "LDS budget of the big direct kernel (always opted in)");
+  return launch_grid<&spmma_f16_fused_big_kernel<BN, BF, NSA, NSB, ANT, DENSE, EPI>>(nwg, 512, lds, lds, st, "sm_spmma_fused_f16", "spmma_f16_fused_big_kernel", a);
 }
 
 // a pointer the compiler cannot prove wave-uniform (an entry of the by-value pointer tables picked by a runtime index), made so
@@ -704,11 +687,9 @@ static int launch_fused_sk(const FusedArgs& a0, void* workspace, size_t workspac
   constexpr size_t lds_main = (size_t)3 * BM * 128 + (size_t)2 * 64 * BN * 2;
   constexpr size_t lds_epi = (size_t)BM * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  static_assert(lds <= 160 * 1024, "LDS budget of the stream-K kernel");
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_sk_kernel<BN, BF, ANT, DENSE>), lds, "spmma_f16_fused_sk_kernel")) return rc;
-  spmma_f16_fused_sk_kernel<BN, BF, ANT, DENSE><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a, s);
-  return check_launch("spmma_f16_fused_sk_kernel");
+  static_assert(lds > 64 * 1024 && lds <= 160 * 1024, "LDS budget of the stream-K kernel (always opted in)");
+  // (sk_launch_limits has settled the grid: 0 < nwg <= 1023)
+  return launch_grid<&spmma_f16_fused_sk_kernel<BN, BF, ANT, DENSE>>(nwg, 512, lds, lds, st, "sm_spmma_fused_f16", "spmma_f16_fused_sk_kernel", a, s);
 }
 
 // The dispatch rule of the workspace entry points: the stream-K form where the rounds of whole tiles leave CUs idle.  Costs in
@@ -881,10 +862,8 @@ static int launch_fused_span(const typename FusedArgsSel<EPI>::type& a0, hipStre
     set_error("sm_spmma_fused_{f16,bf16}: k too long for the span form (use the staged path)");
     return SM_STATUS_NOT_SUPPORTED;
   }
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_span_kernel<BN, BF, DENSE, EPI>), 160 * 1024, "spmma_f16_fused_span_kernel")) return rc;
-  spmma_f16_fused_span_kernel<BN, BF, DENSE, EPI><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a, (unsigned)span_lds, (size_t)a.Mrows * a.K * 2);
-  return check_launch("spmma_f16_fused_span_kernel");
+  return launch_grid<&spmma_f16_fused_span_kernel<BN, BF, DENSE, EPI>>(nwg, 256, 160 * 1024, lds, st, "sm_spmma_fused_f16", "spmma_f16_fused_span_kernel", a,
+                                                                      (unsigned)span_lds, (size_t)a.Mrows * a.K * 2);
 }
 
 // The B tile's LDS-DMA, shared by the B loader waves of the wide kernel and -- when it has none (NLB = 0) -- by its
@@ -1093,20 +1072,11 @@ static int launch_fused_wide(const typename FusedArgsSel<EPI>::type& a0, hipStre
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_spmma_fused_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t lds_main = 2 * (size_t)128 * 72 + (size_t)NSB * 64 * BN * 2;
   constexpr size_t lds_epi = (size_t)128 * (BN * 2 + 16);
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  static LdsOptIn lds_optin;
-  if (lds > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT, EPI>), lds, "spmma_f16_fused_wide_kernel")) return rc;
-  }
-  spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT, EPI><<<dim3((unsigned)nwg), dim3(64 * (WM * WN + 4 + NLB)), lds, st>>>(a);
-  return check_launch("spmma_f16_fused_wide_kernel");
+  return launch_grid<&spmma_f16_fused_wide_kernel<BN, WM, WN, NLB, PF, NSB, BF, ANT, EPI>>(nwg, 64 * (WM * WN + 4 + NLB), lds, lds, st, "sm_spmma_fused_f16",
+                                                                                          "spmma_f16_fused_wide_kernel", a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1347,22 +1317,20 @@ static int launch_fused_widep(const FusedArgs& a0, hipStream_t st) {
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nt = (size_t)a.tiles_m * a.tiles_n * a.batch * a.ngroup;
+  // (the limit is on the TILES, which the kernel counts in 32 bits, not on the grid below: stated here, not left to launch_grid)
   if (nt == 0) return SM_STATUS_SUCCESS;
   if (nt > 0x7fffffffu) {
     set_error("sm_spmma_fused_f16: grid too large");
     return SM_STATUS_NOT_SUPPORTED;
   }
   constexpr size_t lds = 2 * (size_t)128 * 72 + (size_t)NSB * 64 * BN * 2 + (size_t)(WM * WN) * 32 * (64 * 2 + 8);
-  static_assert(lds <= 160 * 1024, "LDS budget of the persistent wide kernel");
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_widep_kernel<BN, WM, WN, NLB, PF, NSB, BF>), lds, "spmma_f16_fused_widep_kernel")) return rc;
+  static_assert(lds > 64 * 1024 && lds <= 160 * 1024, "LDS budget of the persistent wide kernel (always opted in)");
   // one workgroup per CU (LDS); ids congruent mod 8 stay on one XCD across a workgroup's tiles when the grid is a multiple of 8
   size_t cus = (size_t)device_cu_count();
   cus -= cus % 8;
   if (cus == 0) cus = 8;
-  const unsigned grid = (unsigned)(nt <= cus ? nt : cus);
-  spmma_f16_fused_widep_kernel<BN, WM, WN, NLB, PF, NSB, BF><<<dim3(grid), dim3(64 * (WM * WN + 4 + NLB)), lds, st>>>(a, (unsigned)nt);
-  return check_launch("spmma_f16_fused_widep_kernel");
+  return launch_grid<&spmma_f16_fused_widep_kernel<BN, WM, WN, NLB, PF, NSB, BF>>(nt <= cus ? nt : cus, 64 * (WM * WN + 4 + NLB), lds, lds, st, "sm_spmma_fused_f16",
+                                                                                 "spmma_f16_fused_widep_kernel", a, (unsigned)nt);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1550,17 +1518,9 @@ static int launch_fused_astat(const FusedArgs& a0, hipStream_t st) {
   int tps = (a.tiles_n + nsplit - 1) / nsplit;
   nsplit = (a.tiles_n + tps - 1) / tps;  // no empty splits
   const size_t nwg = panels * nsplit;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_spmma_fused_f16: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr int NSB = 3;  // (a ring of 4 measured the same)
-  const size_t lds = astat_lds_bytes(a.K / 64, NSB);
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_fused_astat_kernel<NSB, BF>), (160 * 1024), "spmma_f16_fused_astat_kernel")) return rc;
-  spmma_f16_fused_astat_kernel<NSB, BF><<<dim3((unsigned)nwg), dim3(64 * 16), lds, st>>>(a, nsplit, tps);
-  return check_launch("spmma_f16_fused_astat_kernel");
+  return launch_grid<&spmma_f16_fused_astat_kernel<NSB, BF>>(nwg, 64 * 16, 160 * 1024, astat_lds_bytes(a.K / 64, NSB), st, "sm_spmma_fused_f16",
+                                                            "spmma_f16_fused_astat_kernel", a, nsplit, tps);
 }
 
 }  // namespace sm
@@ -1576,10 +1536,11 @@ using namespace sm;
 // ---------------------------------------------------------------------------------------------
 // span form: rows that are not whole 64-deep stages of 16-byte pieces, when A is one tall contiguous matrix, n <= 128 and a 128-row
 // span + the whole B fit the LDS (k = 147: the stem layer of every ResNet)
+// (the LDS bound of both rules that pick the span form -- the one below and the dense twin's; launch_fused_span's own exact figure is tighter)
+static bool span_lds_fits(size_t n, size_t k) { return ((size_t)128 * k * 2 + 1152) + ((k + 63) / 64 * 64) * (n <= 64 ? 64 : 128) * 2 <= 160 * 1024; }
 static bool span_form_takes(size_t m, size_t n, size_t k, size_t lda, size_t batch, size_t strideA, size_t strideB, size_t strideC, bool all_aligned, bool c_aligned) {
   return (k % 64 != 0 || lda % 8 != 0) && lda == k && n % 8 == 0 && n <= 128 && all_aligned && c_aligned && (batch == 1 || (strideB == 0 && strideA == m * lda && strideC == m * n)) &&
-         (m * batch * k * 2) % 16 == 0 && m * batch <= 0x7fffffffull && k <= 0x7fffffffull &&
-         ((size_t)128 * k * 2 + 1152) + ((k + 63) / 64 * 64) * (n <= 64 ? 64 : 128) * 2 <= 160 * 1024;
+         (m * batch * k * 2) % 16 == 0 && m * batch <= 0x7fffffffull && k <= 0x7fffffffull && span_lds_fits(n, k);
 }
 // whole 64-deep stages of 16-byte aligned rows (every other kernel of this file)
 static bool stage_forms_take(size_t n, size_t k, size_t lda, size_t strideA, size_t strideB, bool all_aligned) {
@@ -1883,7 +1844,7 @@ static int dense_twin16(const DenseTwinCall& c, hipStream_t st) {
   // ragged k: the span form -- one tall contiguous A per problem (lda == k), n <= 128, span + whole B inside the LDS
   if (k % 64 != 0 || c.lda % 8 != 0) {
     if (c.lda != c.K || n > 128 || ((size_t)c.M * k * 2) % 16 != 0 || (c.batch > 1 && !tables)) return SM_STATUS_NOT_SUPPORTED;
-    if (((size_t)128 * k * 2 + 1152) + ((k + 63) / 64 * 64) * (n <= 64 ? 64 : 128) * 2 > 160 * 1024) return SM_STATUS_NOT_SUPPORTED;
+    if (!span_lds_fits(n, k)) return SM_STATUS_NOT_SUPPORTED;
     a.ngroup = c.batch;  // the span kernel indexes problems, not grid batches: with tables every batch entry is a problem
     a.batch = 1;
     if (!tables) a.ngroup = 1;

@@ -178,22 +178,12 @@ static int launch_pruned(const PrunedArgs& a0, hipStream_t st) {
   PrunedArgs a = a0;
   a.tiles_m = (a.Mrows + 127) / 128;
   const size_t nwg = (size_t)a.tiles_m * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_prune24_spmma: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t stage_bytes = 128 * 128 + 64 * BN * 2;
   constexpr size_t lds_epi = (size_t)128 * (BN * 2 + 16);
   const size_t lds_main = (a.K / 64 < 2 ? 1 : 2) * stage_bytes;
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   constexpr size_t lds_max = 2 * stage_bytes > lds_epi ? 2 * stage_bytes : lds_epi;
-  static LdsOptIn lds_optin;
-  if (lds_max > 64 * 1024) {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f16_pruned_kernel<BN, BF, TILE>), lds_max, "spmma_f16_pruned_kernel")) return rc;
-  }
-  spmma_f16_pruned_kernel<BN, BF, TILE><<<dim3((unsigned)nwg), dim3(256), lds, st>>>(a);
-  return check_launch("spmma_f16_pruned_kernel");
+  return launch_grid<&spmma_f16_pruned_kernel<BN, BF, TILE>>(nwg, 256, lds_max, lds, st, "sm_prune24_spmma", "spmma_f16_pruned_kernel", a);
 }
 
 template <bool BF>

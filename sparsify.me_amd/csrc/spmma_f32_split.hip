@@ -565,17 +565,9 @@ static int launch_split_cols(const SplitArgs& a0, hipStream_t st) {
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = 1;
   const size_t nwg = (size_t)a.tiles_m * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_spmma_fused_f32_split: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
-  constexpr size_t lds = 2 * (size_t)128 * 256 + 2 * (size_t)NP * 64 * 128 * 2;
-  static_assert(lds <= 160 * 1024 && (size_t)128 * (128 * 4 + 16) <= lds, "LDS budget");
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f32_split_cols_kernel<CT, NP, DENSE>), lds, "spmma_f32_split_cols_kernel")) return rc;
-  spmma_f32_split_cols_kernel<CT, NP, DENSE><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a);
-  return check_launch("spmma_f32_split_cols_kernel");
+  constexpr size_t lds = 2 * (size_t)128 * 256 + 2 * (size_t)NP * 64 * 128 * 2;  // (more than 64 KiB for every NP: always opted in)
+  static_assert(lds > 64 * 1024 && lds <= 160 * 1024 && (size_t)128 * (128 * 4 + 16) <= lds, "LDS budget");
+  return launch_grid<&spmma_f32_split_cols_kernel<CT, NP, DENSE>>(nwg, 512, lds, lds, st, "sm_spmma_fused_f32_split", "spmma_f32_split_cols_kernel", a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -678,10 +670,8 @@ static int launch_split_span(const SplitArgs& a0, hipStream_t st) {
     set_error("sm_spmma_fused_f32_split: k too long for the span form (use sm_spmma_fused_f32)");
     return SM_STATUS_NOT_SUPPORTED;
   }
-  static LdsOptIn lds_optin;
-  if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f32_split_span_kernel<BN, NP, DENSE>), 160 * 1024, "spmma_f32_split_span_kernel")) return rc;
-  spmma_f32_split_span_kernel<BN, NP, DENSE><<<dim3((unsigned)nwg), dim3(512), lds, st>>>(a, (unsigned)span_lds, (size_t)a.Mrows * a.K * 4);
-  return check_launch("spmma_f32_split_span_kernel");
+  return launch_grid<&spmma_f32_split_span_kernel<BN, NP, DENSE>>(nwg, 512, 160 * 1024, lds, st, "sm_spmma_fused_f32_split", "spmma_f32_split_span_kernel", a,
+                                                                 (unsigned)span_lds, (size_t)a.Mrows * a.K * 4);
 }
 
 // B (fp32, [k][n] row-major per batch) -> planes of truncated bfloat16 pieces, 8 elements per thread
@@ -714,26 +704,16 @@ static int launch_split(const SplitArgs& a0, hipStream_t st) {
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + BN - 1) / BN;
   const size_t nwg = (size_t)a.tiles_m * a.tiles_n * a.batch;
-  if (nwg == 0) return SM_STATUS_SUCCESS;
-  if (nwg > 0x7fffffffu) {
-    set_error("sm_spmma_fused_f32_split: grid too large");
-    return SM_STATUS_NOT_SUPPORTED;
-  }
   constexpr size_t stage_bytes = (size_t)128 * 256 + (size_t)NP * 64 * BN * 2;
   constexpr size_t lds_epi = (size_t)128 * (BN * 4 + 16);
   const size_t lds_main = (a.K / 64 < 2 ? 1 : 2) * stage_bytes;
   const size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  constexpr size_t lds_max = 2 * stage_bytes > lds_epi ? 2 * stage_bytes : lds_epi;
-  static_assert(lds_max <= 160 * 1024, "LDS budget");
-  static LdsOptIn lds_optin, lds_optin_nt;
-  if (a.tiles_n == 1) {  // A is read once by the whole grid: non-temporal
-    if (const int rc = ensure_dyn_lds(lds_optin_nt, reinterpret_cast<const void*>(&spmma_f32_split_kernel<BN, NP, true, NW, DENSE>), lds_max, "spmma_f32_split_kernel")) return rc;
-    spmma_f32_split_kernel<BN, NP, true, NW, DENSE><<<dim3((unsigned)nwg), dim3(64 * NW), lds, st>>>(a);
-  } else {
-    if (const int rc = ensure_dyn_lds(lds_optin, reinterpret_cast<const void*>(&spmma_f32_split_kernel<BN, NP, false, NW, DENSE>), lds_max, "spmma_f32_split_kernel")) return rc;
-    spmma_f32_split_kernel<BN, NP, false, NW, DENSE><<<dim3((unsigned)nwg), dim3(64 * NW), lds, st>>>(a);
-  }
-  return check_launch("spmma_f32_split_kernel");
+  constexpr size_t lds_max = 2 * stage_bytes > lds_epi ? 2 * stage_bytes : lds_epi;  // (more than 64 KiB for every NP, BN: always opted in)
+  static_assert(lds_max > 64 * 1024 && lds_max <= 160 * 1024, "LDS budget");
+  const char* const who = "sm_spmma_fused_f32_split";
+  if (a.tiles_n == 1)  // A is read once by the whole grid: non-temporal
+    return launch_grid<&spmma_f32_split_kernel<BN, NP, true, NW, DENSE>>(nwg, 64 * NW, lds_max, lds, st, who, "spmma_f32_split_kernel", a);
+  return launch_grid<&spmma_f32_split_kernel<BN, NP, false, NW, DENSE>>(nwg, 64 * NW, lds_max, lds, st, who, "spmma_f32_split_kernel", a);
 }
 
 }  // namespace sm
