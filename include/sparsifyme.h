@@ -719,9 +719,15 @@ int sm_gemm_rowmajor_f32_split(const float* A, const float* B, float* C, size_t 
  *      ta / tb (gemm.hxx:33-34): SM_OP_N or SM_OP_T; a transposed operand is read as its stored k x m
  *      (n x k) form through the same leading dimension, which must cover a stored column (m >= k for
  *      ta = T, k >= n for tb = T; SM_STATUS_INVALID_VALUE otherwise, as the vendor BLAS).
- *      Precondition of the f32 / f64 forms: every pointer in the arrays is 16-byte aligned (f64: 8-byte; what hipMalloc returns
- *      is).  The arrays live on the device, so the library cannot look at the bases before it picks the 16-byte-chunk pipeline,
- *      and nothing checks them. */
+ *      Precondition of every form (f16, f16_ws, f32, f64): every pointer in the arrays is 16-byte aligned (f64: 8-byte; what
+ *      hipMalloc returns is).  The arrays live on the device, so the library cannot look at the bases before it picks a
+ *      16-byte-chunk pipeline -- the f16 forms choose their 16-byte vector loads, the LDS-DMA kernel and the dense twin of the
+ *      fused kernels from m and k alone -- and nothing checks them.
+ *      sm_gemm_batched_f16_ws (declared with the other workspace entry points above) is sm_gemm_batched_f16 with the stream-K
+ *      workspace of sm_spmma_fused_workspace_size: for non-transposed operands with 128 < m <= 256, m % 8 == 0, k % 64 == 0 and
+ *      k >= 2048 it runs the stream-K dense twin where sm_spmma_fused_streamk_plan(n, m, k, batch) takes the launch and the
+ *      workspace holds its slots; a null or too small workspace, and every other shape, runs exactly what sm_gemm_batched_f16
+ *      runs.  Same workspace contract as sm_spmma_fused_*_ws (the first 4096 bytes zero before a call; they come back zero). */
 int sm_gemm_batched_f16(const void* const* A_ptrs, const void* const* B_ptrs, void* const* C_ptrs,
                         size_t m, size_t n, size_t k, size_t batch, int ta, int tb, float alpha,
                         float beta, sm_stream_t stream);
