@@ -1341,18 +1341,29 @@ static int launch_fused_widep(const FusedArgs& a0, hipStream_t st) {
 // B streams through its own ring across tile boundaries (no drain); each consumer wave stores its own 32 x 64
 // piece of C through a wave-private LDS patch (no barrier in the epilogue), so the loaders keep prefetching the
 // next tile's B while C is written.  beta == 0 only (the caller falls back to the wide kernel otherwise).
+//
+// TWO WORKGROUPS PER CU (NLA == 0, k <= 256; launch_fused_astat picks it): the same kernel without the four barrier-only waves, with
+// a B ring of 2 and C patches of PR = 16 (k <= 192) or 8 (k = 256) rows, so that a workgroup takes at most 80 KiB of LDS and
+// astat_waves_per_simd() x 4 waves of at most 80 registers: the dispatcher places a second, independent 128-row panel on the CU,
+// whose stages run while this one waits for its A panel, for a B slot or for its C stores.  Phase 1 holds two rows per lane where
+// the workgroup has fewer than 16 waves (k <= 256: the same eight 16-byte registers).  Same image, same ring order, same
+// smfmac_stage on the same operands: the same C bit for bit.
 // ---------------------------------------------------------------------------------------------
-template <int NSB, bool BF = false>
-__global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const FusedArgs p, int nsplit, int tiles_per_split) {
-  constexpr int BM = 128, BN = 128, WM = 4, WN = 2, NC = 8, NLA = 4, NLB = 4;
-  static_assert(NC + NLA + NLB == 16, "launch bounds");
+// waves per SIMD asked of the register allocator: the 16-wave workgroup's own 4; twice a smaller workgroup's share (12 waves: 6 = 80 registers)
+constexpr int astat_waves_per_simd(int nwaves) { return nwaves == 16 ? 4 : (2 * nwaves + 3) / 4; }
+template <int NSB, bool BF = false, int NLA = 4, int NLB = 4, int PR = 32>
+__global__ __launch_bounds__(64 * (8 + NLA + NLB), astat_waves_per_simd(8 + NLA + NLB)) void spmma_f16_fused_astat_kernel(const FusedArgs p, int nsplit, int tiles_per_split) {
+  constexpr int BM = 128, BN = 128, WM = 4, WN = 2, NC = 8;
+  constexpr int NW = NC + NLA + NLB, RPL = (16 + NW - 1) / NW, KTM = 8 / RPL;  // phase 1: RPL rows per lane, at most KTM stages
+  static_assert(NW <= 16 && RPL <= 2 && (PR == 32 || PR == 16 || PR == 8), "launch bounds, phase-1 registers, patch passes");
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 16, FN = TN / 16;  // wave tile 32 x 64
   constexpr int SA = BM * 64, SM_ = BM * 8, ASTG = SA + SM_, SB = 64 * BN * 2;
   constexpr int B_N = BN / 8, B_WI = B_N / NLB;
   static_assert((NSB - 2) * B_WI <= 63, "vmcnt range");
   // wave-private C patch: 32 rows x 136 B.  34 dwords per row: the four 4-row groups a ds_write_b16 instruction
   // touches (rows 4g + q) start 8 banks apart, each covering 8 banks: no conflict beyond the two halves of a dword
-  constexpr int WPITCH = TN * 2 + 8, WPATCH = TM * WPITCH;
+  constexpr int WPITCH = TN * 2 + 8, WPATCH = PR * WPITCH;
+  static_assert(NLA != 0 || (PR == 16 ? 3 : 4) * ASTG + NSB * SB + NC * WPATCH <= 80 * 1024, "two workgroups per CU: 80 KiB each (astat_pair_lds_bytes)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const unsigned tid = threadIdx.x, lane = tid & 63u;
@@ -1376,13 +1387,16 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
   const unsigned lwb = is_b ? wave - (NC + NLA) : 0u;
   const char* Bb = reinterpret_cast<const char*>(p.B[grp] + (size_t)b * p.sB);
   unsigned b_kr[B_WI], b_col[B_WI], b_dst[B_WI];
+  auto b_lanes = [&](unsigned ln) {
 #pragma unroll
-  for (int i = 0; i < B_WI; ++i) {
-    const unsigned j = lwb + (unsigned)NLB * i, panel = j >> 3, grp = j & 7u, kr = 8u * grp + (lane >> 3);
-    b_kr[i] = kr;
-    b_col[i] = 64u * panel + 8u * ((lane & 7u) ^ b_swz(kr));
-    b_dst[i] = panel * 8192u + grp * 1024u;
-  }
+    for (int i = 0; i < B_WI; ++i) {
+      const unsigned j = lwb + (unsigned)NLB * i, panel = j >> 3, grp = j & 7u, kr = 8u * grp + (ln >> 3);
+      b_kr[i] = kr;
+      b_col[i] = 64u * panel + 8u * ((ln & 7u) ^ b_swz(kr));
+      b_dst[i] = panel * 8192u + grp * 1024u;
+    }
+  };
+  b_lanes(lane);
   const size_t row_bytes = (size_t)p.N * 2;
   int i_nt = nt0, i_kt = 0, i_buf = 0;  // the next B stage to issue
   auto issue_b = [&]() {
@@ -1402,30 +1416,50 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
       if (s < T) issue_b();
   }
 
-  // ---- phase 1, all 16 waves: the 2:4 image of the row panel for the whole K.  Wave w owns rows 8w .. 8w+7: one
-  // 16-byte load per lane and stage, all stages in flight at once (K <= 512: at most 8 loads), then selection.
+  // ---- phase 1, all waves: the 2:4 image of the row panel for the whole K.  Wave w owns rows 8w .. 8w+7 (and, of fewer than 16
+  // waves, rows 8(w + NW) .. too): one 16-byte load per lane, row and stage, all in flight at once (at most 8 loads), then selection.
   {
     const half_t* A = p.A[grp] + (size_t)b * p.sA;
-    const unsigned row = 8u * wave + (lane >> 3), c8 = lane & 7u;
-    int gr = m0 + (int)row;
-    gr = gr < p.Mrows - 1 ? gr : p.Mrows - 1;
-    const half_t* a_src = A + (size_t)gr * p.lda + 8u * c8;
-    const unsigned a_val_off = row * 64u + 16u * ((c8 >> 1) ^ a64_swz(row)) + 8u * (c8 & 1u);
-    const unsigned a_meta_off = SA + row * 8u + c8;
-    u4 ra[8];
+    const unsigned c8 = lane & 7u;
+    u4 ra[RPL][KTM];
 #pragma unroll
-    for (int s = 0; s < 8; ++s)
-      if (s < nkt) ra[s] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(a_src + (size_t)s * 64));
+    for (int h = 0; h < RPL; ++h) {
+      const unsigned rg = wave + (unsigned)(NW * h);
+      if (RPL == 1 || rg < 16u) {
+        int gr = m0 + (int)(8u * rg + (lane >> 3));
+        gr = gr < p.Mrows - 1 ? gr : p.Mrows - 1;
+        const half_t* a_src = A + (size_t)gr * p.lda + 8u * c8;
 #pragma unroll
-    for (int s = 0; s < 8; ++s)
-      if (s < nkt) {
-        uint32_t k0, k1, n0, n1;
-        strip_select_f16(ra[s][0], ra[s][1], k0, n0);
-        strip_select_f16(ra[s][2], ra[s][3], k1, n1);
-        char* sb = smem + s * ASTG;
-        *reinterpret_cast<u2*>(sb + a_val_off) = u2{k0, k1};
-        *reinterpret_cast<unsigned char*>(sb + a_meta_off) = (unsigned char)(n0 | (n1 << 4));
+        for (int s = 0; s < KTM; ++s)
+          if (s < nkt) ra[h][s] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(a_src + (size_t)s * 64));
       }
+    }
+#pragma unroll
+    for (int h = 0; h < RPL; ++h) {
+      const unsigned rg = wave + (unsigned)(NW * h);
+      if (RPL == 1 || rg < 16u) {
+        const unsigned row = 8u * rg + (lane >> 3);
+        const unsigned a_val_off = row * 64u + 16u * ((c8 >> 1) ^ a64_swz(row)) + 8u * (c8 & 1u);
+        const unsigned a_meta_off = SA + row * 8u + c8;
+#pragma unroll
+        for (int s = 0; s < KTM; ++s)
+          if (s < nkt) {
+            uint32_t k0, k1, n0, n1;
+            strip_select_f16(ra[h][s][0], ra[h][s][1], k0, n0);
+            strip_select_f16(ra[h][s][2], ra[h][s][3], k1, n1);
+            char* sb = smem + s * ASTG;
+            *reinterpret_cast<u2*>(sb + a_val_off) = u2{k0, k1};
+            *reinterpret_cast<unsigned char*>(sb + a_meta_off) = (unsigned char)(n0 | (n1 << 4));
+          }
+      }
+    }
+  }
+  if constexpr (RPL > 1) {
+    // two rows per lane in phase 1: inside 80 registers there is no room to carry the loaders' twelve lane constants through it,
+    // so they are computed again here, from a lane id the compiler cannot trace back (a few VALU instructions, once per workgroup)
+    unsigned ln = lane;
+    asm volatile("" : "+v"(ln));
+    b_lanes(ln);
   }
   __syncthreads();  // the image is complete (and the B prologue has landed)
   if (wave >= (unsigned)NC && !is_b) {  // 4 of the 16 waves were only needed for phase 1: they just keep the barrier count
@@ -1462,28 +1496,66 @@ __global__ __launch_bounds__(64 * 16) void spmma_f16_fused_astat_kernel(const Fu
       cb = cb + 1 == NSB ? 0 : cb + 1;
       if (++kt == nkt) {
         // ---- this column tile is done: C piece of this wave through its private LDS patch, 16-byte row pieces out
+        if constexpr (PR == TM) {
+          const int gc = nt * BN + (int)(wn * TN) + 8 * (int)(lane & 7u);
 #pragma unroll
-        for (int i = 0; i < FM; ++i)
+          for (int i = 0; i < FM; ++i)
 #pragma unroll
-          for (int j = 0; j < FN; ++j) {
-            const unsigned lr = i * 16 + 4u * g, lc = j * 16 + r;
+            for (int j = 0; j < FN; ++j) {
+              const unsigned lr = i * 16 + 4u * g, lc = j * 16 + r;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              *reinterpret_cast<half_t*>(patch + (lr + q) * WPITCH + lc * 2) = to_elt<BF>(p.alpha * acc[i][j][q]);
-              acc[i][j][q] = 0.f;
+              for (int q = 0; q < 4; ++q) {
+                *reinterpret_cast<half_t*>(patch + (lr + q) * WPITCH + lc * 2) = to_elt<BF>(p.alpha * acc[i][j][q]);
+                acc[i][j][q] = 0.f;
+              }
+            }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave wrote and reads: no barrier
+#pragma unroll
+          for (int s = 0; s < TM / 8; ++s) {
+            const unsigned lr = 8u * s + (lane >> 3);
+            const int gr = m0 + (int)(wm * TM + lr);
+            if (gr < p.Mrows && gc < p.N) {
+              const u2 lo = *reinterpret_cast<const u2*>(patch + lr * WPITCH + 16u * (lane & 7u));  // rows are 8-byte aligned
+              const u2 hi = *reinterpret_cast<const u2*>(patch + lr * WPITCH + 16u * (lane & 7u) + 8u);
+              __builtin_nontemporal_store(u4{lo[0], lo[1], hi[0], hi[1]}, reinterpret_cast<u4*>(C + (size_t)gr * p.N + gc));
             }
           }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave wrote and reads: no barrier
-        const int gc = nt * BN + (int)(wn * TN) + 8 * (int)(lane & 7u);
+        } else {
+          // a patch of PR < 32 rows: the piece goes out in 32 / PR passes of PR rows (PR = 8: the lanes of 4-row groups 2h, 2h + 1
+          // write pass h).  One wave's LDS instructions execute in order, so a pass may overwrite the rows the one before it read.
+          // (the store addresses are built per tile from a lane id the compiler cannot trace back: hoisted out of the stage loop
+          // as invariants they would not fit the 80 registers)
+          unsigned le = lane;
+          asm volatile("" : "+v"(le));
+          const int gce = nt * BN + (int)(wn * TN) + 8 * (int)(le & 7u);
 #pragma unroll
-        for (int s = 0; s < TM / 8; ++s) {
-          const unsigned lr = 8u * s + (lane >> 3);
-          const int gr = m0 + (int)(wm * TM + lr);
-          if (gr < p.Mrows && gc < p.N) {
-            const u2 lo = *reinterpret_cast<const u2*>(patch + lr * WPITCH + 16u * (lane & 7u));  // rows are 8-byte aligned
-            const u2 hi = *reinterpret_cast<const u2*>(patch + lr * WPITCH + 16u * (lane & 7u) + 8u);
-            __builtin_nontemporal_store(u4{lo[0], lo[1], hi[0], hi[1]}, reinterpret_cast<u4*>(C + (size_t)gr * p.N + gc));
-          }
+          for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int h = 0; h < 16 / PR; ++h) {
+              if (PR == 16 || (g >> 1) == (unsigned)h) {
+#pragma unroll
+                for (int j = 0; j < FN; ++j) {
+                  const unsigned lr = 4u * (g & (unsigned)(PR / 4 - 1)), lc = j * 16 + r;
+#pragma unroll
+                  for (int q = 0; q < 4; ++q) *reinterpret_cast<half_t*>(patch + (lr + q) * WPITCH + lc * 2) = to_elt<BF>(p.alpha * acc[i][j][q]);
+                }
+              }
+              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave wrote and reads: no barrier
+#pragma unroll
+              for (int s = 0; s < PR / 8; ++s) {
+                const unsigned lr = 8u * s + (le >> 3);
+                const int gr = m0 + (int)(wm * TM + i * 16 + h * PR + lr);
+                if (gr < p.Mrows && gce < p.N) {
+                  const u2 lo = *reinterpret_cast<const u2*>(patch + lr * WPITCH + 16u * (le & 7u));  // rows are 8-byte aligned
+                  const u2 hi = *reinterpret_cast<const u2*>(patch + lr * WPITCH + 16u * (le & 7u) + 8u);
+                  __builtin_nontemporal_store(u4{lo[0], lo[1], hi[0], hi[1]}, reinterpret_cast<u4*>(C + (size_t)gr * p.N + gce));
+                }
+              }
+            }
+#pragma unroll
+          for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int j = 0; j < FN; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
         }
         kt = 0;
         ++nt;
@@ -1508,16 +1580,72 @@ static size_t astat_nsplit(size_t panels, size_t tiles_n, size_t cus) {
 }
 static size_t astat_lds_bytes(int nkt, int nsb) { return (size_t)nkt * (128 * 72) + (size_t)nsb * 64 * 128 * 2 + 8 * 32 * (64 * 2 + 8); }
 
+// Which A-stationary kernel runs: ONE statement.  The two-per-CU instantiations exist where an image of k / 64 stages, a B ring of 2
+// and the patches fit 80 KiB: k <= 256 (16-row patches up to k = 192: 77 824 B; 8-row patches at k = 256: 78 336 B).  Up to k = 192
+// every measured grid (150 .. 3136 workgroups) is 5-25 % faster two per CU.  At k = 256 the stage loop is bound by the CU's LDS reads
+// (8 consumer waves x 10 KiB per stage), which two resident workgroups share: 2-5 % faster where every workgroup walks all its
+// column tiles (nsplit == 1) on a grid of 448 .. 1344 workgroups, 3-15 % SLOWER on the column-split grids of 196, 256 and 448 --
+// those, and the unsplit grids under 7/4 workgroups per CU that were not measured, keep the one-per-CU kernel, as does every
+// k > 256 (profiles/astat_two_per_cu_ab.txt).
+constexpr int ASTAT_PAIR_NLB = 4;  // B loader waves beside the 8 consumers: 12 waves, 3 per SIMD and workgroup (2 loaders: 4-24 % slower)
+static bool astat_pair_takes(int nkt, size_t nwg, int nsplit, size_t cus) { return nkt <= 3 || (nkt == 4 && nsplit == 1 && 4 * nwg >= 7 * cus); }
+static size_t astat_pair_lds_bytes(int nkt) { return (size_t)nkt * (128 * 72) + (size_t)2 * 64 * 128 * 2 + 8 * (nkt <= 3 ? 16 : 8) * (64 * 2 + 8); }
+static_assert(3 * (128 * 72) + 2 * 64 * 128 * 2 + 8 * 16 * 136 == 77824 && 4 * (128 * 72) + 2 * 64 * 128 * 2 + 8 * 8 * 136 == 78336, "LDS of the two-per-CU kernels");
+
+// Whether the runtime reports two workgroups of KERNEL (with `lds` bytes each) resident on one CU of the current device: asked once
+// per instantiation and device, and never inside a stream capture -- until it could be asked the answer is "no" (that launch runs
+// the one-per-CU kernel), and "no" it stays on a device whose CUs hold only one.
+template <auto KERNEL>
+static bool two_resident_per_cu(unsigned threads, size_t lds, hipStream_t st) {
+  static std::atomic<signed char> known[256];  // per device ordinal -- 0: not asked, 1: two fit, -1: they do not
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 256) return false;
+  signed char k = known[dev].load(std::memory_order_relaxed);
+  if (k == 0) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    if (cs != hipStreamCaptureStatusNone) return false;
+    static LdsOptIn optin;
+    int nb = 0;
+    if (ensure_dyn_lds(optin, reinterpret_cast<const void*>(KERNEL), lds, "spmma_f16_fused_astat_kernel") != SM_STATUS_SUCCESS ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL, (int)threads, lds) != hipSuccess) {
+      (void)hipGetLastError();
+      nb = 0;
+    }
+    k = nb >= 2 ? 1 : -1;
+    known[dev].store(k, std::memory_order_relaxed);
+  }
+  return k > 0;
+}
+
 template <bool BF = false>
 static int launch_fused_astat(const FusedArgs& a0, hipStream_t st) {
   FusedArgs a = a0;
   a.tiles_m = (a.Mrows + 127) / 128;
   a.tiles_n = (a.N + 127) / 128;
   const size_t panels = (size_t)a.tiles_m * a.batch * a.ngroup;
-  int nsplit = (int)astat_nsplit(panels, (size_t)a.tiles_n, (size_t)device_cu_count());
+  const size_t cus = (size_t)device_cu_count();
+  int nsplit = (int)astat_nsplit(panels, (size_t)a.tiles_n, cus);
   int tps = (a.tiles_n + nsplit - 1) / nsplit;
   nsplit = (a.tiles_n + tps - 1) / tps;  // no empty splits
   const size_t nwg = panels * nsplit;
+  const int nkt = a.K / 64;
+  if (astat_pair_takes(nkt, nwg, nsplit, cus)) {
+    constexpr unsigned threads = 64 * (8 + ASTAT_PAIR_NLB);
+    const size_t lds = astat_pair_lds_bytes(nkt);
+    if (nkt <= 3) {
+      constexpr auto kernel = &spmma_f16_fused_astat_kernel<2, BF, 0, ASTAT_PAIR_NLB, 16>;
+      if (two_resident_per_cu<kernel>(threads, 80 * 1024, st))
+        return launch_grid<kernel>(nwg, threads, 80 * 1024, lds, st, "sm_spmma_fused_f16", "spmma_f16_fused_astat_kernel", a, nsplit, tps);
+    } else {
+      constexpr auto kernel = &spmma_f16_fused_astat_kernel<2, BF, 0, ASTAT_PAIR_NLB, 8>;
+      if (two_resident_per_cu<kernel>(threads, 80 * 1024, st))
+        return launch_grid<kernel>(nwg, threads, 80 * 1024, lds, st, "sm_spmma_fused_f16", "spmma_f16_fused_astat_kernel", a, nsplit, tps);
+    }
+  }
   constexpr int NSB = 3;  // (a ring of 4 measured the same)
   return launch_grid<&spmma_f16_fused_astat_kernel<NSB, BF>>(nwg, 64 * 16, 160 * 1024, astat_lds_bytes(a.K / 64, NSB), st, "sm_spmma_fused_f16",
                                                             "spmma_f16_fused_astat_kernel", a, nsplit, tps);
