@@ -36,6 +36,10 @@ template <typename T>
 struct spmma_fns;
 template <>
 struct spmma_fns<float> {
+  static int moe_gate_on(const void* logits, const float* bias, int* ids, float* w, std::size_t tokens, std::size_t experts, std::size_t top_k,
+                         std::size_t ld, int scoring, int renorm, float scale, hipStream_t st) {
+    return sm_moe_gate_f32(logits, bias, ids, w, tokens, experts, top_k, ld, scoring, renorm, scale, st);
+  }
   static int fused(float* A, float* B, float* C, std::size_t m, std::size_t n, std::size_t k, std::size_t b, float al, float be) {
     return sm_spmma_fused_f32(A, B, C, m, n, k, k, b, m * k, k * n, m * n, al, be, nullptr);
   }
@@ -108,6 +112,10 @@ struct spmma_fns_f16 {
                             std::size_t hidden, std::size_t rows_p, std::size_t ldp, std::size_t ldo, hipStream_t st) {
     return sm_moe_combine_f16(Yp, pos, w, R, out, tokens, top_k, hidden, rows_p, ldp, ldo, st);
   }
+  static int moe_gate_on(const void* logits, const float* bias, int* ids, float* w, std::size_t tokens, std::size_t experts, std::size_t top_k,
+                         std::size_t ld, int scoring, int renorm, float scale, hipStream_t st) {
+    return sm_moe_gate_f16(logits, bias, ids, w, tokens, experts, top_k, ld, scoring, renorm, scale, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -178,6 +186,10 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
   static int moe_combine_on(const void* Yp, const int* pos, const float* w, const void* R, void* out, std::size_t tokens, std::size_t top_k,
                             std::size_t hidden, std::size_t rows_p, std::size_t ldp, std::size_t ldo, hipStream_t st) {
     return sm_moe_combine_bf16(Yp, pos, w, R, out, tokens, top_k, hidden, rows_p, ldp, ldo, st);
+  }
+  static int moe_gate_on(const void* logits, const float* bias, int* ids, float* w, std::size_t tokens, std::size_t experts, std::size_t top_k,
+                         std::size_t ld, int scoring, int renorm, float scale, hipStream_t st) {
+    return sm_moe_gate_bf16(logits, bias, ids, w, tokens, experts, top_k, ld, scoring, renorm, scale, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -638,6 +650,18 @@ inline std::size_t moe_route_workspace(std::size_t tokens, std::size_t top_k, st
 inline int moe_route(const int* d_expert_ids, std::size_t tokens, std::size_t top_k, std::size_t groups, int* d_offsets, int* d_sorted_token,
                      int* d_sorted_pair, int* d_pair_pos, void* workspace = nullptr, std::size_t workspace_bytes = 0, hipStream_t stream = nullptr) {
   return sm_moe_route(d_expert_ids, tokens, top_k, groups, d_offsets, d_sorted_token, d_sorted_pair, d_pair_pos, workspace, workspace_bytes, stream);
+}
+
+// Extension (fp16 / bfloat16 / float logits): the MoE gate (sm_moe_gate_*): logits[tokens][experts] (row pitch ld, 0 = experts) to
+// d_topk_ids (int32) and d_topk_weights (fp32), both tokens * top_k values in pair order -- moe_route's d_expert_ids and moe_combine's
+// d_weights.  Descending key, equal keys in ascending expert index; scoring SM_MOE_SCORE_SOFTMAX / _SIGMOID, renormalised over the top_k
+// or not, times scale; d_select_bias (experts floats, sigmoid only, selection only) may be null.  Enqueue only.
+template <typename type_t>
+int moe_gate(const type_t* d_logits, int* d_topk_ids, float* d_topk_weights, std::size_t tokens, std::size_t experts, std::size_t top_k,
+             int scoring = SM_MOE_SCORE_SOFTMAX, bool renormalize = true, float scale = 1.0f, const float* d_select_bias = nullptr,
+             hipStream_t stream = nullptr, std::size_t ld = 0) {
+  return detail::spmma_fns<type_t>::moe_gate_on(d_logits, d_select_bias, d_topk_ids, d_topk_weights, tokens, experts, top_k, ld ? ld : experts, scoring,
+                                                renormalize ? 1 : 0, scale, stream);
 }
 
 // Extension (fp16 / bfloat16): the un-permute and weighted sum over top_k that close the block (sm_moe_combine_*):

@@ -676,6 +676,54 @@ int sm_moe_combine_bf16(const void* Yp, const int* pair_pos, const float* weight
                         size_t hidden, size_t rows_p, size_t ldp, size_t ldo, sm_stream_t stream);
 int sm_moe_combine_form(const void* Yp, const void* R, const void* out, size_t hidden, size_t ldp, size_t ldo, int* form);
 
+/* ---- MoE gate (extension): the router's logits to top_k expert ids and fp32 weights per token, in one launch; fp16 / bf16 / fp32 logits.
+ *      logits[tokens][experts], row pitch ld >= experts in elements, no alignment beyond the element's.  topk_ids (int32) and
+ *      topk_weights (fp32) are [tokens][top_k], compact, in pair order p = t * top_k + j: what sm_moe_route reads as expert_ids and
+ *      sm_moe_combine_* as weights.  select_bias: `experts` floats in DEVICE memory, or NULL; it takes part in the selection only, never
+ *      in the weights (the sigmoid router's correction bias).  x_e is the logit converted exactly to fp32.
+ *      Selection key:
+ *        without a bias  key_e = x_e  (both scorings are monotone in x: no exp decides an id);
+ *        with a bias (SM_MOE_SCORE_SIGMOID only)  q_e = 1 / (1 + expf(-x_e)), key_e = q_e + select_bias[e], one fp32 add;
+ *        a NaN key counts as -inf.
+ *      Selection: ids[j], j = 0 .. top_k - 1, are the experts in DESCENDING key order, equal keys in ASCENDING expert index.  Whatever
+ *      the logits hold, the top_k ids of a token are distinct and in [0, experts).
+ *      Weights, all in fp32:
+ *        SM_MOE_SCORE_SOFTMAX with renormalize (only top_k exponentials):  m = x_{ids[0]};  e_j = expf(x_{ids[j]} - m);
+ *          S = sum_j e_j in ascending j;  w_j = (e_j / S) * scale.
+ *        SM_MOE_SCORE_SOFTMAX without renormalize:  m = the maximum over all experts;  S = the sum of expf(x_e - m) over all experts
+ *          (its order is not fixed);  e_j and w_j as above.
+ *        SM_MOE_SCORE_SIGMOID:  q_j = 1 / (1 + expf(-x_{ids[j]}));  w_j = q_j * scale, or (q_j / sum_j q_j) * scale with renormalize,
+ *          the sum in ascending j.
+ *        inf and NaN propagate through this arithmetic as IEEE has it: only the ids carry a guarantee.
+ *      Forms (sm_moe_gate_form; the entry points switch on it): one wave per token, lane l holds experts l, l + 64, ...;
+ *      SM_MOE_GATE_FORM_LANE{1,2,4,8,16} is the number of keys a lane holds, the least of them >= ceil(experts / 64); _EMPTY
+ *      tokens == 0 or top_k == 0; _INVALID top_k > experts, experts > SM_LINEAR24_MAX_GROUPS, top_k > SM_MOE_GATE_MAX_TOP_K,
+ *      tokens * top_k or tokens >= 2^31.
+ *      Enqueue only: no allocation, no workspace, no synchronisation, no memset node; capturable into a hipGraph, and a captured graph
+ *      stays valid when the logits change.  Nothing outside the two outputs is written.
+ *      Status, decided before any device work, in this order: a null logits, topk_ids or topk_weights, ld < experts, top_k > experts,
+ *      scoring not one of the two, or a bias with SM_MOE_SCORE_SOFTMAX: SM_STATUS_INVALID_VALUE; tokens * top_k, tokens * ld or a
+ *      dimension >= 2^31, then experts > SM_LINEAR24_MAX_GROUPS, then top_k > SM_MOE_GATE_MAX_TOP_K: SM_STATUS_NOT_SUPPORTED (the text
+ *      names the limit); tokens == 0 or top_k == 0: success, nothing enqueued.
+ *      Not covered: group-limited selection, the router projection that produces the logits. */
+#define SM_MOE_SCORE_SOFTMAX 0
+#define SM_MOE_SCORE_SIGMOID 1
+#define SM_MOE_GATE_MAX_TOP_K 32
+#define SM_MOE_GATE_FORM_INVALID 0
+#define SM_MOE_GATE_FORM_EMPTY 1
+#define SM_MOE_GATE_FORM_LANE1 2
+#define SM_MOE_GATE_FORM_LANE2 3
+#define SM_MOE_GATE_FORM_LANE4 4
+#define SM_MOE_GATE_FORM_LANE8 5
+#define SM_MOE_GATE_FORM_LANE16 6
+int sm_moe_gate_f16(const void* logits, const float* select_bias, int* topk_ids, float* topk_weights, size_t tokens, size_t experts,
+                    size_t top_k, size_t ld, int scoring, int renormalize, float scale, sm_stream_t stream);
+int sm_moe_gate_bf16(const void* logits, const float* select_bias, int* topk_ids, float* topk_weights, size_t tokens, size_t experts,
+                     size_t top_k, size_t ld, int scoring, int renormalize, float scale, sm_stream_t stream);
+int sm_moe_gate_f32(const void* logits, const float* select_bias, int* topk_ids, float* topk_weights, size_t tokens, size_t experts,
+                    size_t top_k, size_t ld, int scoring, int renormalize, float scale, sm_stream_t stream);
+int sm_moe_gate_form(size_t tokens, size_t experts, size_t top_k, int* form);
+
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +
  * sm_spmma_f32 to fp32 accumulation order.  Needs k % 32 == 0, n % 4 == 0, 16-byte aligned rows. */

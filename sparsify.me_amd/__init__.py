@@ -193,6 +193,10 @@ _SIGS["sm_moe_route_form"] = [_c_size] * 3 + [ctypes.POINTER(_c_i)]
 for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_moe_combine_" + _sfx16] = [_c_ptr] * 5 + [_c_size] * 6 + [_c_ptr]
 _SIGS["sm_moe_combine_form"] = [_c_ptr] * 3 + [_c_size] * 3 + [ctypes.POINTER(_c_i)]
+# MoE gate (moe_gate.hip): logits -> top_k ids and weights
+for _sfx3 in ("f16", "bf16", "f32"):
+    _SIGS["sm_moe_gate_" + _sfx3] = [_c_ptr] * 4 + [_c_size] * 4 + [_c_i, _c_i, _c_f, _c_ptr]
+_SIGS["sm_moe_gate_form"] = [_c_size] * 3 + [ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -760,6 +764,36 @@ def moe_combine_form(Yp, residual, out, hidden, ldp, ldo):
     form = _c_i(-1)
     _check(lib().sm_moe_combine_form(ptr(Yp), ptr(residual), ptr(out), hidden, ldp, ldo, ctypes.byref(form)), "sm_moe_combine_form")
     return MOE_COMBINE_FORMS[form.value]
+
+
+# include/sparsifyme.h: SM_MOE_GATE_FORM_* (index = value), SM_MOE_SCORE_*, SM_MOE_GATE_MAX_TOP_K
+MOE_GATE_FORMS = ("invalid", "empty", "lane1", "lane2", "lane4", "lane8", "lane16")
+MOE_SCORE_SOFTMAX, MOE_SCORE_SIGMOID = 0, 1
+MOE_GATE_MAX_TOP_K = 32
+_MOE_SCORES = {"softmax": MOE_SCORE_SOFTMAX, "sigmoid": MOE_SCORE_SIGMOID}
+
+
+def moe_gate_form(tokens, experts, top_k):
+    """The name (MOE_GATE_FORMS) of the form moe_gate runs -- sm_moe_gate_form, the rule the entry points switch on.  Host only."""
+    form = _c_i(-1)
+    _check(lib().sm_moe_gate_form(tokens, experts, top_k, ctypes.byref(form)), "sm_moe_gate_form")
+    return MOE_GATE_FORMS[form.value]
+
+
+def moe_gate(logits, topk_ids, topk_weights, tokens, experts, top_k, scoring="softmax", renormalize=True, scale=1.0, select_bias=None, ld=None):
+    """The router's logits [tokens][experts] (row pitch ld; float16, bfloat16 or float32) to topk_ids (int32) and topk_weights (float32),
+    both [tokens * top_k] in pair order: descending key, equal keys in ascending expert index; softmax or sigmoid weights in fp32,
+    renormalised over the top_k or not, times scale (sm_moe_gate_*).  scoring: "softmax" / "sigmoid" or a MOE_SCORE_* value.
+    select_bias: float32 [experts] added to the sigmoid scores for the selection only, or None."""
+    torch = _t()
+    if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise SparsifymeError(f"moe_gate: logits are float16, bfloat16 or float32, not {logits.dtype}")
+    if topk_ids.dtype != torch.int32 or topk_weights.dtype != torch.float32 or (select_bias is not None and select_bias.dtype != torch.float32):
+        raise SparsifymeError("moe_gate: topk_ids is int32, topk_weights and select_bias float32")
+    ld = experts if ld is None else ld
+    fn = getattr(lib(), "sm_moe_gate_" + _sfx(logits))
+    _check(fn(_dev(logits), _dev(select_bias) if select_bias is not None else None, _dev(topk_ids), _dev(topk_weights), tokens, experts, top_k, ld,
+              _MOE_SCORES.get(scoring, scoring), 1 if renormalize else 0, float(scale), _stream()), "sm_moe_gate")
 
 
 def spmma_fused_i8(A, B, C, m, n, k, lda=None, batch=1, strideA=None, strideB=0, strideC=None, accumulate=False, scale=None):
