@@ -116,6 +116,10 @@ struct spmma_fns_f16 {
                          std::size_t ld, int scoring, int renorm, float scale, hipStream_t st) {
     return sm_moe_gate_f16(logits, bias, ids, w, tokens, experts, top_k, ld, scoring, renorm, scale, st);
   }
+  static int rmsnorm_on(const void* H, const void* D, const void* gamma, void* res, void* N, void* Q, float* row_scale, std::size_t tokens,
+                        std::size_t hidden, std::size_t ldh, std::size_t ldd, std::size_t ldn, std::size_t ldq, float eps, int fmt, hipStream_t st) {
+    return sm_rmsnorm_f16(H, D, gamma, res, N, Q, row_scale, tokens, hidden, ldh, ldd, ldn, ldq, eps, fmt, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -190,6 +194,10 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
   static int moe_gate_on(const void* logits, const float* bias, int* ids, float* w, std::size_t tokens, std::size_t experts, std::size_t top_k,
                          std::size_t ld, int scoring, int renorm, float scale, hipStream_t st) {
     return sm_moe_gate_bf16(logits, bias, ids, w, tokens, experts, top_k, ld, scoring, renorm, scale, st);
+  }
+  static int rmsnorm_on(const void* H, const void* D, const void* gamma, void* res, void* N, void* Q, float* row_scale, std::size_t tokens,
+                        std::size_t hidden, std::size_t ldh, std::size_t ldd, std::size_t ldn, std::size_t ldq, float eps, int fmt, hipStream_t st) {
+    return sm_rmsnorm_bf16(H, D, gamma, res, N, Q, row_scale, tokens, hidden, ldh, ldd, ldn, ldq, eps, fmt, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -662,6 +670,19 @@ int moe_gate(const type_t* d_logits, int* d_topk_ids, float* d_topk_weights, std
              hipStream_t stream = nullptr, std::size_t ld = 0) {
   return detail::spmma_fns<type_t>::moe_gate_on(d_logits, d_select_bias, d_topk_ids, d_topk_weights, tokens, experts, top_k, ld ? ld : experts, scoring,
                                                 renormalize ? 1 : 0, scale, stream);
+}
+
+// Extension (fp16 / bfloat16): residual add + RMSNorm in one launch (sm_rmsnorm_*): h = d_H + d_D rounded to type_t (d_D null: d_H unchanged),
+// written to d_res_out (null: not written; d_H itself: in place); n = h * (1 / sqrt(mean(h^2) + eps)) * d_gamma (null: 1), fp32 to the operation,
+// rounded once, written to d_N (null: not written); d_Q / d_row_scale (both or neither): n quantised per row to fmt (SM_FP8_E4M3 / _E5M2) by
+// the rule of sm_quantize_rows_fp8_*, what sm_linear24_fp8 reads as X / x_scale.  d_N or d_Q is given.  Row pitches in elements (ldq in bytes),
+// 0 = hidden; d_res_out has d_H's pitch.  hidden % 8 == 0, hidden <= SM_RMSNORM_MAX_HIDDEN, 16-byte aligned rows.  Enqueue only.
+template <typename type_t>
+int rmsnorm(const type_t* d_H, const type_t* d_D, const type_t* d_gamma, type_t* d_res_out, type_t* d_N, std::size_t tokens, std::size_t hidden,
+            float eps = 1e-6f, void* d_Q = nullptr, float* d_row_scale = nullptr, int fmt = SM_FP8_E4M3, hipStream_t stream = nullptr, std::size_t ldh = 0,
+            std::size_t ldd = 0, std::size_t ldn = 0, std::size_t ldq = 0) {
+  return detail::spmma_fns<type_t>::rmsnorm_on(d_H, d_D, d_gamma, d_res_out, d_N, d_Q, d_row_scale, tokens, hidden, ldh ? ldh : hidden, ldd ? ldd : hidden,
+                                               ldn ? ldn : hidden, ldq ? ldq : hidden, eps, fmt, stream);
 }
 
 // Extension (fp16 / bfloat16): the un-permute and weighted sum over top_k that close the block (sm_moe_combine_*):

@@ -724,6 +724,52 @@ int sm_moe_gate_f32(const void* logits, const float* select_bias, int* topk_ids,
                     size_t top_k, size_t ld, int scoring, int renormalize, float scale, sm_stream_t stream);
 int sm_moe_gate_form(size_t tokens, size_t experts, size_t top_k, int* form);
 
+/* ---- Residual add + RMSNorm (extension): the pre-norm in front of every layer, in one launch; fp16 / bf16, optional per-token fp8 output.
+ *      H[tokens][hidden] (row pitch ldh, in elements) is the residual stream; D (ldd) the branch output to add, or NULL; gamma[hidden] the
+ *      weight in the same 16-bit type, or NULL (= 1); res_out (pitch ldh) receives the updated stream, or NULL; N (ldn) the normalised
+ *      16-bit output, or NULL; Q (row pitch ldq in bytes) with row_scale[tokens] the fp8 output in fmt (SM_FP8_E4M3 / SM_FP8_E5M2), or
+ *      both NULL.  At least one of N and Q is given.
+ *      Definition, per row, all in fp32:
+ *        h_j = rne16(fp32(H_j) + fp32(D_j)): one fp32 add, one rounding to nearest even to the 16-bit type; without D, h_j = H_j
+ *          unchanged.  This is what res_out receives, and everything below reads these ROUNDED values: the fused call is the composition
+ *          of its parts.
+ *        S = sum_j fp32(h_j)^2.  The order is not fixed by the definition; it is fixed per `hidden` by the kernel (the same bits on
+ *          every run, whatever rows ride along).
+ *        ms = S / fp32(hidden), one correctly rounded fp32 division.
+ *        r = 1 / sqrtf(ms + eps): the add, the correctly rounded square root and the correctly rounded division are three separate
+ *          operations; no rsq approximation.
+ *        n_j = rne16((fp32(h_j) * r) * fp32(gamma_j)): two fp32 multiplies in this order, one rounding; without gamma one multiply.
+ *        Q, row_scale: exactly the rule of sm_quantize_rows_fp8_* (below) applied to the rounded n_j -- amax over the finite elements
+ *          with the 2^-100 floor, the two divisions, one multiply, rne to fmt, the non-finite bytes -- whether or not N is written.
+ *        NaN and inf go through this arithmetic as IEEE has it: an inf in a row gives r = 0, hence zeros and NaN at the inf; an all-zero
+ *          row with eps = 0 gives NaN.
+ *      Aliasing allowed: res_out == H (the usual in-place update); N == D; N == H when res_out is NULL or == H (at equal pitches).  A
+ *      lane reads every element it owns before it stores any.  Q and row_scale alias nothing.
+ *      Forms (sm_rmsnorm_form; the entry points switch on it; a function of `hidden` only, so a row's bits do not depend on how many
+ *      rows ride with it): SM_RMSNORM_FORM_LANES, hidden <= SM_RMSNORM_LANES_MAX_HIDDEN: 2^L lanes (8 .. 64) of one wave own a row, a wave
+ *      holds several rows when hidden is short; _BLOCK: one 256-thread workgroup per row, the reductions cross waves through LDS;
+ *      _EMPTY hidden == 0; _INVALID hidden > SM_RMSNORM_MAX_HIDDEN or hidden % 8 != 0.  Every row is read once and every output written
+ *      once.  Enqueue only: no allocation, no workspace, no atomics, no memset node, no synchronisation; capturable into a hipGraph.
+ *      Nothing outside the outputs is written.
+ *      Status, decided before any device work, in this order: a null H, N and Q both null, exactly one of Q / row_scale null, Q with a
+ *      fmt that is not SM_FP8_*, ldh, ldd (with D), ldn (with N) or ldq (with Q) below hidden, eps negative or NaN, or an aliasing not
+ *      listed above (N == H with a distinct res_out, res_out == D, res_out == N, aliased operands at different pitches):
+ *      SM_STATUS_INVALID_VALUE; then tokens, hidden or a pitch >= 2^31, then hidden > SM_RMSNORM_MAX_HIDDEN, then hidden % 8 != 0, then
+ *      a 16-bit operand whose rows are not 16-byte aligned (pointer, pitch % 8): SM_STATUS_NOT_SUPPORTED (the text names the limit);
+ *      tokens == 0 or hidden == 0: success, nothing enqueued.
+ *      Not covered: LayerNorm, a 1 + gamma weight, an fp32 gamma, fp32 activations, hidden > 16384, the 2:4 compress of the output. */
+#define SM_RMSNORM_MAX_HIDDEN 16384
+#define SM_RMSNORM_LANES_MAX_HIDDEN 512
+#define SM_RMSNORM_FORM_INVALID 0
+#define SM_RMSNORM_FORM_EMPTY 1
+#define SM_RMSNORM_FORM_LANES 2
+#define SM_RMSNORM_FORM_BLOCK 3
+int sm_rmsnorm_f16(const void* H, const void* D, const void* gamma, void* res_out, void* N, void* Q, float* row_scale, size_t tokens,
+                   size_t hidden, size_t ldh, size_t ldd, size_t ldn, size_t ldq, float eps, int fmt, sm_stream_t stream);
+int sm_rmsnorm_bf16(const void* H, const void* D, const void* gamma, void* res_out, void* N, void* Q, float* row_scale, size_t tokens,
+                    size_t hidden, size_t ldh, size_t ldd, size_t ldn, size_t ldq, float eps, int fmt, sm_stream_t stream);
+int sm_rmsnorm_form(size_t hidden, int* form);
+
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +
  * sm_spmma_f32 to fp32 accumulation order.  Needs k % 32 == 0, n % 4 == 0, 16-byte aligned rows. */

@@ -197,6 +197,10 @@ _SIGS["sm_moe_combine_form"] = [_c_ptr] * 3 + [_c_size] * 3 + [ctypes.POINTER(_c
 for _sfx3 in ("f16", "bf16", "f32"):
     _SIGS["sm_moe_gate_" + _sfx3] = [_c_ptr] * 4 + [_c_size] * 4 + [_c_i, _c_i, _c_f, _c_ptr]
 _SIGS["sm_moe_gate_form"] = [_c_size] * 3 + [ctypes.POINTER(_c_i)]
+# residual add + RMSNorm with an optional fp8 output (rmsnorm.hip)
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_rmsnorm_" + _sfx16] = [_c_ptr] * 7 + [_c_size] * 6 + [_c_f, _c_i, _c_ptr]
+_SIGS["sm_rmsnorm_form"] = [_c_size, ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -931,6 +935,62 @@ def quantize_rows_fp8(A, Q, row_scale, rows, k, lda=None, ldq=None):
     rs = _quant_row_scale(row_scale, "quantize_rows_fp8")
     fn = getattr(lib(), "sm_quantize_rows_fp8_" + sfx)
     _check(fn(_dev(A), rows, k, k if lda is None else lda, _dev(Q), k if ldq is None else ldq, rs, fmt, _stream()), "sm_quantize_rows_fp8")
+
+
+# include/sparsifyme.h: SM_RMSNORM_FORM_* (index = value), SM_RMSNORM_LANES_MAX_HIDDEN, SM_RMSNORM_MAX_HIDDEN
+RMSNORM_FORMS = ("invalid", "empty", "lanes", "block")
+RMSNORM_LANES_MAX_HIDDEN = 512
+RMSNORM_MAX_HIDDEN = 16384
+
+
+def rmsnorm_form(hidden):
+    """The name (RMSNORM_FORMS) of the form rmsnorm runs -- sm_rmsnorm_form, the rule the entry points switch on.  Host only."""
+    form = _c_i(-1)
+    _check(lib().sm_rmsnorm_form(hidden, ctypes.byref(form)), "sm_rmsnorm_form")
+    return RMSNORM_FORMS[form.value]
+
+
+def _rows2d(t, what, name):
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise SparsifymeError(f"{what}: {name} is [tokens][hidden] with contiguous rows (any row pitch)")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def rmsnorm(h, delta=None, gamma=None, eps=1e-6, out=None, res_out=None, fp8=None):
+    """Residual add + RMSNorm in one launch (sm_rmsnorm_*): s = h + delta rounded to h's dtype (float16 / bfloat16), written to res_out
+    (None: not written; h itself: the in-place update); n = s * (1 / sqrt(mean(s^2) + eps)) * gamma, fp32 to the operation, rounded once.
+    h, delta, res_out, out: [tokens][hidden] with contiguous rows, any row pitch; gamma: [hidden] in h's dtype, or None (= 1).
+    fp8: None -- returns n (in `out`, allocated when None); an fp8 dtype or a pair (Q, row_scale) -- also quantises n per row by the
+    rule of quantize_rows_fp8 and returns (out or None, Q, row_scale): n itself is written only when `out` is given."""
+    torch = _t()
+    sfx = _quant_src_sfx(h, "rmsnorm")
+    tokens, hidden = h.shape if h.dim() == 2 else (0, 0)
+    ldh = _rows2d(h, "rmsnorm", "h")
+    for name, t in (("delta", delta), ("out", out), ("res_out", res_out)):
+        if t is not None and (t.dtype != h.dtype or tuple(t.shape) != (tokens, hidden)):
+            raise SparsifymeError(f"rmsnorm: {name} has h's dtype and shape")
+    if gamma is not None and (gamma.dtype != h.dtype or tuple(gamma.shape) != (hidden,) or not gamma.is_contiguous()):
+        raise SparsifymeError("rmsnorm: gamma is a contiguous [hidden] tensor of h's dtype")
+    if res_out is not None and _rows2d(res_out, "rmsnorm", "res_out") != ldh:
+        raise SparsifymeError("rmsnorm: res_out has h's row pitch")
+    Q = rs = None
+    if fp8 is not None:
+        if isinstance(fp8, torch.dtype):
+            fp8_format(fp8)
+            Q = torch.empty((tokens, hidden), dtype=fp8, device=h.device)
+            rs = torch.empty(tokens, dtype=torch.float32, device=h.device)
+        else:
+            Q, rs = fp8
+        if tuple(Q.shape) != (tokens, hidden) or tuple(rs.shape) != (tokens,) or not rs.is_contiguous():
+            raise SparsifymeError("rmsnorm: Q is [tokens][hidden] fp8, row_scale a contiguous float32 [tokens]")
+    elif out is None:
+        out = torch.empty((tokens, hidden), dtype=h.dtype, device=h.device)
+    ptr = lambda t: _dev(t) if t is not None else None
+    fn = getattr(lib(), "sm_rmsnorm_" + sfx)
+    _check(fn(_dev(h), ptr(delta), ptr(gamma), ptr(res_out), ptr(out), ptr(Q), _quant_row_scale(rs, "rmsnorm") if rs is not None else None, tokens, hidden,
+              ldh, _rows2d(delta, "rmsnorm", "delta") if delta is not None else 0, _rows2d(out, "rmsnorm", "out") if out is not None else 0,
+              _rows2d(Q, "rmsnorm", "Q") if Q is not None else 0, float(eps), fp8_format(Q.dtype) if Q is not None else 0, _stream()), "sm_rmsnorm")
+    return out if fp8 is None else (out, Q, rs)
 
 
 def quantize_compress24_fp8(A, blob, row_scale, rows, k, fmt_dtype, lda=None):
