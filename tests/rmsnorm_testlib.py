@@ -6,41 +6,18 @@ test (operands at moved bases with pitches above `hidden`, NaN in the padding, g
 16-bit values travel as uint16 bit patterns; `ty` is "f16" or "bf16"."""
 import numpy as np
 
+from guard_testlib import NAN16, f32_of, is_nan16, rne16   # noqa: F401  (the two 16-bit types as bit patterns: one set for all files; re-exported)
+
 TYPES = ["f16", "bf16"]
 MANT = {"f16": 10, "bf16": 7}                 # explicit significand bits
 EMIN = {"f16": -14, "bf16": -126}             # exponent of the smallest normal
-NAN16 = {"f16": 0x7E00, "bf16": 0x7FC0}
-INF16 = {"f16": 0x7C00, "bf16": 0x7F80}
 FP8 = {"e4m3": 0, "e5m2": 1}                  # SM_FP8_*
 
 
 # ------------------------------------------------------------------------------------------------ the two 16-bit types
-def f32_of(bits, ty):
-    """uint16 bit patterns -> their exact float32 values"""
-    bits = np.asarray(bits, dtype=np.uint16)
-    if ty == "f16":
-        return bits.view(np.float16).astype(np.float32)
-    return (bits.astype(np.uint32) << 16).view(np.float32)
-
-
-def rne16(x, ty):
-    """float32 -> the 16-bit type, round to nearest even, as uint16 bit patterns (a NaN becomes a NaN)"""
-    x = np.asarray(x, dtype=np.float32)
-    if ty == "f16":
-        with np.errstate(over="ignore"):
-            return x.astype(np.float16).view(np.uint16)
-    b = x.view(np.uint32)
-    r = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16).astype(np.uint16)
-    return np.where(np.isnan(x), np.uint16(NAN16["bf16"]), r)
-
-
 def bits_of(x, ty):
     """any real array -> the 16-bit type's bit patterns (one rounding from float32)"""
     return rne16(np.asarray(x, dtype=np.float32), ty)
-
-
-def is_nan16(bits, ty):
-    return (np.asarray(bits) & 0x7FFF) > INF16[ty]
 
 
 def same_bits_nan_as_nan(a, b, ty):

@@ -11,7 +11,7 @@ arithmetic (column c * kh * kw + r * kw + u, zeros outside the image), the STRIP
 lower k), the product with B, alpha and beta in fp64.  Two data kinds per case: `ties` (X, B and the initial C integers in [-3, 3], (alpha, beta) in
 {(1, 0), (0.5, -2)}: every partial sum is a multiple of 0.5 of magnitude <= 4.5 K + 6 < 2^24 -- asserted -- so fp32 accumulation is exact in ANY
 order and ALL of C must equal the reference rounded ONCE to the output type, bit for bit, +0 and -0 equal) and `uniform` (U(-1, 1): check_close of
-test_gpu_parity at FP16_TOL and the rounding + accumulation bound of the output type, k = the K / 2 kept terms + 2).  Every taken case also
+parity_testlib at FP16_TOL and the rounding + accumulation bound of the output type, k = the K / 2 kept terms + 2).  Every taken case also
 asserts: the implicit kernel's C is bit-identical to sm_im2col_compress24 + sm_spmma for all N images; sm_im2col gives the reference's A and,
 followed by sm_compress24, the same blob; sm_conv_spmma_fused_plan names the class the case is listed under.  Every declined case asserts status 2
 with C untouched, and through the routed sm_conv_spmma_*: the reference with the reported workspace, status 2 without one.
@@ -43,10 +43,9 @@ import functools
 import numpy as np
 import pytest
 
-import test_gpu_parity as tp
-from test_gpu_parity import FP16_TOL, MARGINS, check_close
-from test_gpu_spmm32 import Workspace
-from test_gpu_strided8 import _seed
+from guard_testlib import (Guarded, Workspace, canon16 as canon, f64_of as bits_to_f64, is_nan16, margin_report_fixture, rne16 as f32_to_bits,
+                           round_once, seed)
+from parity_testlib import FP16_TOL, check_close, rand
 
 pytestmark = pytest.mark.gpu
 
@@ -62,42 +61,8 @@ DECLINED = "declined"
 FORM_NAMES = {"v16": "V16", "small4": "SMALL", "large4": "LARGE"}
 
 
-# ---------------------------------------------------------------------------------------------
-# the 16-bit types as bit patterns
-# ---------------------------------------------------------------------------------------------
-def f32_to_bits(x, t):
-    """float32 -> the type's bits, round to nearest even (no NaN among x)."""
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    if t == "f16":
-        with np.errstate(over="ignore"):
-            return x.astype(np.float16).view(np.uint16)
-    u = x.view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def bits_to_f64(b, t):
-    if t == "f16":
-        return b.view(np.float16).astype(np.float64)
-    return (b.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-
-
-def round_once(ref, t):
-    """The fp64 reference rounded ONCE to the output type, as bits.  bf16: through fp32, which must hold the value exactly."""
-    if t == "f16":
-        with np.errstate(over="ignore"):
-            return ref.astype(np.float16).view(np.uint16)
-    f = ref.astype(np.float32)
-    assert np.array_equal(f.astype(np.float64), ref)
-    return f32_to_bits(f, t)
-
-
-def canon(b):
-    """The bits with -0 turned into +0."""
-    return np.where(b == 0x8000, np.uint16(0), b)
-
-
-def is_nan16(b, t):
-    return (b & 0x7FFF) > (0x7C00 if t == "f16" else 0x7F80)
+def _seed(*xs):
+    return seed(0x5718, *xs)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -225,7 +190,7 @@ class Problem:
         OH, OW, L, K = dims(case.geom)
         self.N, self.L, self.K, self.n_out = N, L, K, n_out
         rng = np.random.default_rng(_seed("conv", case.name, kind, t if kind != "ties" else ""))
-        gen = lambda n: f32_to_bits(tp.rand(rng, n, np.float32, "ties" if kind == "ties" else "uniform"), t)
+        gen = lambda n: f32_to_bits(rand(rng, n, np.float32, "ties" if kind == "ties" else "uniform"), t)
         self.X, self.B, self.C0 = gen(N * Cin * H * W), gen(K * n_out), gen(N * L * n_out)
         if kind == "special":
             self._plant_special_values(rng)
@@ -301,64 +266,20 @@ def assert_ties_premise(p, ref, scale):
 # ---------------------------------------------------------------------------------------------
 # guarded buffers
 # ---------------------------------------------------------------------------------------------
-class Buf16:
+def Buf16(payload, guard, off=0):
     """An input (bits) between GUARD guard elements, `off` more of them in front."""
-
-    def __init__(self, payload, guard, off=0):
-        payload = np.ascontiguousarray(payload).view(np.uint16).reshape(-1)
-        self.base, self.size = GUARD + off, payload.size
-        self.host = np.full(self.base + payload.size + GUARD, guard, dtype=np.uint16)
-        self.host[self.base:self.base + payload.size] = payload
-
-    def to_device(self):
-        import torch
-        self.dev = torch.from_numpy(self.host.view(np.int16)).cuda()
-        assert self.dev.data_ptr() % 16 == 0   # so that the base alignment is the offset's
-        return self
-
-    @property
-    def ptr(self):
-        return self.dev.data_ptr() + 2 * self.base
-
-    def unchanged(self):
-        import torch
-        torch.cuda.synchronize()
-        return np.array_equal(self.dev.cpu().numpy().view(np.uint16), self.host)
+    return Guarded.around(payload, guard, GUARD + off, GUARD)
 
 
-class CBuf16:
+def CBuf16(payload):
     """C (bits) inside an allocation of sentinel words: GUARD in front, GUARD + 8 behind."""
+    return Guarded.around(payload, SENT16, GUARD, GUARD + 8)
 
-    def __init__(self, payload):
-        self.size = payload.size
-        self.host = np.full(GUARD + payload.size + GUARD + 8, SENT16, dtype=np.uint16)
-        self.host[GUARD:GUARD + payload.size] = payload
 
-    def to_device(self):
-        import torch
-        self.dev = torch.from_numpy(self.host.view(np.int16)).cuda()
-        assert self.dev.data_ptr() % 16 == 0
-        return self
-
-    @property
-    def ptr(self):
-        return self.dev.data_ptr() + 2 * GUARD
-
-    def result(self, what):
-        """C as bits, after asserting that every sentinel around it kept its bits."""
-        import torch
-        torch.cuda.synchronize()
-        got = self.dev.cpu().numpy().view(np.uint16)
-        out = np.ones(got.size, dtype=bool)
-        out[GUARD:GUARD + self.size] = False
-        changed = np.flatnonzero(out & (got != self.host))
-        assert changed.size == 0, f"{what}: {changed.size} elements outside C were written, first at {changed[:8] - GUARD} (C has {self.size})"
-        return got[GUARD:GUARD + self.size].copy()
-
-    def untouched(self):
-        import torch
-        torch.cuda.synchronize()
-        return np.array_equal(self.dev.cpu().numpy().view(np.uint16), self.host)
+def c_result(C, what):
+    """The logical C as bits, after asserting that every sentinel around it kept its bits."""
+    size = C.idx.stop - C.idx.start
+    return C.result(lambda n, first: f"{what}: {n} elements outside C were written, first at {first - GUARD} (C has {size})")
 
 
 def compare(got, p, ab, what, cls):
@@ -442,7 +363,7 @@ def run_taken(gpu, case, t, kind):
         C = CBuf16(c0).to_device()
         rc = call_fused(L, t, dX.ptr, dB.ptr, C.ptr, case.geom, ab)      # beta != 0: C in place
         assert rc == 0, f"{what}: status {rc}: {L.sm_last_error().decode()}"
-        got = C.result(what)
+        got = c_result(C, what)
         want = pair.product(c0, ab)
         diff = np.flatnonzero(got != want)
         assert diff.size == 0, (f"{what}: {diff.size} of {got.size} results differ from sm_im2col_compress24 + sm_spmma, first at "
@@ -461,8 +382,8 @@ def run_declined(gpu, case, t, kind):
     assert form == "not_taken", f"{what0}: the library reports {form} with {plan}"
     dX, dB = Buf16(p.X, QNAN16[t], off=case.x_off).to_device(), Buf16(p.B, QNAN16[t]).to_device()
     C = CBuf16(initial_c(p, ABS[0])).to_device()
-    assert call_fused(L, t, dX.ptr, dB.ptr, C.ptr, case.geom) == NOT_SUPPORTED and C.untouched(), f"{what0}: the implicit kernel must decline"
-    assert call_routed(L, t, dX.ptr, dB.ptr, C.ptr, case.geom) == NOT_SUPPORTED and C.untouched(), f"{what0}: without a workspace the routed entry must decline"
+    assert call_fused(L, t, dX.ptr, dB.ptr, C.ptr, case.geom) == NOT_SUPPORTED and C.unchanged(), f"{what0}: the implicit kernel must decline"
+    assert call_routed(L, t, dX.ptr, dB.ptr, C.ptr, case.geom) == NOT_SUPPORTED and C.unchanged(), f"{what0}: without a workspace the routed entry must decline"
     need = gpu.conv_spmma_workspace(*case.geom[:9])
     assert need == gpu.compress24_size(p.L, p.K, 2, p.N) > 0
     for ab in ABS:
@@ -471,7 +392,7 @@ def run_declined(gpu, case, t, kind):
         C = CBuf16(initial_c(p, ab)).to_device()
         rc = call_routed(L, t, dX.ptr, dB.ptr, C.ptr, case.geom, ab, ws.ptr, need)
         assert rc == 0, f"{what}: status {rc}: {L.sm_last_error().decode()}"
-        got = C.result(what)
+        got = c_result(C, what)
         ws.check(what)
         compare(got, p, ab, what, "routed")
     assert dX.unchanged() and dB.unchanged(), f"{what0}: an input or one of its guards was modified"
@@ -541,17 +462,5 @@ def test_conv_refusals(gpu, name):
 # ---------------------------------------------------------------------------------------------
 # margins of this file's `uniform` comparisons, appended to the session's report: the worst per class, then the worst cases
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", autouse=True)
-def _conv_margin_report():
-    start = len(MARGINS)
-    yield
-    mine = MARGINS[start:]
-    if not mine:
-        return
-    lines = [f"{len(mine)} comparisons of tests/test_gpu_conv.py against the numpy fp64 convolution; err / bound (check_close), worst per class:"]
-    for cls in sorted({w.split()[0] for w, _ in mine}):
-        w, r = max(((w, r) for w, r in mine if w.split()[0] == cls), key=lambda t: t[1])
-        lines.append(f"  {r:6.3f}  {w}")
-    lines.append("worst first:")
-    lines += [f"  {r:6.3f}  {w}" for w, r in sorted(mine, key=lambda t: -t[1])[:25]]
-    tp.write_margin_report(lines)
+_conv_margin_report = margin_report_fixture(
+    "{n} comparisons of tests/test_gpu_conv.py against the numpy fp64 convolution; err / bound (check_close), worst per class:", per_first_word=True)

@@ -10,56 +10,12 @@ import pytest
 # then runs on its own as well as in the whole suite
 import torch  # noqa: F401
 
+# (val64 here is torch's own conversion of the bytes: b8_testlib keeps it apart from the one through the fp16 image)
+from b8_testlib import EXACT_VALS, FMTS, OUTS, PAIRS, ROUND, TINY, bytes_of, dev8, finite_bytes, ksteps, odt, tdt, to8, val64_direct as val64
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMTS = ["e4m3", "e5m2"]
-PAIRS = [(a, b) for a in FMTS for b in FMTS]
-OUTS = ["f32", "f16", "bf16"]
-ROUND = {"f32": 2.0 ** -24, "f16": 2.0 ** -11, "bf16": 2.0 ** -8}
-TINY = {"f32": 2.0 ** -149, "f16": 2.0 ** -24, "bf16": 2.0 ** -133}
-# the fp32 accumulation term of the bound counts the products the instructions sum: k rounded up to whole 128-k steps (the
-# padding products are zeros, but a k = 64 product is one 128-k instruction, and its error is that of one: measured 1.15x
-# over a bound with k = 64 itself, for the sparse instruction as for the dense one)
-def ksteps(k):
-    return (k + 127) // 128 * 128
-
-
-EXACT_VALS = np.array([0.0, 0.5, -0.5, 1.0, -1.0, 2.0, -2.0, 3.0, -3.0, 4.0, -4.0], dtype=np.float32)
-
-
-def tdt(f):
-    import torch
-    return {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}[f]
-
-
-def odt(o):
-    import torch
-    return {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[o]
-
-
-def dev8(a, f):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).view(tdt(f)).cuda()
-
-
-def bytes_of(t):
-    import torch
-    return t.view(torch.uint8).cpu().numpy()
-
-
-def val64(a, f):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).view(tdt(f)).to(torch.float64).numpy()
-
-
-def to8(x, f):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(tdt(f)).view(torch.uint8).numpy().copy()
-
-
-def finite_bytes(rng, size, f, lo=-2.0, hi=2.0):
-    return to8(rng.uniform(lo, hi, size), f)
 
 
 def host(C):

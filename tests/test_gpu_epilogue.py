@@ -7,7 +7,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-# the project's bound for GEMM-type results (tests/test_gpu_parity.py): |got - ref| <= ROUND * |ref| + 2 k ACC * sum|ab| + TINY
+# the project's bound for GEMM-type results (tests/parity_testlib.py): |got - ref| <= ROUND * |ref| + 2 k ACC * sum|ab| + TINY
 ROUND = {"f16": 2.0 ** -10, "bf16": 2.0 ** -7}
 ACC = {"f16": 2.0 ** -24, "bf16": 2.0 ** -24}
 TINY = {"f16": 2.0 ** -24, "bf16": 2.0 ** -126}

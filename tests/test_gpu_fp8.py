@@ -9,72 +9,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from b8_testlib import FMTS, OUTS, PAIRS, ROUND, TINY, bytes_of, dev8, finite_bytes, img16, make_bytes, map_back, odt, tdt, val64
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMTS = ["e4m3", "e5m2"]
-PAIRS = [(a, b) for a in FMTS for b in FMTS]
-OUTS = ["f32", "f16", "bf16"]
-ROUND = {"f32": 2.0 ** -24, "f16": 2.0 ** -11, "bf16": 2.0 ** -8}
-TINY = {"f32": 2.0 ** -149, "f16": 2.0 ** -24, "bf16": 2.0 ** -133}
-# every byte with a name: +-0, the NaNs, e5m2 +-inf, the largest finite values, subnormals
-SPECIALS = {"e4m3": [0x00, 0x80, 0x7f, 0xff, 0x7e, 0xfe, 0x01, 0x81, 0x07, 0x08, 0x38, 0xb8],
-            "e5m2": [0x00, 0x80, 0x7c, 0xfc, 0x7d, 0x7e, 0x7f, 0xfd, 0xfe, 0xff, 0x7b, 0x01, 0x83, 0x04, 0x3c, 0xbc]}
-
-
-def tdt(f):
-    import torch
-    return {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}[f]
-
-
-def odt(o):
-    import torch
-    return {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[o]
-
-
-def dev8(a, f):
-    """uint8 numpy bytes -> fp8 device tensor of format f."""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).view(tdt(f)).cuda()
-
-
-def bytes_of(t):
-    import torch
-    return t.view(torch.uint8).cpu().numpy()
-
-
-def img16(a, f):
-    """the fp16 image's bit patterns (uint16) of fp8 bytes a."""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).view(tdt(f)).to(torch.float16).view(torch.int16).numpy().view(np.uint16)
-
-
-def val64(a, f):
-    return img16(a, f).view(np.float16).astype(np.float64)
-
-
-def map_back(pruned16, image16, a):
-    """bytes of a where the pruned image kept the element, 0x00 where it dropped it."""
-    return np.where(pruned16 == image16, a, 0).astype(np.uint8)
-
-
-def make_bytes(rng, size, f, kind):
-    if kind == "rand":
-        return rng.integers(0, 256, size).astype(np.uint8)
-    if kind == "ties":  # few distinct magnitudes, both signs, both zeros: ties decided by the lower k
-        return rng.choice(np.array([0x00, 0x80, 0x38, 0xb8, 0x40, 0xc0, 0x3c, 0xbc] if f == "e5m2" else [0x00, 0x80, 0x38, 0xb8, 0x40, 0xc0, 0x30, 0xb0],
-                                   dtype=np.uint8), size)
-    a = rng.integers(0, 256, size).astype(np.uint8)
-    sel = rng.random(size) < 0.5
-    a[sel] = rng.choice(np.array(SPECIALS[f], dtype=np.uint8), int(sel.sum()))
-    return a
-
-
-def finite_bytes(rng, size, f, lo=-2.0, hi=2.0):
-    """random finite fp8 values (uniform before rounding) as bytes"""
-    import torch
-    x = torch.from_numpy(rng.uniform(lo, hi, size).astype(np.float32)).to(tdt(f))
-    return x.view(torch.uint8).numpy().copy()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -55,11 +55,15 @@ import collections
 import numpy as np
 import pytest
 
-import test_gpu_parity as tp
-from test_gpu_parity import FP16_TOL, FP32_TOL, MARGINS, bits, check_close
-from test_gpu_strided8 import _seed
+from guard_testlib import margin_report_fixture, seed
+from parity_testlib import FP16_TOL, FP32_TOL, bits, check_close
 
 pytestmark = pytest.mark.gpu
+
+
+def _seed(*xs):
+    return seed(0x5718, *xs)
+
 
 assert np.finfo(np.longdouble).nmant >= 63, "the f64 reference needs a wider type than the kernel's"
 
@@ -756,17 +760,6 @@ def test_refusals_and_empty_extents_leave_c_alone(gpu, name):
 # ---------------------------------------------------------------------------------------------
 # margins of this file's `uniform` comparisons, appended to the session's report: the worst per entry point, then the worst cases
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", autouse=True)
-def _gemm_batched_margin_report():
-    start = len(MARGINS)
-    yield
-    mine = MARGINS[start:]
-    if not mine:
-        return
-    lines = [f"{len(mine)} comparisons of tests/test_gpu_gemm_batched.py against the numpy fp64 / longdouble product; err / bound (check_close), worst per entry point:"]
-    for entry in sorted({w.split()[0] for w, _ in mine}):
-        w, r = max(((w, r) for w, r in mine if w.split()[0] == entry), key=lambda t: t[1])
-        lines.append(f"  {r:6.3f}  {w}")
-    lines.append("worst first:")
-    lines += [f"  {r:6.3f}  {w}" for w, r in sorted(mine, key=lambda t: -t[1])[:25]]
-    tp.write_margin_report(lines)
+_gemm_batched_margin_report = margin_report_fixture(
+    "{n} comparisons of tests/test_gpu_gemm_batched.py against the numpy fp64 / longdouble product; err / bound (check_close), worst per entry point:",
+    per_first_word=True)

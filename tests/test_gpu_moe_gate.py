@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 from linear24_testlib import DEV
-from test_gpu_moe_route import route_ref
+from moe_route_testlib import route_ref
 
 import moe_gate_testlib as gl
 

@@ -8,27 +8,13 @@ import numpy as np
 import pytest
 import torch
 from linear24_testlib import DEV
+from moe_route_testlib import route_ref
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 8                  # int32 words before and behind every output
 SENT = -77777
 SINGLE_MAX, CHUNK = 4096, 4096
-
-
-def route_ref(ids, top_k, groups):
-    """include/sparsifyme.h, sm_moe_route, to the letter -- vectorised: a stable argsort with the dropped pairs behind every expert"""
-    ids = np.asarray(ids, dtype=np.int64)
-    Pn = len(ids)
-    kept = (ids >= 0) & (ids < groups)
-    V = int(kept.sum())
-    order = np.argsort(np.where(kept, ids, groups), kind="stable")[:V]
-    off = np.concatenate([[0], np.cumsum(np.bincount(ids[kept], minlength=groups))]).astype(np.int32)
-    st, sp, pp = (np.full(Pn, -1, dtype=np.int32) for _ in range(3))
-    sp[:V] = order
-    st[:V] = order // top_k
-    pp[order] = np.arange(V)
-    return off, st, sp, pp
 
 
 class Buffers:

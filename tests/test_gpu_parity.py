@@ -6,38 +6,10 @@ allows (check_close: one rounding of the output type + k fp32 accumulation steps
 import numpy as np
 import pytest
 
+from parity_testlib import (ACC, FP16_TOL, FP32_TOL, MARGINS, ROUND, SPLIT_TOL, TINY, _sk_ran, _sk_ws, bf16_bits, bf16_f64, bits, check_close, host, rand,
+                            split_bound, to_dev, torch_dtype, write_margin_report)
+
 pytestmark = pytest.mark.gpu
-
-FP16_TOL = 1e-2
-FP32_TOL = 1e-3
-
-
-def bits(a):
-    return a.view({2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def to_dev(a):
-    import torch
-    return torch.from_numpy(a).cuda()
-
-
-def torch_dtype(np_dtype):
-    import torch
-    return {np.float16: torch.float16, np.float32: torch.float32, np.float64: torch.float64}[np_dtype]
-
-
-def host(t):
-    import torch
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def rand(rng, n, dtype, kind="uniform"):
-    if kind == "ties":
-        return rng.integers(-3, 4, n).astype(dtype)
-    if kind == "u01":
-        return rng.uniform(0, 1, n).astype(dtype)
-    return rng.uniform(-1, 1, n).astype(dtype)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -347,51 +319,6 @@ def test_prune_compress_full_size_resnet50_layer(gpu, orc):
 # ---------------------------------------------------------------------------------------------
 # (a4) spmma and (a5) dense gemm
 # ---------------------------------------------------------------------------------------------
-# What the arithmetic allows, not just what north_star asks: the kernels accumulate in fp32 (k products, any order)
-# and round once to the output type, the oracle accumulates in fp64 and rounds once.  So
-#     |got - ref| <= ROUND[out] * |ref|  +  2 * k * ACC[out] * sum_k |a*b|
-# (one rounding of the result, half an ulp each side plus a possible double-rounding ulp; Higham's k*u bound on the
-# fp32 accumulation with a factor 2 for alpha/beta and fused-multiply-add differences).  A dropped k-slot changes a
-# result by ~|a*b| ~ scale/k, two orders of magnitude above this bound at k = 1024; the old 1e-2 * scale bound would
-# have let it pass.  The looser north_star tolerance (1e-2 / 1e-3 relative) is implied and still asserted.
-ROUND = {"f16": 2.0 ** -10, "bf16": 2.0 ** -7, "f32": 2.0 ** -22, "f64": 2.0 ** -51}
-ACC = {"f16": 2.0 ** -24, "bf16": 2.0 ** -24, "f32": 2.0 ** -24, "f64": 2.0 ** -53}
-TINY = {"f16": 2.0 ** -24, "bf16": 2.0 ** -126, "f32": 2.0 ** -126, "f64": 0.0}   # one subnormal step of the output type
-MARGINS = []   # (what, max err / bound) of every comparison made: written out by the session report below
-
-
-def check_close(got, ref, scale, tol, what, k, out="f16"):
-    got64, ref64 = got.astype(np.float64), ref.astype(np.float64)
-    err = np.abs(got64 - ref64)
-    scale = np.maximum(scale, 0.0)
-    bad = err > tol * np.maximum(scale, 1e-30)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} outside north_star tol {tol}; max err {err.max():.3e}"
-    bound = ROUND[out] * np.abs(ref64) + 2.0 * max(int(k), 1) * ACC[out] * scale + TINY[out]
-    ratio = float((err / bound).max()) if err.size else 0.0
-    MARGINS.append((what, ratio))
-    assert ratio <= 1.0, (f"{what}: max err / (rounding + accumulation bound) = {ratio:.3f} > 1 "
-                          f"(max err {err.max():.3e}, k = {k}, out = {out})")
-
-
-_REPORTS_WRITTEN = []
-
-
-def write_margin_report(lines):
-    """Print a margin report and keep it in the run's output directory: the first report of a session starts the file anew, a
-    later module's report follows it."""
-    import os
-    print("\n".join(lines))
-    mode = "a" if _REPORTS_WRITTEN else "w"
-    _REPORTS_WRITTEN.append(len(lines))
-    try:
-        d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-        os.makedirs(d, exist_ok=True)
-        with open(os.path.join(d, "parity_margins.txt"), mode) as fh:
-            fh.write("\n".join(lines) + "\n")
-    except OSError:
-        pass
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _parity_margin_report():
     yield
@@ -996,15 +923,6 @@ def test_spmma_fused_f32(gpu, orc, shape, ab):
         Pm = np.abs(host(P).astype(np.float64)).reshape(batch * m, k)
         scale = abs(alpha) * (Pm @ np.abs(B.astype(np.float64)).reshape(k, n)).reshape(-1) + abs(beta) * np.abs(C0.astype(np.float64))
         check_close(host(Cf), Cref, scale, FP32_TOL, f"spmma_fused_f32 {shape}", k, "f32")
-
-
-SPLIT_TOL = {3: 2.0 ** -21, 2: 2.0 ** -13}  # sm_spmma_fused_f32_split: |error| <= SPLIT_TOL * sum |a||b| on top of the fp32 accumulation bound
-
-
-def split_bound(planes, k, scale, ref):
-    """The bound of both split forms against the fp64 product: the dropped piece products (SPLIT_TOL) and 2 k fp32 accumulation steps, each
-    relative to scale = sum |a||b| (+ |beta||C0|), and one rounding of the result."""
-    return (SPLIT_TOL[planes] + 2.0 * k * 2.0 ** -24) * scale + 2.0 ** -22 * np.abs(ref) + 1e-30
 
 
 @pytest.mark.parametrize("shape", [(128, 64, 64, 1), (196, 128, 256, 2), (132, 72, 192, 3), (260, 256, 128, 2), (132, 200, 192, 3), (100, 512, 320, 1),
@@ -2288,17 +2206,6 @@ def test_fused_big_form_equals_staged(gpu, shape, bf):
         assert torch.equal(Cs[i].view(torch.int16), Cref.view(torch.int16)), f"grouped big form, problem {i}"
 
 
-def _sk_ws(gpu):
-    import torch
-    ws = gpu.spmma_fused_workspace()
-    ws[4096:].fill_(0xff)   # so that a written slot shows (the flags -- the first 4 KiB -- must be zero before a call)
-    return ws
-
-
-def _sk_ran(ws):
-    return bool((ws[4096:] != 0xff).any().item())
-
-
 @pytest.mark.parametrize("shape", [(196, 512, 2048, 4), (100, 264, 2304, 3), (300, 256, 2304, 2), (64, 136, 4608, 1), (600, 512, 3072, 5)], ids=lambda s_: "x".join(map(str, s_)))
 @pytest.mark.parametrize("bf", [False, True], ids=["f16", "bf16"])
 @pytest.mark.parametrize("ab", [(1.0, 0.0), (0.5, -2.0)])
@@ -2620,13 +2527,6 @@ def test_fused_grouped_rejects_bad_arguments(gpu):
 # ---------------------------------------------------------------------------------------------
 # (f-2) bfloat16 forms of the 2:4 path
 # ---------------------------------------------------------------------------------------------
-def bf16_bits(rng, n, kind="uniform"):
-    """n random bfloat16 values as uint16 bit patterns (torch's CPU conversion, round to nearest even)."""
-    import torch
-    x = rng.integers(-3, 4, n).astype(np.float32) if kind == "ties" else rng.uniform(-1, 1, n).astype(np.float32)
-    return torch.from_numpy(x).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16).copy()
-
-
 def bf16_dev(b):
     import torch
     return torch.from_numpy(b.view(np.int16)).cuda().view(torch.bfloat16)
@@ -2636,10 +2536,6 @@ def bf16_host(t):
     import torch
     torch.cuda.synchronize()
     return t.view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def bf16_f64(b):
-    return (b.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
 
 
 @pytest.mark.parametrize("shape", [(4, 4), (7, 10), (196, 512), (130, 147), (784, 64), (33, 8)])

@@ -25,6 +25,8 @@ from collections import namedtuple
 import numpy as np
 import pytest
 
+from guard_testlib import ByteRegion, Guarded, dev_bits as dev, seed
+
 pytestmark = pytest.mark.gpu
 
 TILE, STRIP = 0, 1
@@ -102,37 +104,20 @@ def orc_prune(orc, bits, m, k, alg, ty, batch=1):
 # ---------------------------------------------------------------------------------------------
 # padded, guarded buffers
 # ---------------------------------------------------------------------------------------------
-def torch_dtype(ty):
-    import torch
-    return {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}[ty]
-
-
-def dev(h, ty):
-    import torch
-    t = torch.from_numpy(h.view(np.int16 if ELT[ty] == 2 else np.int32).copy()).cuda().view(torch_dtype(ty))
-    assert t.data_ptr() % 16 == 0      # so that a base's alignment is its offset's
-    return t
-
-
-def host_bits(t, ty):
-    import torch
-    torch.cuda.synchronize()
-    return t.view(torch.int16 if ELT[ty] == 2 else torch.int32).cpu().numpy().view(NP[ty])
-
-
-class Pad:
+class Pad(Guarded):
     """`batch` logical m x k matrices inside a buffer: base = GUARD + off elements, ld = k + ld_pad, stride = m * ld + gap.  fill: "nan"
     (an input) or "sent" (an output).  The buffer ends GUARD elements behind the last logical one, so a read or a write of a whole last row
     of ld leaves it.  extra: more elements behind that (the one-pass operands: see Blob)."""
 
     def __init__(self, ty, m, k, ld_pad=0, batch=1, gap=0, off=0, fill="nan", data=None, extra=0):
         self.ty, self.m, self.k, self.batch = ty, m, k, batch
-        self.ld, self.base = k + ld_pad, GUARD + off
+        self.ld, base = k + ld_pad, GUARD + off
         self.stride = m * self.ld + gap
         self.fill = QNAN[ty] if fill == "nan" else SENT[ty]
-        n = self.base + (batch - 1) * self.stride + (m - 1) * self.ld + k + GUARD + extra
-        self.h = np.full(n, self.fill, dtype=NP[ty])
-        self.idx = (self.base + np.arange(batch)[:, None, None] * self.stride + np.arange(m)[None, :, None] * self.ld + np.arange(k)[None, None, :]).reshape(-1)
+        n = base + (batch - 1) * self.stride + (m - 1) * self.ld + k + GUARD + extra
+        idx = (base + np.arange(batch)[:, None, None] * self.stride + np.arange(m)[None, :, None] * self.ld + np.arange(k)[None, None, :]).reshape(-1)
+        Guarded.__init__(self, n, self.fill, NP[ty], base, idx)
+        self.h = self.host
         assert self.idx[-1] + 1 + GUARD + extra == n
         if data is not None:
             self.h[self.idx] = data
@@ -143,58 +128,46 @@ class Pad:
         return origin + self.base * ELT[self.ty]
 
     def to_dev(self):
-        self.d = dev(self.h, self.ty)
+        import torch
+        self.d = self.to_device().dev.view({"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}[self.ty])
         self.p = self.d[self.base:]
         return self
 
-    def host(self):
-        return host_bits(self.d, self.ty)
-
     def logical(self, arr=None):
-        return (self.host() if arr is None else arr)[self.idx]
+        return (self.read() if arr is None else arr)[self.idx]
 
     def matrix(self, b):
         """Device view of batch matrix b (the pointer a per-matrix call gets)."""
         return self.d[self.base + b * self.stride:]
 
     def assert_outside_kept(self, what):
-        got = self.host()
-        out = np.ones(got.size, dtype=bool)
-        out[self.idx] = False
-        bad = np.flatnonzero(out & (got != self.fill))
-        assert bad.size == 0, f"{what}: {bad.size} elements outside the logical operand changed, first at element {bad[:8] - self.base} from the base"
+        Guarded.assert_outside_kept(self, lambda n, first: f"{what}: {n} elements outside the logical operand changed, first at element "
+                                                           f"{first - self.base} from the base")
 
     def assert_unchanged(self, what):
-        assert np.array_equal(self.host(), self.h), f"{what}: the buffer changed"
+        assert self.unchanged(), f"{what}: the buffer changed"
 
 
-class Blob:
+class Blob(ByteRegion):
     """Exactly sm_compress24_size bytes at a 16-byte aligned address, sentinel bytes before and behind.  back: the guard behind it in blob
     sizes -- 8 where a wave of the one-pass kernel walks several (g, j) units of a row with nj > 1 (at most 7 row groups in ONEPASS_CASES):
     a mis-stepped counter then writes a stage plane that lies in the guard, where it is seen, not beyond it.  This guard and the `extra`
     2 k elements behind the one-pass operands (Pad) are what keeps the seeded mutation 5 of profiles/mutation_prune_classes.txt, and any
     real defect of that kind, inside the test's own allocations."""
+    OUTSIDE, WRITTEN = "bytes outside the blob's reported size were written", "the blob was written"
 
     def __init__(self, gpu, m, k, ty, batch, back=1):
-        import torch
         self.size = gpu.compress24_size(m, k, ELT[ty], batch)
         self.front = 256
         self.back = max(256, back * ((self.size + 255) // 256 * 256))
-        self.d = torch.full((self.front + self.size + self.back,), 0x5A, dtype=torch.uint8, device="cuda")
-        assert self.d.data_ptr() % 16 == 0
-        self.p = self.d[self.front:]
+        ByteRegion.__init__(self, self.size, self.front, self.back, 16)
+        self.d = self.dev
 
     def result(self, what):
-        import torch
-        torch.cuda.synchronize()
-        g = self.d.cpu().numpy()
-        assert (g[:self.front] == 0x5A).all() and (g[self.front + self.size:] == 0x5A).all(), f"{what}: bytes outside the blob's reported size were written"
-        return g[self.front:self.front + self.size]
+        return self.check(what)
 
     def assert_untouched(self, what):
-        import torch
-        torch.cuda.synchronize()
-        assert (self.d.cpu().numpy() == 0x5A).all(), f"{what}: the blob was written"
+        self.check(what, untouched=True)
 
 
 class Flag:
@@ -215,10 +188,7 @@ class Flag:
 
 
 def seed_of(*xs):
-    s = 0x2404
-    for x in xs:
-        s = s * 1000003 + (sum(map(ord, x)) if isinstance(x, str) else int(x))
-    return s % (1 << 32)
+    return seed(0x2404, *xs)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -931,7 +901,7 @@ def test_graph_replay_gives_the_eager_bytes(gpu, orc, ty):
     torch.cuda.synchronize()
     want = orc_prune(orc, data, m, k, TILE, ty, batch)
     for key in ("pr", "op", "de"):
-        assert np.array_equal(eager[key].host(), replay[key].host()), key
+        assert np.array_equal(eager[key].read(), replay[key].read()), key
         eager[key].assert_outside_kept(key)
         assert np.array_equal(eager[key].logical(), want), key
     for key in ("b1", "b2"):

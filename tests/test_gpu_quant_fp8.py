@@ -14,26 +14,19 @@ import os
 import numpy as np
 import pytest
 
+from b8_testlib import FMAX, FMTS, ROUND, TINY, bytes_of, cast8, img16, nonfinite_bytes, ref_quant_rows, tdt, val64
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMTS = ["e4m3", "e5m2"]
 SRCS = ["f16", "bf16"]
-FMAX = {"e4m3": 448.0, "e5m2": 57344.0}
 # |a - row_scale q| <= R |a| + S row_scale: half an ulp of the format's normals, half its smallest subnormal
 QR = {"e4m3": 2.0 ** -4, "e5m2": 2.0 ** -3}
 QS = {"e4m3": 2.0 ** -10, "e5m2": 2.0 ** -17}
-ROUND = {"f32": 2.0 ** -24, "f16": 2.0 ** -11, "bf16": 2.0 ** -8}
-TINY = {"f32": 2.0 ** -149, "f16": 2.0 ** -24, "bf16": 2.0 ** -133}
 # (rows, k, lda, ldq); k = 16448 = 32 x 512 + 64 lies beyond what a lane holds in registers (the re-reading form)
 SHAPES = [(2, 64, 64, 64), (6, 128, 128, 128), (7, 100, 104, 100), (130, 192, 192, 192), (196, 512, 512, 512), (1568, 2304, 2304, 2304),
           (64, 4608, 4608, 4608), (33, 576, 584, 592), (34, 16448, 16448, 16448)]
 KINDS = ["normal", "relu", "ties", "mixed"]
-
-
-def tdt(f):
-    import torch
-    return {"e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}[f]
 
 
 def sdt(s):
@@ -46,49 +39,9 @@ def bits16(t):
     return t.view(torch.int16).numpy().view(np.uint16)
 
 
-def bytes_of(t):
-    import torch
-    return t.view(torch.uint8).cpu().numpy()
-
-
 def f32_bits(t):
     import torch
     return t.view(torch.int32).cpu().numpy()
-
-
-def img16(a, f):
-    """the fp16 image's bit patterns (uint16) of fp8 bytes a."""
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).view(tdt(f)).to(torch.float16).view(torch.int16).numpy().view(np.uint16)
-
-
-def val64(a, f):
-    return img16(a, f).view(np.float16).astype(np.float64)
-
-
-def _nonfinite_bytes(x, q, f):
-    """the explicit select of the rule on the SOURCE values x (fp32, exact images of the 16-bit elements)."""
-    q = q.copy()
-    q[np.isnan(x)] = 0x7F
-    inf = np.isinf(x)
-    q[inf] = 0x7F if f == "e4m3" else np.where(np.signbit(x[inf]), 0xFC, 0x7C).astype(np.uint8)
-    return q
-
-
-def _cast8(y, f):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to(tdt(f)).view(torch.uint8).numpy()
-
-
-def ref_quant_rows(x, f):
-    """x: rows x k float32 (the exact values of the 16-bit A) -> (Q bytes rows x k, row_scale float32)."""
-    fm = np.float32(FMAX[f])
-    fin = np.isfinite(x)
-    amax = np.maximum(np.where(fin, np.abs(x), np.float32(0)).max(axis=1), np.float32(2.0 ** -100)).astype(np.float32)
-    scale = (amax / fm).astype(np.float32)
-    inv = (fm / amax).astype(np.float32)
-    y = (np.where(fin, x, np.float32(0)) * inv[:, None]).astype(np.float32)
-    return _nonfinite_bytes(x, _cast8(y, f), f), scale
 
 
 def ref_quant_transpose(x, inv_scale, f):
@@ -96,7 +49,7 @@ def ref_quant_transpose(x, inv_scale, f):
     fm = np.float32(FMAX[f])
     fin = np.isfinite(x)
     y = np.clip((np.where(fin, x, np.float32(0)) * np.float32(inv_scale)).astype(np.float32), -fm, fm)
-    return np.ascontiguousarray(_nonfinite_bytes(x, _cast8(y, f), f).T)
+    return np.ascontiguousarray(nonfinite_bytes(x, cast8(y, f), f).T)
 
 
 def strip_keep(q):

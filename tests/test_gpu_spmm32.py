@@ -11,7 +11,7 @@ The references are NOT the library: numpy fp64 from the definition (Blocked-ELL:
 np.add.at into a dense A, duplicates adding, coordinates out of range skipped), alpha and beta applied in fp64.  Two data kinds per case: `ties`
 (integers in [-3, 3], (alpha, beta) in {(1, 0), (0.5, -2)}: every partial sum is a multiple of 0.5 below 2^24 -- asserted -- so the fp32 result is
 exact in ANY summation order, atomics included, and ALL of C must equal the reference; +0 and -0 compare equal: beta * (+0) is -0 where C is scaled
-first and +0 where the scaling is fused into the store) and `uniform` (U(-1, 1): check_close of test_gpu_parity at FP32_TOL and the rounding +
+first and +0 where the scaling is fused into the store) and `uniform` (U(-1, 1): check_close of parity_testlib at FP32_TOL and the rounding +
 accumulation bound, k = the longest row's term count + 2).
 
 Launch classes and the cases that pin them (tests/test_spmm32_cases.py restates every rule and holds every case against it):
@@ -46,9 +46,8 @@ import ctypes
 import numpy as np
 import pytest
 
-import test_gpu_parity as tp
-from test_gpu_parity import FP32_TOL, MARGINS, bits, check_close, rand
-from test_gpu_strided8 import _seed
+from guard_testlib import Guarded, Workspace, canon32 as canon, margin_report_fixture, seed
+from parity_testlib import FP32_TOL, bits, check_close, rand
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +55,6 @@ QNAN = np.uint32(0x7FC00000)
 SENT = np.uint32(0x5A5A5A5A)
 ALL1 = np.uint64(0xFFFFFFFFFFFFFFFF)
 GUARD = 64                     # words in front of and behind every buffer (a multiple of 16 bytes: the base alignment is the offset's)
-WS_GUARD = 256                 # bytes behind (and, with an offset base, in front of) a workspace
 INVALID, NOT_SUPPORTED = 1, 2
 KINDS = ("ties", "uniform")
 ABS = ((1.0, 0.0), (0.5, -2.0))
@@ -66,34 +64,16 @@ BATCH = 3
 # ---------------------------------------------------------------------------------------------
 # guarded buffers
 # ---------------------------------------------------------------------------------------------
-class Buf:
+def _seed(*xs):
+    return seed(0x5718, *xs)
+
+
+def Buf(payload, guard, off=0):
     """An input (4- or 8-byte elements, kept as bits) between GUARD guard words, `off` more of them in front."""
-
-    def __init__(self, payload, guard, off=0):
-        payload = np.ascontiguousarray(payload)
-        u = {4: np.uint32, 8: np.uint64}[payload.dtype.itemsize]
-        payload = payload.view(u).reshape(-1)
-        self.base, self.size = GUARD + off, payload.size
-        self.host = np.full(self.base + payload.size + GUARD, guard, dtype=u)
-        self.host[self.base:self.base + payload.size] = payload
-
-    def to_device(self):
-        import torch
-        self.dev = torch.from_numpy(self.host.view({4: np.int32, 8: np.int64}[self.host.itemsize])).cuda()
-        assert self.dev.data_ptr() % 16 == 0   # so that the base alignment is the offset's
-        return self
-
-    @property
-    def ptr(self):
-        return self.dev.data_ptr() + self.host.itemsize * self.base
-
-    def unchanged(self):
-        import torch
-        torch.cuda.synchronize()
-        return np.array_equal(self.dev.cpu().numpy().view(self.host.dtype), self.host)
+    return Guarded.around(payload, guard, GUARD + off, GUARD)
 
 
-class CBuf:
+class CBuf(Guarded):
     """One allocation of sentinel words that holds the logical Cs (bit patterns): C_b for b in `order`, one after the other, GUARD words in front
     of the first and GUARD + 4 * (i + 1) behind the i-th -- unequal gaps; `off` shifts every base."""
 
@@ -105,57 +85,17 @@ class CBuf:
         for i, b in enumerate(order):
             self.start[b] = pos
             pos += payloads[b].size + GUARD + 4 * (i + 1)
-        self.host = np.full(pos, SENT, dtype=np.uint32)
-        self.outside = np.ones(pos, dtype=bool)
+        Guarded.__init__(self, pos, SENT, np.uint32, GUARD + off, np.concatenate([np.arange(s, s + n) for s, n in zip(self.start, self.sizes)]))
         for b, p in enumerate(payloads):
             self.host[self.start[b]:self.start[b] + p.size] = p
-            self.outside[self.start[b]:self.start[b] + p.size] = False
-
-    def to_device(self):
-        import torch
-        self.dev = torch.from_numpy(self.host.view(np.int32)).cuda()
-        assert self.dev.data_ptr() % 16 == 0
-        return self
 
     def ptr(self, b=0):
         return self.dev.data_ptr() + 4 * self.start[b]
 
     def results(self, what):
         """The logical Cs as bits, after asserting that every sentinel around them kept its bits."""
-        import torch
-        torch.cuda.synchronize()
-        got = self.dev.cpu().numpy().view(np.uint32)
-        changed = np.flatnonzero(self.outside & (got != self.host))
-        assert changed.size == 0, f"{what}: {changed.size} words outside C were written, first at {changed[:8]} (the Cs start at {self.start})"
+        got = self.assert_outside_kept(lambda n, first: f"{what}: {n} words outside C were written, first at {first} (the Cs start at {self.start})")
         return [got[s:s + n] for s, n in zip(self.start, self.sizes)]
-
-
-class Workspace:
-    """`nbytes` bytes of 0x5A at `off` bytes from a 256-byte aligned base, WS_GUARD more behind them."""
-
-    def __init__(self, nbytes, off=0):
-        import torch
-        self.nbytes, self.off = nbytes, off
-        self.dev = torch.full((off + nbytes + WS_GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
-        assert self.dev.data_ptr() % 256 == 0
-
-    @property
-    def ptr(self):
-        return self.dev.data_ptr() + self.off
-
-    def _host(self):
-        import torch
-        torch.cuda.synchronize()
-        return self.dev.cpu().numpy()
-
-    def flag(self):
-        return int(self._host()[self.off:self.off + 4].view(np.int32)[0])
-
-    def check(self, what, untouched=False):
-        h = self._host()
-        assert (h[:self.off] == 0x5A).all() and (h[self.off + self.nbytes:] == 0x5A).all(), f"{what}: bytes outside the reported workspace size were written"
-        if untouched:
-            assert (h == 0x5A).all(), f"{what}: the workspace was written"
 
 
 def compare(got_bits, ref, scale, kind, k, what, shape):
@@ -169,11 +109,6 @@ def compare(got_bits, ref, scale, kind, k, what, shape):
                                  f"{g[wrong[:4]]} for {ref[wrong[:4]]}")
     else:
         check_close(g, ref, scale, FP32_TOL, what, k, "f32")
-
-
-def canon(got_bits):
-    """The bits with -0 turned into +0 (see the docstring)."""
-    return bits(got_bits.view(np.float32) + np.float32(0.0))
 
 
 def assert_ties_premise(ref, scale):
@@ -762,17 +697,5 @@ def test_refusals_leave_c_alone(gpu, name):
 # ---------------------------------------------------------------------------------------------
 # margins of this file's `uniform` comparisons, appended to the session's report: the worst per entry point, then the worst cases
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", autouse=True)
-def _spmm32_margin_report():
-    start = len(MARGINS)
-    yield
-    mine = MARGINS[start:]
-    if not mine:
-        return
-    lines = [f"{len(mine)} comparisons of tests/test_gpu_spmm32.py against the numpy fp64 product; err / bound (check_close), worst per entry point:"]
-    for entry in sorted({w.split()[0] for w, _ in mine}):
-        w, r = max(((w, r) for w, r in mine if w.split()[0] == entry), key=lambda t: t[1])
-        lines.append(f"  {r:6.3f}  {w}")
-    lines.append("worst first:")
-    lines += [f"  {r:6.3f}  {w}" for w, r in sorted(mine, key=lambda t: -t[1])[:25]]
-    tp.write_margin_report(lines)
+_spmm32_margin_report = margin_report_fixture(
+    "{n} comparisons of tests/test_gpu_spmm32.py against the numpy fp64 product; err / bound (check_close), worst per entry point:", per_first_word=True)

@@ -4,7 +4,7 @@ Every case places the logical operands in larger buffers (a base offset, lda > k
 the logical operand is NaN, all of C outside the logical result a sentinel bit pattern.  A kernel that reads padding into a product
 shows a NaN; one that writes outside its tile changes a sentinel; a wrong row base shows in the integer-exact variant.  The
 reference is NOT the library: the gathered logical A, pruned by the oracle's STRIP rule on the compact copy, times B in numpy fp64,
-under exactly test_gpu_parity.check_close's bound (imported, not restated).  Every exact fused form is also held, bit for bit,
+under exactly parity_testlib.check_close's bound (imported, not restated).  Every exact fused form is also held, bit for bit,
 against compress + sm_spmma_* on a compact copy -- the library's stated contract.
 
 Each fused case FIRST asserts, through sm_spmma_fused_form with cus = 0, that this device sends the call to the form the case is
@@ -13,8 +13,9 @@ kernel fails, it never skips."""
 import numpy as np
 import pytest
 
-import test_gpu_parity as tp
-from test_gpu_parity import FP16_TOL, MARGINS, check_close   # the one bound: ROUND*|ref| + 2k*ACC*sum|ab| + TINY, and the 1e-2 north star
+import parity_testlib as pl
+from guard_testlib import Guarded, Layout, Strided, dev_bits, f64_of as _f64_of, host_bits, margin_report_fixture, round_bits as _round_bits, seed
+from parity_testlib import FP16_TOL, check_close   # the one bound: ROUND*|ref| + 2k*ACC*sum|ab| + TINY, and the 1e-2 north star
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +30,12 @@ DT_IDS = ["f16", "bf16"]
 # ---------------------------------------------------------------------------------------------
 def rand_bits(rng, n, bf, kind="uniform"):
     if bf:
-        return tp.bf16_bits(rng, n, kind)
-    return tp.bits(tp.rand(rng, n, np.float16, kind)).copy()
+        return pl.bf16_bits(rng, n, kind)
+    return pl.bits(pl.rand(rng, n, np.float16, kind)).copy()
 
 
 def f64_of(b, bf):
-    return tp.bf16_f64(b) if bf else b.view(np.float16).astype(np.float64)
+    return _f64_of(b, DT_IDS[bf])
 
 
 def bits_of_f64(x, bf):
@@ -46,58 +47,29 @@ def bits_of_f64(x, bf):
 
 
 def round_bits(x, bf):
-    """fp64 values (exact in fp32) rounded once, to nearest even, to the 16-bit type."""
-    import torch
-    if bf:
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16).copy()
-    return np.ascontiguousarray(x).astype(np.float16).view(np.uint16)
+    return _round_bits(x, DT_IDS[bf])
 
 
 def dev(b, bf):
-    import torch
-    t = torch.from_numpy(b.view(np.int16)).cuda()
-    return t.view(torch.bfloat16 if bf else torch.float16)
-
-
-def host_bits(t):
-    import torch
-    torch.cuda.synchronize()
-    return t.view(torch.int16).cpu().numpy().view(np.uint16)
+    return dev_bits(b, DT_IDS[bf])
 
 
 # ---------------------------------------------------------------------------------------------
 # the layout builder
 # ---------------------------------------------------------------------------------------------
-class Layout:
-    """Where the logical operands lie: element offsets of the bases, lda = k + lda_pad, strideX = its contiguous value + gapX
-    (gapB None: one shared B, strideB = 0)."""
+class Problem(Strided):
+    """Padded host buffers (bit patterns), index maps of the logical operands, the fp64 reference and -- after to_device(), which the
+    constructor calls unless told upload=False -- the device copies."""
 
-    def __init__(self, lda_pad=0, gapA=0, gapB=None, gapC=0, offA=0, offB=0, offC=0, batch=2, alpha=1.0, beta=0.0):
-        self.lda_pad, self.gapA, self.gapB, self.gapC = lda_pad, gapA, gapB, gapC
-        self.offA, self.offB, self.offC, self.batch, self.alpha, self.beta = offA, offB, offC, batch, alpha, beta
-
-
-class Problem:
-    """Padded host buffers (bit patterns), their device copies, index maps of the logical operands and the fp64 reference."""
-
-    def __init__(self, rng, m, n, k, lay, bf, kind="uniform", int_b=False, dense=False, slack_rows=256):
-        self.m, self.n, self.k, self.bf, self.lay = m, n, k, bf, lay
-        self.batch = batch = lay.batch
-        self.lda = lda = k + lay.lda_pad
-        self.sA = m * lda + lay.gapA
-        self.sB = 0 if lay.gapB is None else k * n + lay.gapB
-        self.sC = m * n + lay.gapC
-        nb = 1 if lay.gapB is None else batch
+    def __init__(self, rng, m, n, k, lay, bf, kind="uniform", int_b=False, dense=False, slack_rows=256, upload=True):
+        Strided.__init__(self, m, n, k, lay, lay.offA, lay.offB, lay.offC)
+        self.bf = bf
+        batch, nb, lda = self.batch, self.nb, self.lda
         # whole-tile reads past a ragged m (and 16-byte pieces past a row's end) stay inside the allocations
-        nA = lay.offA + batch * self.sA + slack_rows * lda + 64
-        nB = lay.offB + nb * (k * n + (lay.gapB or 0)) + 64 * n + 64
-        nC = lay.offC + batch * self.sC + 64
-        self.A = np.full(nA, NAN_BITS[bf], dtype=np.uint16)
-        self.B = np.full(nB, NAN_BITS[bf], dtype=np.uint16)
-        self.C = np.full(nC, SENTINEL, dtype=np.uint16)
-        self.iA = (lay.offA + np.arange(batch)[:, None, None] * self.sA + np.arange(m)[None, :, None] * lda + np.arange(k)[None, None, :]).reshape(-1)
-        self.iB = (lay.offB + np.arange(nb)[:, None] * self.sB + np.arange(k * n)[None, :]).reshape(-1)
-        self.iC = (lay.offC + np.arange(batch)[:, None] * self.sC + np.arange(m * n)[None, :]).reshape(-1)
+        self.gA = Guarded(lay.offA + batch * self.sA + slack_rows * lda + 64, NAN_BITS[bf], np.uint16, lay.offA, self.iA)
+        self.gB = Guarded(lay.offB + nb * self.sBe + 64 * n + 64, NAN_BITS[bf], np.uint16, lay.offB, self.iB)
+        self.gC = Guarded(lay.offC + batch * self.sC + 64, SENTINEL, np.uint16, lay.offC, self.iC)
+        self.A, self.B, self.C = self.gA.host, self.gB.host, self.gC.host
         self.A[self.iA] = rand_bits(rng, batch * m * k, bf, kind)
         if int_b:   # asymmetric small integers, as test_mfma_lane_maps_with_identity_and_asymmetric_b's B
             Bi = ((np.arange(k)[:, None] * 3 + np.arange(n)[None, :] * 7) % 13 - 6).astype(np.float64)
@@ -107,11 +79,15 @@ class Problem:
         self.C0 = rand_bits(rng, batch * m * n, bf) if lay.beta != 0.0 else np.full(batch * m * n, SENTINEL, dtype=np.uint16)
         self.C[self.iC] = self.C0
         self.dense = dense
-        self.dA, self.dB, self.dC = dev(self.A, bf), dev(self.B, bf), dev(self.C, bf)
+        if upload:
+            self.to_device()
+
+    def to_device(self):
+        import torch
+        lay, ty = self.lay, torch.bfloat16 if self.bf else torch.float16
+        self.dA, self.dB, self.dC = (g.to_device().dev.view(ty) for g in (self.gA, self.gB, self.gC))
         self.pA, self.pB, self.pC = self.dA[lay.offA:], self.dB[lay.offB:], self.dC[lay.offC:]
-        for t, off in ((self.dA, lay.offA), (self.dB, lay.offB), (self.dC, lay.offC)):
-            assert t.data_ptr() % 16 == 0   # so that the base alignment is the offset's
-        self.nb = nb
+        return self
 
     def a_compact(self):
         return self.A[self.iA].copy()
@@ -133,12 +109,7 @@ class Problem:
 
     def result(self):
         """The logical C as bits, after asserting that every sentinel outside it kept its bits."""
-        got = host_bits(self.dC)
-        outside = np.ones(got.size, dtype=bool)
-        outside[self.iC] = False
-        changed = np.flatnonzero(outside & (got != SENTINEL))
-        assert changed.size == 0, f"{changed.size} elements of C outside the logical result were written, first at {changed[:8]}"
-        return got[self.iC]
+        return self.gC.result(lambda n, first: f"{n} elements of C outside the logical result were written, first at {first}")
 
     def check(self, orc, what, exact=False):
         got = self.result()
@@ -222,10 +193,7 @@ def _case_id(c):
 
 
 def _seed(*xs):
-    s = 0x5716
-    for x in xs:
-        s = s * 1000003 + (sum(map(ord, x)) if isinstance(x, str) else int(x))
-    return s % (1 << 32)
+    return seed(0x5716, *xs)
 
 
 @pytest.mark.parametrize("bf", DT, ids=DT_IDS)
@@ -332,10 +300,10 @@ def test_fused_streamk_integer_exact(gpu, orc, bf):
     m, n, k, batch = STREAMK_SHAPE
     p = Problem(np.random.default_rng(_seed("sk", "int", bf)), m, n, k, Layout(lda_pad=8, gapA=64, gapB=8, gapC=8, batch=batch), bf, kind="ties", int_b=True)
     assert p.form(gpu, workspace=True) == "streamk"
-    ws = tp._sk_ws(gpu)
+    ws = pl._sk_ws(gpu)
     p.run_fused(gpu, workspace=ws)
     torch.cuda.synchronize()
-    assert tp._sk_ran(ws), "the stream-K kernel did not run"
+    assert pl._sk_ran(ws), "the stream-K kernel did not run"
     assert gpu.spmma_fused_workspace_state(ws) == 0
     p.check(orc, f"strided stream-K integer {DT_IDS[bf]}", exact=True)
 
@@ -349,10 +317,10 @@ def test_fused_streamk_on_padded_operands(gpu, orc, bf, ab):
     m, n, k, batch = STREAMK_SHAPE
     p = Problem(np.random.default_rng(_seed("sk", bf, ab[1] != 0)), m, n, k, Layout(lda_pad=8, gapA=64, gapC=8, batch=batch, alpha=ab[0], beta=ab[1]), bf)
     assert p.form(gpu, workspace=True) == "streamk"
-    ws = tp._sk_ws(gpu)
+    ws = pl._sk_ws(gpu)
     p.run_fused(gpu, workspace=ws)
     torch.cuda.synchronize()
-    assert tp._sk_ran(ws), "the stream-K kernel did not run"
+    assert pl._sk_ran(ws), "the stream-K kernel did not run"
     assert gpu.spmma_fused_workspace_state(ws) == 0
     p.check(orc, f"strided stream-K {ab} {DT_IDS[bf]}")
 
@@ -515,13 +483,5 @@ def test_gemm_rowmajor_integer_exact_on_padded_operands(gpu, orc):
 # ---------------------------------------------------------------------------------------------
 # margins of this file's comparisons, appended to the session's report
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", autouse=True)
-def _strided_margin_report():
-    start = len(MARGINS)
-    yield
-    mine = MARGINS[start:]
-    if not mine:
-        return
-    lines = [f"{len(mine)} comparisons of tests/test_gpu_strided16.py against the fp64 product; err / (ROUND*|ref| + 2k*ACC*sum|ab| + TINY), worst first:"]
-    lines += [f"  {r:6.3f}  {w}" for w, r in sorted(mine, key=lambda t: -t[1])]
-    tp.write_margin_report(lines)
+_strided_margin_report = margin_report_fixture(
+    "{n} comparisons of tests/test_gpu_strided16.py against the fp64 product; err / (ROUND*|ref| + 2k*ACC*sum|ab| + TINY), worst first:")

@@ -7,7 +7,7 @@ references are NOT the library: the gathered logical A (for the 2:4 entry points
 times the gathered B in numpy fp64, alpha and beta applied in fp64.  Two data kinds per case: `ties` (integers in [-3, 3], k <= 256,
 (alpha, beta) in {(1, 0), (0.5, -2)}: every product, partial sum, bf16 piece and scale is exact, so C must equal the fp64 result
 converted to fp32 bit for bit -- the premise is asserted per case) and `uniform` (U(-1, 1): check_close at FP32_TOL, the fmaf-chain
-kernels also at 1e-5, the split forms under test_gpu_parity.split_bound).  Stated contracts (include/sparsifyme.h), bit for bit with the
+kernels also at 1e-5, the split forms under parity_testlib.split_bound).  Stated contracts (include/sparsifyme.h), bit for bit with the
 right-hand side on compact copies: sm_spmma_fused_f32 == sm_gemm_rowmajor_f32 of the oracle-pruned A; sm_spmma_fused_f32_split_prepared
 == sm_spmma_fused_f32_split (B overwritten with NaN between prepare and the product).
 
@@ -38,9 +38,8 @@ import ctypes
 import numpy as np
 import pytest
 
-import test_gpu_parity as tp
-from test_gpu_parity import FP32_TOL, MARGINS, bits, check_close, rand
-from test_gpu_strided8 import _seed
+from guard_testlib import Guarded, Layout, Strided, margin_report_fixture, seed
+from parity_testlib import FP32_TOL, MARGINS, bits, check_close, rand, split_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -55,13 +54,8 @@ AB = (0.5, -2.0)
 # ---------------------------------------------------------------------------------------------
 # the layout builder
 # ---------------------------------------------------------------------------------------------
-class Layout:
-    """Where the logical operands lie, in float elements: offsets of the bases, lda = k + lda_pad, strideX = its contiguous value + gapX
-    (gapB None: one shared B, strideB = 0)."""
-
-    def __init__(self, lda_pad=0, gapA=0, gapB=None, gapC=0, offA=0, offB=0, offC=0, batch=2, alpha=1.0, beta=0.0):
-        self.lda_pad, self.gapA, self.gapB, self.gapC = lda_pad, gapA, gapB, gapC
-        self.offA, self.offB, self.offC, self.batch, self.alpha, self.beta = offA, offB, offC, batch, alpha, beta
+def _seed(*xs):
+    return seed(0x5718, *xs)
 
 
 LAYOUTS = {
@@ -100,26 +94,18 @@ def draw(rng, kind, batch, nb, m, n, k):
             rand(rng, batch * m * n, np.float32, kind).reshape(batch, m, n))
 
 
-class Problem:
+class Problem(Strided):
     """Padded host buffers (uint32 bit patterns), index maps of the logical operands, the references and -- after to_device() -- the
     device copies.  kind: "ties" or "uniform"; data: (A [batch][m][k], B [nb][k][n], C0 [batch][m][n]) instead of a draw from rng."""
 
     def __init__(self, m, n, k, lay, kind, rng=None, data=None):
-        self.m, self.n, self.k, self.lay, self.kind = m, n, k, lay, kind
-        self.batch = batch = lay.batch
-        self.lda = lda = k + lay.lda_pad
-        self.sA = m * lda + lay.gapA
-        self.nb = nb = 1 if lay.gapB is None else batch
-        sBe = k * n + (lay.gapB or 0)
-        self.sB = 0 if lay.gapB is None else sBe
-        self.sC = m * n + lay.gapC
-        self.baseA, self.baseB, self.baseC = GUARD + lay.offA, GUARD + lay.offB, GUARD + lay.offC
-        self.A = np.full(self.baseA + (batch - 1) * self.sA + m * lda + GUARD, QNAN, dtype=np.uint32)
-        self.B = np.full(self.baseB + (nb - 1) * sBe + k * n + GUARD, QNAN, dtype=np.uint32)
-        self.C = np.full(self.baseC + (batch - 1) * self.sC + m * n + GUARD, SENT, dtype=np.uint32)
-        self.iA = (self.baseA + np.arange(batch)[:, None, None] * self.sA + np.arange(m)[None, :, None] * lda + np.arange(k)[None, None, :]).reshape(-1)
-        self.iB = (self.baseB + np.arange(nb)[:, None] * sBe + np.arange(k * n)[None, :]).reshape(-1)
-        self.iC = (self.baseC + np.arange(batch)[:, None] * self.sC + np.arange(m * n)[None, :]).reshape(-1)
+        Strided.__init__(self, m, n, k, lay, GUARD + lay.offA, GUARD + lay.offB, GUARD + lay.offC)
+        self.kind = kind
+        batch, nb = self.batch, self.nb
+        self.gA = Guarded(self.baseA + (batch - 1) * self.sA + m * self.lda + GUARD, QNAN, np.uint32, self.baseA, self.iA)
+        self.gB = Guarded(self.baseB + (nb - 1) * self.sBe + k * n + GUARD, QNAN, np.uint32, self.baseB, self.iB)
+        self.gC = Guarded(self.baseC + (batch - 1) * self.sC + m * n + GUARD, SENT, np.uint32, self.baseC, self.iC)
+        self.A, self.B, self.C = self.gA.host, self.gB.host, self.gC.host
         a, b, c0 = draw(rng, kind, batch, nb, m, n, k) if data is None else data
         assert a.shape == (batch, m, k) and b.shape == (nb, k, n) and c0.shape == (batch, m, n)
         self.A[self.iA] = bits(np.ascontiguousarray(a, dtype=np.float32)).reshape(-1)
@@ -127,8 +113,7 @@ class Problem:
         self.reads_c = lay.beta != 0.0
         self.C0 = bits(np.ascontiguousarray(c0, dtype=np.float32)).reshape(-1) if self.reads_c else np.full(batch * m * n, SENT, dtype=np.uint32)
         self.C[self.iC] = self.C0
-        self.outC = np.ones(self.C.size, dtype=bool)
-        self.outC[self.iC] = False
+        self.outC = self.gC.outside
         self._refs = {}
 
     def a_compact(self):
@@ -167,15 +152,11 @@ class Problem:
 
     # ---- device ---------------------------------------------------------------------------------
     def to_device(self):
-        import torch
-        up = lambda a: torch.from_numpy(a.view(np.int32)).cuda()
-        self.dA, self.dB, self.dC = up(self.A), up(self.B), up(self.C)
-        for t in (self.dA, self.dB, self.dC):
-            assert t.data_ptr() % 16 == 0   # so that the base alignment is the offset's
+        self.dA, self.dB, self.dC = (g.to_device().dev for g in (self.gA, self.gB, self.gC))
         return self
 
     def ptr(self, which):
-        return getattr(self, "d" + which).data_ptr() + 4 * getattr(self, "base" + which)
+        return getattr(self, "g" + which).ptr
 
     def reset_c(self):
         import torch
@@ -183,22 +164,17 @@ class Problem:
 
     def result(self, what):
         """The logical C as bits, after asserting that every sentinel outside it kept its bits and that A and B are unchanged."""
-        import torch
-        torch.cuda.synchronize()
-        got = self.dC.cpu().numpy().view(np.uint32)
+        got = self.gC.read()
         if self.lay.gapC and self.batch > 1:
             gap = self.baseC + self.m * self.n + np.arange(self.lay.gapC)
             assert np.array_equal(got[gap], self.C[gap]), f"{what}: the strideC gap behind batch 0 was written (the fold fired on a gap, or b * strideC is wrong)"
-        changed = np.flatnonzero(self.outC & (got != self.C))
-        assert changed.size == 0, f"{what}: {changed.size} words of C outside the logical result were written, first at {changed[:8]}"
-        assert np.array_equal(self.dA.cpu().numpy().view(np.uint32), self.A), f"{what}: A was modified"
-        assert np.array_equal(self.dB.cpu().numpy().view(np.uint32), self.B), f"{what}: B was modified"
+        self.gC.assert_outside_kept(lambda n, first: f"{what}: {n} words of C outside the logical result were written, first at {first}", got)
+        assert self.gA.unchanged(), f"{what}: A was modified"
+        assert self.gB.unchanged(), f"{what}: B was modified"
         return got[self.iC]
 
     def untouched(self):
-        import torch
-        torch.cuda.synchronize()
-        return np.array_equal(self.dC.cpu().numpy().view(np.uint32), self.C)
+        return self.gC.unchanged()
 
     def check(self, orc, what, entry, got, planes=None):
         ref, scale = self.reference(orc, entry not in ("dense", "dsplit"))
@@ -212,7 +188,7 @@ class Problem:
             assert wrong.size == 0, (f"{what}: {wrong.size} results are not the exact product, first at (batch, row, col) "
                                      f"{np.unravel_index(wrong[:4], (self.batch, self.m, self.n))}")
         elif planes is not None:
-            ratio = float((np.abs(g.astype(np.float64) - ref) / tp.split_bound(planes, self.k, scale, ref)).max())
+            ratio = float((np.abs(g.astype(np.float64) - ref) / split_bound(planes, self.k, scale, ref)).max())
             MARGINS.append((what, ratio))
             assert ratio <= 1.0, f"{what}: max err / split bound = {ratio:.3f}"
             assert not (np.abs(g.astype(np.float64) - ref) > FP32_TOL * np.maximum(scale, 1e-30)).any()
@@ -537,18 +513,6 @@ def test_refusals_leave_c_alone(gpu, name):
 # ---------------------------------------------------------------------------------------------
 # margins of this file's `uniform` comparisons, appended to the session's report: the worst per entry point, then the worst cases
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", autouse=True)
-def _strided32_margin_report():
-    start = len(MARGINS)
-    yield
-    mine = MARGINS[start:]
-    if not mine:
-        return
-    lines = [f"{len(mine)} comparisons of tests/test_gpu_strided32.py against the numpy fp64 product; err / bound (check_close; split forms: split_bound), "
-             "worst per entry point:"]
-    for entry in sorted({w.split()[0] for w, _ in mine}):
-        w, r = max(((w, r) for w, r in mine if w.split()[0] == entry), key=lambda t: t[1])
-        lines.append(f"  {r:6.3f}  {w}")
-    lines.append("worst first:")
-    lines += [f"  {r:6.3f}  {w}" for w, r in sorted(mine, key=lambda t: -t[1])[:25]]
-    tp.write_margin_report(lines)
+_strided32_margin_report = margin_report_fixture(
+    "{n} comparisons of tests/test_gpu_strided32.py against the numpy fp64 product; err / bound (check_close; split forms: split_bound), "
+    "worst per entry point:", per_first_word=True)

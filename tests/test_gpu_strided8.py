@@ -7,8 +7,8 @@ its tile changes a sentinel.  The references are NOT the library: the gathered l
 compact copy (fp8: on its fp16 image), times the gathered B in numpy -- int64 for int8 (exact), fp64 for fp8.  fp8 operands are drawn
 from EXACT_VALS with row scales in {0.5, 1, 2} and (alpha, beta) in {(1, 0), (0.5, -2)}, so every fp32 product, sum, scale and add is
 exact and C must equal the fp64 result rounded once, bit for bit (the premise is asserted per case: Problem.assert_exact_premise);
-random finite operands are held to test_gpu_dense8's bound on the layout `all`.  Every fused call must also equal, bit for bit,
-prune + compress + the staged matmul on compact copies (include/sparsifyme.h).
+random finite operands are held to the dense 1-byte GEMM's bound (b8_testlib's constants) on the layout `all`.  Every fused call must
+also equal, bit for bit, prune + compress + the staged matmul on compact copies (include/sparsifyme.h).
 
 The launch classes of launch_spmma_b8 (csrc/spmma_b8.h) are fixed by n alone, so a shape pins the kernel that runs:
 
@@ -26,11 +26,9 @@ The launch classes of launch_spmma_b8 (csrc/spmma_b8.h) are fixed by n alone, so
 import numpy as np
 import pytest
 
-import test_gpu_parity as tp
-from test_gpu_parity import MARGINS
-from test_gpu_dense8 import EXACT_VALS, FMTS, OUTS, PAIRS, ROUND, TINY, finite_bytes, ksteps, odt, tdt, to8
-from test_gpu_fp8 import img16, make_bytes, map_back, val64
-from test_gpu_quant_fp8 import ref_quant_rows
+from b8_testlib import EXACT_VALS, FMTS, OUTS, PAIRS, ROUND, TINY, finite_bytes, img16, ksteps, make_bytes, map_back, odt, ref_quant_rows, tdt, to8, val64
+from guard_testlib import Guarded, Layout, Strided, margin_report_fixture, seed
+from parity_testlib import MARGINS
 
 pytestmark = pytest.mark.gpu
 
@@ -46,10 +44,7 @@ def sentinel(dt):
 
 
 def _seed(*xs):
-    s = 0x5718
-    for x in xs:
-        s = s * 1000003 + (sum(map(ord, x)) if isinstance(x, str) else int(x))
-    return s % (1 << 32)
+    return seed(0x5718, *xs)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -139,39 +134,21 @@ def blob_ref(orc, a, kind, m, k, batch):
 # ---------------------------------------------------------------------------------------------
 # the layout builder
 # ---------------------------------------------------------------------------------------------
-class Layout:
-    """Where the logical operands lie: element offsets of the bases, lda = k + lda_pad, strideX = its contiguous value + gapX
-    (gapB None: one shared B, strideB = 0); rs: an fp8 row_scale; beta != 0 means accumulate for an int32 C."""
+class Problem(Strided):
+    """Padded host buffers, index maps of the logical operands, the references and -- after to_device(), which the constructor calls
+    unless told upload=False -- the device copies.  fa / fb: "e4m3", "e5m2" or "i8" (both); out: "f32" / "f16" / "bf16" (fp8), "i32" / "q"
+    (int8); data: "exact" or "rand" (fp8).  beta != 0 means accumulate for an int32 C.  (B is stored [n][k]: k * n elements all the same.)"""
 
-    def __init__(self, lda_pad=0, gapA=0, gapB=None, gapC=0, offA=0, offB=0, offC=0, batch=2, alpha=1.0, beta=0.0, rs=False):
-        self.lda_pad, self.gapA, self.gapB, self.gapC = lda_pad, gapA, gapB, gapC
-        self.offA, self.offB, self.offC, self.batch, self.alpha, self.beta, self.rs = offA, offB, offC, batch, alpha, beta, rs
-
-
-class Problem:
-    """Padded host buffers, their device copies, index maps of the logical operands and the references.  fa / fb: "e4m3", "e5m2"
-    or "i8" (both); out: "f32" / "f16" / "bf16" (fp8), "i32" / "q" (int8); data: "exact" or "rand" (fp8)."""
-
-    def __init__(self, rng, m, n, k, lay, fa, fb, out, data="exact", slack_rows=64):
-        import torch
-        self.m, self.n, self.k, self.lay, self.fa, self.fb, self.out, self.data = m, n, k, lay, fa, fb, out, data
+    def __init__(self, rng, m, n, k, lay, fa, fb, out, data="exact", slack_rows=64, upload=True):
+        Strided.__init__(self, m, n, k, lay, lay.offA, lay.offB, lay.offC)
+        self.fa, self.fb, self.out, self.data = fa, fb, out, data
         self.i8 = fa == "i8"
-        self.batch = batch = lay.batch
-        self.lda = lda = k + lay.lda_pad
-        self.sA = m * lda + lay.gapA
-        self.sB = 0 if lay.gapB is None else n * k + lay.gapB
-        self.sC = m * n + lay.gapC
-        self.nb = nb = 1 if lay.gapB is None else batch
+        batch, nb, lda = self.batch, self.nb, self.lda
         # slack after each buffer: whole-tile reads past a ragged m or n stay inside the allocations
-        nA = lay.offA + batch * self.sA + slack_rows * lda + 256
-        nB = lay.offB + nb * (n * k + (lay.gapB or 0)) + 64 * k + 256
-        nC = lay.offC + batch * self.sC + 256
-        self.A = np.full(nA, POISON[fa], dtype=np.uint8)
-        self.B = np.full(nB, POISON[fb], dtype=np.uint8)
-        self.C = np.full(nC, sentinel(ELT[out]), dtype=ELT[out])
-        self.iA = (lay.offA + np.arange(batch)[:, None, None] * self.sA + np.arange(m)[None, :, None] * lda + np.arange(k)[None, None, :]).reshape(-1)
-        self.iB = (lay.offB + np.arange(nb)[:, None] * (n * k + (lay.gapB or 0)) + np.arange(n * k)[None, :]).reshape(-1)
-        self.iC = (lay.offC + np.arange(batch)[:, None] * self.sC + np.arange(m * n)[None, :]).reshape(-1)
+        self.gA = Guarded(lay.offA + batch * self.sA + slack_rows * lda + 256, POISON[fa], np.uint8, lay.offA, self.iA)
+        self.gB = Guarded(lay.offB + nb * self.sBe + 64 * k + 256, POISON[fb], np.uint8, lay.offB, self.iB)
+        self.gC = Guarded(lay.offC + batch * self.sC + 256, sentinel(ELT[out]), ELT[out], lay.offC, self.iC)
+        self.A, self.B, self.C = self.gA.host, self.gB.host, self.gC.host
         if self.i8:
             a = rng.integers(-128, 128, (batch * m, k)).astype(np.int8)
             a[:, 0], a[:, -1] = -128, 127
@@ -196,12 +173,20 @@ class Problem:
         self.rs = None
         if lay.rs and not self.i8:
             self.rs = (rng.choice(np.array([0.5, 1.0, 2.0]), m) if data == "exact" else rng.uniform(0.25, 2.0, m)).astype(np.float32)
-            self.drs = torch.from_numpy(np.concatenate([self.rs, np.full(1024, np.nan, dtype=np.float32)])).cuda()
-        self.dA, self.dB, self.dC = dev_bytes(self.A, fa), dev_bytes(self.B, fb), dev_c(self.C, out)
-        for t in (self.dA, self.dB, self.dC):
-            assert t.data_ptr() % 16 == 0   # so that the base alignment is the offset's
-        self.pA, self.pB, self.pC = self.dA[lay.offA:], self.dB[lay.offB:], self.dC[lay.offC:]
         self._refs = {}
+        if upload:
+            self.to_device()
+
+    def to_device(self):
+        import torch
+        lay = self.lay
+        if self.rs is not None:
+            self.drs = torch.from_numpy(np.concatenate([self.rs, np.full(1024, np.nan, dtype=np.float32)])).cuda()
+        self.dA = self.gA.to_device().dev.view(torch.int8 if self.i8 else tdt(self.fa))
+        self.dB = self.gB.to_device().dev.view(torch.int8 if self.i8 else tdt(self.fb))
+        self.dC = self.gC.to_device().dev.view(c_torch(self.out))
+        self.pA, self.pB, self.pC = self.dA[lay.offA:], self.dB[lay.offB:], self.dC[lay.offC:]
+        return self
 
     def a_compact(self):
         return self.A[self.iA].copy()
@@ -210,7 +195,7 @@ class Problem:
         return self.B[self.iB].copy()
 
     def reset_c(self):
-        self.dC = dev_c(self.C, self.out)
+        self.dC = self.gC.to_device().dev.view(c_torch(self.out))
         self.pC = self.dC[self.lay.offC:]
 
     # ---- references -------------------------------------------------------------------------
@@ -249,12 +234,7 @@ class Problem:
     # ---- results ----------------------------------------------------------------------------
     def result(self, what):
         """The logical C as bits, after asserting that every sentinel outside it kept its bits."""
-        got = host_c(self.dC)
-        outside = np.ones(got.size, dtype=bool)
-        outside[self.iC] = False
-        changed = np.flatnonzero(outside & (got != self.C))
-        assert changed.size == 0, f"{what}: {changed.size} elements of C outside the logical result were written, first at {changed[:8]}"
-        return got[self.iC]
+        return self.gC.result(lambda n, first: f"{what}: {n} elements of C outside the logical result were written, first at {first}")
 
     def _where(self, idx):
         return np.unravel_index(idx[:4], (self.batch, self.m, self.n))
@@ -269,7 +249,7 @@ class Problem:
         if self.data == "exact":
             wrong = np.flatnonzero(got != bits_of(ref, self.out))
             assert wrong.size == 0, f"{what}: {wrong.size} results are not the exact product rounded once, first at (batch, row, col) {self._where(wrong)}"
-        else:   # test_gpu_dense8's bound, from its constants
+        else:   # the dense 1-byte GEMM's bound, from b8_testlib's constants
             bound = ROUND[self.out] * np.abs(ref) + (2.0 * ksteps(self.k) + 4.0) * 2.0 ** -24 * scale + TINY[self.out]
             ratio = float((np.abs(g64 - ref) / bound).max())
             print(f"{what}: err/bound {ratio:.3f}")
@@ -442,7 +422,7 @@ def test_both_sides_of_each_threshold(gpu, orc, fam, n):
 @pytest.mark.parametrize("k", KS)
 @pytest.mark.parametrize("n", NS["fp8"])
 def test_fp8_random_operands_within_the_dense8_bound(gpu, orc, n, k):
-    """Random finite operands on the layout `all`, per entry point and class: test_gpu_dense8's bound, ratios to the margins report."""
+    """Random finite operands on the layout `all`, per entry point and class: the dense 1-byte GEMM's bound, ratios to the margins report."""
     out = OUTS[(NS["fp8"].index(n) + KS.index(k)) % 3]
     p = Problem(np.random.default_rng(_seed("rand", n, k)), M, n, k, Layout(**LAYOUTS["all"]), "e4m3", "e5m2", out, data="rand")
     run_entries(gpu, orc, p, f"strided8 random e4m3xe5m2->{out} all (m, n, k) = {(M, n, k)}")
@@ -674,13 +654,5 @@ def test_quantize_compress24_fp8_from_padded_a_drives_spmma_fp8(gpu, orc, src):
 # ---------------------------------------------------------------------------------------------
 # margins of this file's random comparisons, appended to the session's report
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", autouse=True)
-def _strided8_margin_report():
-    start = len(MARGINS)
-    yield
-    mine = MARGINS[start:]
-    if not mine:
-        return
-    lines = [f"{len(mine)} comparisons of tests/test_gpu_strided8.py against the fp64 product; err / (ROUND*|ref| + (2*ksteps(k)+4)*2^-24*sum|ab| + TINY), worst first:"]
-    lines += [f"  {r:6.3f}  {w}" for w, r in sorted(mine, key=lambda t: -t[1])]
-    tp.write_margin_report(lines)
+_strided8_margin_report = margin_report_fixture(
+    "{n} comparisons of tests/test_gpu_strided8.py against the fp64 product; err / (ROUND*|ref| + (2*ksteps(k)+4)*2^-24*sum|ab| + TINY), worst first:")
