@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <cmath>
 #include <cstddef>
 #include <iostream>
 #include <vector>
@@ -120,6 +121,13 @@ struct spmma_fns_f16 {
                         std::size_t hidden, std::size_t ldh, std::size_t ldd, std::size_t ldn, std::size_t ldq, float eps, int fmt, hipStream_t st) {
     return sm_rmsnorm_f16(H, D, gamma, res, N, Q, row_scale, tokens, hidden, ldh, ldd, ldn, ldq, eps, fmt, st);
   }
+  static int attn_decode_on(const void* Q, const void* Kc, const void* Vc, const int* bt, const int* sl, void* O, float* lse, void* ws, std::size_t ws_bytes,
+                            std::size_t seqs, std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t num_pages, std::size_t page_size,
+                            std::size_t max_pages, std::size_t ldq, std::size_t ldkv, std::size_t page_stride, std::size_t ldbt, std::size_t ldo, float scale,
+                            hipStream_t st) {
+    return sm_attn_decode_f16(Q, Kc, Vc, bt, sl, O, lse, ws, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages, ldq, ldkv, page_stride,
+                             ldbt, ldo, scale, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -198,6 +206,13 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
   static int rmsnorm_on(const void* H, const void* D, const void* gamma, void* res, void* N, void* Q, float* row_scale, std::size_t tokens,
                         std::size_t hidden, std::size_t ldh, std::size_t ldd, std::size_t ldn, std::size_t ldq, float eps, int fmt, hipStream_t st) {
     return sm_rmsnorm_bf16(H, D, gamma, res, N, Q, row_scale, tokens, hidden, ldh, ldd, ldn, ldq, eps, fmt, st);
+  }
+  static int attn_decode_on(const void* Q, const void* Kc, const void* Vc, const int* bt, const int* sl, void* O, float* lse, void* ws, std::size_t ws_bytes,
+                            std::size_t seqs, std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t num_pages, std::size_t page_size,
+                            std::size_t max_pages, std::size_t ldq, std::size_t ldkv, std::size_t page_stride, std::size_t ldbt, std::size_t ldo, float scale,
+                            hipStream_t st) {
+    return sm_attn_decode_bf16(Q, Kc, Vc, bt, sl, O, lse, ws, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages, ldq, ldkv, page_stride,
+                             ldbt, ldo, scale, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -683,6 +698,30 @@ int rmsnorm(const type_t* d_H, const type_t* d_D, const type_t* d_gamma, type_t*
             std::size_t ldd = 0, std::size_t ldn = 0, std::size_t ldq = 0) {
   return detail::spmma_fns<type_t>::rmsnorm_on(d_H, d_D, d_gamma, d_res_out, d_N, d_Q, d_row_scale, tokens, hidden, ldh ? ldh : hidden, ldd ? ldd : hidden,
                                                ldn ? ldn : hidden, ldq ? ldq : hidden, eps, fmt, stream);
+}
+
+// Extension (fp16 / bfloat16): single-query attention over a paged KV cache (sm_attn_decode_*): d_Q [seqs][q_heads][head_dim]; d_Kc / d_Vc
+// [num_pages][page_size][kv_heads][head_dim]; d_block_table [seqs][max_pages] and d_seq_lens [seqs], int32 in device memory; d_O like d_Q; d_lse
+// [seqs][q_heads] fp32 or null.  Query head h reads KV head h / (q_heads / kv_heads); page ids outside [0, num_pages) are absent pages; the
+// context is split into chunks of SM_ATTN_DECODE_CHUNK tokens merged in ascending order (include/sparsifyme.h has the definition to the
+// letter).  scale 0 = head_dim^-1/2.  Pitches in elements, 0 = the extent: ldq / ldo q_heads * head_dim, ldkv kv_heads * head_dim, page_stride
+// page_size * ldkv, ldbt max_pages.  workspace: attn_decode_workspace_size(...) bytes, null where that is 0 (max_pages * page_size <=
+// SM_ATTN_DECODE_CHUNK).  head_dim 64 or 128, page_size 16 .. 128, q_heads / kv_heads <= 16, 16-byte aligned rows.  Enqueue only.
+inline std::size_t attn_decode_workspace_size(std::size_t seqs, std::size_t q_heads, std::size_t head_dim, std::size_t page_size, std::size_t max_pages) {
+  std::size_t bytes = 0;
+  (void)sm_attn_decode_workspace_size(seqs, q_heads, head_dim, page_size, max_pages, &bytes);
+  return bytes;
+}
+template <typename type_t>
+int attn_decode(const type_t* d_Q, const type_t* d_Kc, const type_t* d_Vc, const int* d_block_table, const int* d_seq_lens, type_t* d_O, std::size_t seqs,
+                std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t num_pages, std::size_t page_size, std::size_t max_pages,
+                void* workspace = nullptr, std::size_t workspace_bytes = 0, float* d_lse = nullptr, float scale = 0.0f, hipStream_t stream = nullptr,
+                std::size_t ldq = 0, std::size_t ldkv = 0, std::size_t page_stride = 0, std::size_t ldbt = 0, std::size_t ldo = 0) {
+  const std::size_t kv = ldkv ? ldkv : kv_heads * head_dim;
+  return detail::spmma_fns<type_t>::attn_decode_on(d_Q, d_Kc, d_Vc, d_block_table, d_seq_lens, d_O, d_lse, workspace, workspace_bytes, seqs, q_heads, kv_heads,
+                                                   head_dim, num_pages, page_size, max_pages, ldq ? ldq : q_heads * head_dim, kv,
+                                                   page_stride ? page_stride : page_size * kv, ldbt ? ldbt : max_pages, ldo ? ldo : q_heads * head_dim,
+                                                   scale != 0.0f ? scale : 1.0f / std::sqrt((float)head_dim), stream);
 }
 
 // Extension (fp16 / bfloat16): the un-permute and weighted sum over top_k that close the block (sm_moe_combine_*):

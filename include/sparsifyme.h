@@ -770,6 +770,80 @@ int sm_rmsnorm_bf16(const void* H, const void* D, const void* gamma, void* res_o
                     size_t hidden, size_t ldh, size_t ldd, size_t ldn, size_t ldq, float eps, int fmt, sm_stream_t stream);
 int sm_rmsnorm_form(size_t hidden, int* form);
 
+/* ---- Paged-KV decode attention (extension): one query token per sequence over a paged KV cache, grouped query heads (GQA), the
+ *      context split into chunks; fp16 / bf16.  All pitches are in elements.
+ *      Q[seqs][q_heads][head_dim], row pitch ldq >= q_heads * head_dim (a column slice of a fused QKV projection's output, used as it
+ *      is).  Kc and Vc are each [num_pages][page_size][kv_heads][head_dim]: token pitch ldkv >= kv_heads * head_dim, page pitch
+ *      page_stride >= page_size * ldkv (token-major inside a page: appending a token is one row of the QKV projection).
+ *      block_table[seqs][max_pages] (int32, DEVICE memory, pitch ldbt) and seq_lens[seqs] (int32, DEVICE memory).  O[seqs][q_heads]
+ *      [head_dim], pitch ldo.  lse[seqs][q_heads] fp32, compact, or NULL.  Query head h reads KV head h / (q_heads / kv_heads).
+ *      Definition, per (sequence s, query head h), all in fp32:
+ *        L = clamp(seq_lens[s], 0, max_pages * page_size).  Token t < L lives in page block_table[s][t / page_size], slot
+ *          t % page_size.  A page id outside [0, num_pages) makes that page's tokens ABSENT: they take no part in the maximum, the sum
+ *          or the product, and no address is ever formed from such an id.  Table entries at or beyond ceil(L / page_size) are never
+ *          read.  Slots at or beyond L in the last page take no part: they are masked by selection, not by a multiply (the cache may
+ *          hold NaN there), and they are never loaded.
+ *        s_t = scale * sum_d fp32(q_d) * fp32(k_t,d).  The order of the sum is not fixed by the definition.
+ *        The context is cut into chunks of SM_ATTN_DECODE_CHUNK tokens (a multiple of every allowed page_size); chunk c holds tokens
+ *          c * CHUNK .. and yields (m_c, l_c, acc_c) over its present tokens t < L:
+ *        m_c = max_t s_t
+ *        p_t = rne16(exp2f((s_t - m_c) * log2e)): log2e = 1.44269502f, one fp32 multiply, then exp2f as the hardware's v_exp_f32
+ *          evaluates it (1 ulp; exp2f(0) = 1 exactly, and a result below 2^-126 is 0), then one rounding to nearest even to the
+ *          operand's 16-bit type
+ *        l_c = sum_t fp32(p_t), from the SAME rounded p_t that enter the product: the output is a convex combination of V rows
+ *        acc_c,d = sum_t fp32(p_t) * fp32(v_t,d)
+ *        A chunk without a present token has m_c = -inf, l_c = 0, acc_c = 0.  The order of the two sums inside a chunk is the
+ *          kernel's, a function of the chunk alone.
+ *        m = max_c m_c;  w_c = exp2f((m_c - m) * log2e);  l = sum_c w_c * l_c;  acc_d = sum_c w_c * acc_c,d: both sums in ASCENDING c
+ *          over the ceil(L / CHUNK) chunks the sequence has.  With one chunk this is that chunk (w = 1).
+ *        O_d = rne16(acc_d / l): one correctly rounded fp32 division, then one rounding.  lse = m + logf(l).
+ *        L == 0, or every page absent: O = +0 and lse = -inf.
+ *        NaN and inf in present tokens go through this arithmetic as IEEE has it (the maximum ignores a NaN); only memory safety
+ *          and the masking above are guaranteed then.
+ *      The chunk size does not depend on seqs, so a sequence's bits do not depend on which sequences ride along, and two runs on the
+ *      same operands give the same bits.
+ *      Forms (sm_attn_decode_form; the entry points switch on it): SM_ATTN_DECODE_FORM_DIRECT, max_pages * page_size <=
+ *      SM_ATTN_DECODE_CHUNK: one launch, workspace may be NULL; _SPLIT: a partial kernel -- one workgroup per (sequence, kv head,
+ *      chunk); one whose chunk starts at or beyond L returns at once -- then a combine kernel: two launches, no atomics, no memset
+ *      node; the workspace (sm_attn_decode_workspace_size bytes: seqs * q_heads * ceil(max_pages * page_size / CHUNK) * (head_dim + 2)
+ *      * 4; 4-byte aligned) holds acc, m and l per (sequence, query head, chunk), and the combine reads only the ceil(L / CHUNK)
+ *      chunks a sequence has, so stale workspace bytes are never read; _EMPTY: seqs == 0 or q_heads == 0; _INVALID: what the entry
+ *      points refuse by a limit below, kv_heads == 0 or q_heads % kv_heads != 0.
+ *      Limits: head_dim is SM_ATTN_DECODE_MIN_HEAD_DIM (64) or SM_ATTN_DECODE_MAX_HEAD_DIM (128); page_size is a power of two from
+ *      SM_ATTN_DECODE_MIN_PAGE_SIZE (16) to SM_ATTN_DECODE_MAX_PAGE_SIZE (128); q_heads % kv_heads == 0 and the group q_heads /
+ *      kv_heads <= SM_ATTN_DECODE_MAX_GROUP (16: one 16-row matrix-instruction tile of query rows); max_pages * page_size <=
+ *      SM_ATTN_DECODE_MAX_CONTEXT (2^31 - 1); rows of Q, Kc, Vc and O 16-byte aligned (pointer, ldq, ldkv, page_stride, ldo % 8 == 0).
+ *      Status, decided before any device work, in this order: a null Q, Kc, Vc, block_table, seq_lens or O; a pitch below its
+ *      extent; kv_heads == 0 with q_heads > 0; q_heads % kv_heads != 0; max_pages * page_size > CHUNK with a null, misaligned or short
+ *      workspace; scale NaN: SM_STATUS_INVALID_VALUE; then a dimension, a pitch, q_heads * head_dim, kv_heads * head_dim or seqs *
+ *      q_heads >= 2^31, then the limits above in the listed order: SM_STATUS_NOT_SUPPORTED (the text names the limit); seqs == 0 or
+ *      q_heads == 0: success, nothing enqueued.
+ *      Enqueue only: no allocation, no synchronisation; capturable into a hipGraph, and a captured graph stays valid when seq_lens
+ *      and block_table change on the device.  Nothing outside O, lse and the workspace is written.
+ *      Not covered: more than one query token per sequence, a sliding window, soft-capping, ALiBi, an fp8 cache, head dimensions
+ *      other than the two, RoPE, the cache append, prefill. */
+#define SM_ATTN_DECODE_CHUNK 256
+#define SM_ATTN_DECODE_MIN_HEAD_DIM 64
+#define SM_ATTN_DECODE_MAX_HEAD_DIM 128
+#define SM_ATTN_DECODE_MIN_PAGE_SIZE 16
+#define SM_ATTN_DECODE_MAX_PAGE_SIZE 128
+#define SM_ATTN_DECODE_MAX_GROUP 16
+#define SM_ATTN_DECODE_MAX_CONTEXT 2147483647
+#define SM_ATTN_DECODE_FORM_INVALID 0
+#define SM_ATTN_DECODE_FORM_EMPTY 1
+#define SM_ATTN_DECODE_FORM_DIRECT 2
+#define SM_ATTN_DECODE_FORM_SPLIT 3
+int sm_attn_decode_f16(const void* Q, const void* Kc, const void* Vc, const int* block_table, const int* seq_lens, void* O, float* lse,
+                       void* workspace, size_t workspace_bytes, size_t seqs, size_t q_heads, size_t kv_heads, size_t head_dim,
+                       size_t num_pages, size_t page_size, size_t max_pages, size_t ldq, size_t ldkv, size_t page_stride, size_t ldbt,
+                       size_t ldo, float scale, sm_stream_t stream);
+int sm_attn_decode_bf16(const void* Q, const void* Kc, const void* Vc, const int* block_table, const int* seq_lens, void* O, float* lse,
+                        void* workspace, size_t workspace_bytes, size_t seqs, size_t q_heads, size_t kv_heads, size_t head_dim,
+                        size_t num_pages, size_t page_size, size_t max_pages, size_t ldq, size_t ldkv, size_t page_stride, size_t ldbt,
+                        size_t ldo, float scale, sm_stream_t stream);
+int sm_attn_decode_workspace_size(size_t seqs, size_t q_heads, size_t head_dim, size_t page_size, size_t max_pages, size_t* bytes);
+int sm_attn_decode_form(size_t seqs, size_t q_heads, size_t kv_heads, size_t head_dim, size_t page_size, size_t max_pages, int* form);
+
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +
  * sm_spmma_f32 to fp32 accumulation order.  Needs k % 32 == 0, n % 4 == 0, 16-byte aligned rows. */

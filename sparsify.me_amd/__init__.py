@@ -201,6 +201,11 @@ _SIGS["sm_moe_gate_form"] = [_c_size] * 3 + [ctypes.POINTER(_c_i)]
 for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_rmsnorm_" + _sfx16] = [_c_ptr] * 7 + [_c_size] * 6 + [_c_f, _c_i, _c_ptr]
 _SIGS["sm_rmsnorm_form"] = [_c_size, ctypes.POINTER(_c_i)]
+# paged-KV decode attention (attn_decode.hip)
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_attn_decode_" + _sfx16] = [_c_ptr] * 8 + [_c_size] * 13 + [_c_f, _c_ptr]
+_SIGS["sm_attn_decode_workspace_size"] = [_c_size] * 5 + [ctypes.POINTER(_c_size)]
+_SIGS["sm_attn_decode_form"] = [_c_size] * 6 + [ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -991,6 +996,76 @@ def rmsnorm(h, delta=None, gamma=None, eps=1e-6, out=None, res_out=None, fp8=Non
               ldh, _rows2d(delta, "rmsnorm", "delta") if delta is not None else 0, _rows2d(out, "rmsnorm", "out") if out is not None else 0,
               _rows2d(Q, "rmsnorm", "Q") if Q is not None else 0, float(eps), fp8_format(Q.dtype) if Q is not None else 0, _stream()), "sm_rmsnorm")
     return out if fp8 is None else (out, Q, rs)
+
+
+# include/sparsifyme.h: SM_ATTN_DECODE_FORM_* (index = value), SM_ATTN_DECODE_CHUNK and the limits
+ATTN_DECODE_FORMS = ("invalid", "empty", "direct", "split")
+ATTN_DECODE_CHUNK = 256
+ATTN_DECODE_HEAD_DIMS = (64, 128)
+ATTN_DECODE_PAGE_SIZES = (16, 32, 64, 128)
+ATTN_DECODE_MAX_GROUP = 16
+ATTN_DECODE_MAX_CONTEXT = 2 ** 31 - 1
+
+
+def attn_decode_form(seqs, q_heads, kv_heads, head_dim, page_size, max_pages):
+    """The name (ATTN_DECODE_FORMS) of the form attn_decode runs -- sm_attn_decode_form, the rule the entry points switch on.  Host only."""
+    form = _c_i(-1)
+    _check(lib().sm_attn_decode_form(seqs, q_heads, kv_heads, head_dim, page_size, max_pages, ctypes.byref(form)), "sm_attn_decode_form")
+    return ATTN_DECODE_FORMS[form.value]
+
+
+def attn_decode_workspace_size(seqs, q_heads, head_dim, page_size, max_pages):
+    """Bytes of workspace attn_decode needs (0 in the direct form) -- sm_attn_decode_workspace_size.  Host only."""
+    out = ctypes.c_size_t(0)
+    _check(lib().sm_attn_decode_workspace_size(seqs, q_heads, head_dim, page_size, max_pages, ctypes.byref(out)), "sm_attn_decode_workspace_size")
+    return out.value
+
+
+def attn_decode(q, k_cache, v_cache, block_table, seq_lens, scale=None, out=None, lse=None, workspace=None):
+    """Single-query attention over a paged KV cache (sm_attn_decode_*).  q: [seqs][q_heads][head_dim] float16 / bfloat16 with contiguous
+    heads (any row pitch: a column slice of a fused QKV output); k_cache, v_cache: [num_pages][page_size][kv_heads][head_dim] of q's dtype
+    with contiguous heads (any token and page pitch); block_table: int32 [seqs][max_pages] (any row pitch), seq_lens: int32 [seqs], both on
+    the device.  scale: head_dim ** -0.5 when None.  out: [seqs][q_heads][head_dim] (allocated when None); lse: a contiguous float32
+    [seqs][q_heads], or None; workspace: a uint8 tensor of attn_decode_workspace_size bytes (allocated when None and the form is split).
+    Returns out."""
+    torch = _t()
+    sfx = _quant_src_sfx(q, "attn_decode")
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 or block_table.dim() != 2 or seq_lens.dim() != 1:
+        raise SparsifymeError("attn_decode: q is [seqs][q_heads][head_dim], the caches [num_pages][page_size][kv_heads][head_dim], block_table "
+                              "[seqs][max_pages], seq_lens [seqs]")
+    seqs, q_heads, head_dim = q.shape
+    num_pages, page_size, kv_heads, _ = k_cache.shape
+    max_pages = block_table.shape[1]
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.shape[3] != head_dim:
+        raise SparsifymeError("attn_decode: the caches have q's dtype and head_dim, and one shape")
+    if v_cache.stride() != k_cache.stride():
+        raise SparsifymeError("attn_decode: the caches have the same strides")
+    if block_table.dtype != torch.int32 or seq_lens.dtype != torch.int32 or block_table.shape[0] != seqs or seq_lens.shape[0] != seqs or \
+            not seq_lens.is_contiguous() or (max_pages > 1 and block_table.stride(1) != 1):
+        raise SparsifymeError("attn_decode: block_table is int32 [seqs][max_pages] with contiguous rows, seq_lens a contiguous int32 [seqs]")
+    if out is None:
+        out = torch.empty((seqs, q_heads, head_dim), dtype=q.dtype, device=q.device)
+    for name, t in (("q", q), ("out", out)):
+        if t.dtype != q.dtype or tuple(t.shape) != (seqs, q_heads, head_dim) or (head_dim > 1 and t.stride(2) != 1) or (q_heads > 1 and t.stride(1) != head_dim):
+            raise SparsifymeError(f"attn_decode: {name} is [seqs][q_heads][head_dim] of one dtype with contiguous heads (any row pitch)")
+    if (head_dim > 1 and k_cache.stride(3) != 1) or (kv_heads > 1 and k_cache.stride(2) != head_dim):
+        raise SparsifymeError("attn_decode: a cache token is [kv_heads][head_dim], contiguous")
+    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != (seqs, q_heads) or not lse.is_contiguous()):
+        raise SparsifymeError("attn_decode: lse is a contiguous float32 [seqs][q_heads]")
+    pitch = lambda t, d, least: t.stride(d) if t.shape[d] > 1 else max(t.stride(d), least)
+    ldq, ldo = pitch(q, 0, q_heads * head_dim), pitch(out, 0, q_heads * head_dim)
+    ldkv = pitch(k_cache, 1, kv_heads * head_dim)
+    page_stride = pitch(k_cache, 0, page_size * ldkv)
+    ldbt = pitch(block_table, 0, max_pages)
+    need = attn_decode_workspace_size(seqs, q_heads, head_dim, page_size, max_pages)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    fn = getattr(lib(), "sm_attn_decode_" + sfx)
+    _check(fn(_dev(q), _dev(k_cache), _dev(v_cache), _dev(block_table), _dev(seq_lens), _dev(out), _dev(lse) if lse is not None else None,
+              _dev(workspace) if workspace is not None else None, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages,
+              ldq, ldkv, page_stride, ldbt, ldo, float(head_dim ** -0.5 if scale is None else scale), _stream()), "sm_attn_decode")
+    return out
 
 
 def quantize_compress24_fp8(A, blob, row_scale, rows, k, fmt_dtype, lda=None):
