@@ -128,6 +128,14 @@ struct spmma_fns_f16 {
     return sm_attn_decode_f16(Q, Kc, Vc, bt, sl, O, lse, ws, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages, ldq, ldkv, page_stride,
                              ldbt, ldo, scale, st);
   }
+  static int rope_append_on(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc, void* Vc, const float* cs, const int* positions,
+                            const int* token_seq, const int* seq_lens, const int* bt, std::size_t tokens, std::size_t seqs, std::size_t q_heads,
+                            std::size_t kv_heads, std::size_t head_dim, std::size_t rot_dim, std::size_t max_pos, std::size_t num_pages, std::size_t page_size,
+                            std::size_t max_pages, std::size_t ldq, std::size_t ldk, std::size_t ldv, std::size_t ldqo, std::size_t ldko, std::size_t ldkv,
+                            std::size_t page_stride, std::size_t ldcs, std::size_t ldbt, int style, hipStream_t st) {
+    return sm_rope_append_f16(Q, K, V, Qo, Ko, Kc, Vc, cs, positions, token_seq, seq_lens, bt, tokens, seqs, q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages,
+                              page_size, max_pages, ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride, ldcs, ldbt, style, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -213,6 +221,14 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
                             hipStream_t st) {
     return sm_attn_decode_bf16(Q, Kc, Vc, bt, sl, O, lse, ws, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages, ldq, ldkv, page_stride,
                              ldbt, ldo, scale, st);
+  }
+  static int rope_append_on(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc, void* Vc, const float* cs, const int* positions,
+                            const int* token_seq, const int* seq_lens, const int* bt, std::size_t tokens, std::size_t seqs, std::size_t q_heads,
+                            std::size_t kv_heads, std::size_t head_dim, std::size_t rot_dim, std::size_t max_pos, std::size_t num_pages, std::size_t page_size,
+                            std::size_t max_pages, std::size_t ldq, std::size_t ldk, std::size_t ldv, std::size_t ldqo, std::size_t ldko, std::size_t ldkv,
+                            std::size_t page_stride, std::size_t ldcs, std::size_t ldbt, int style, hipStream_t st) {
+    return sm_rope_append_bf16(Q, K, V, Qo, Ko, Kc, Vc, cs, positions, token_seq, seq_lens, bt, tokens, seqs, q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages,
+                              page_size, max_pages, ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride, ldcs, ldbt, style, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -722,6 +738,39 @@ int attn_decode(const type_t* d_Q, const type_t* d_Kc, const type_t* d_Vc, const
                                                    head_dim, num_pages, page_size, max_pages, ldq ? ldq : q_heads * head_dim, kv,
                                                    page_stride ? page_stride : page_size * kv, ldbt ? ldbt : max_pages, ldo ? ldo : q_heads * head_dim,
                                                    scale != 0.0f ? scale : 1.0f / std::sqrt((float)head_dim), stream);
+}
+
+// Extension (fp16 / bfloat16): RoPE on every Q and K head and the append of K and V to attn_decode's paged cache, in one launch
+// (sm_rope_append_*): d_Q [tokens][q_heads][head_dim], d_K / d_V [tokens][kv_heads][head_dim] (the column slices of a fused QKV output); d_Qo
+// receives the rotated Q (d_Q itself: in place), d_Ko the rotated K or null (d_K itself: in place); d_Kc / d_Vc the cache, or both null (then
+// d_Ko is required); d_cs the fp32 table [max_pos][rot_dim] (rope_table below), null with rot_dim 0; d_positions / d_token_seq [tokens],
+// d_seq_lens [seqs], d_block_table [seqs][max_pages], int32 in device memory: positions null takes seq_lens[s] - 1, token_seq null takes token
+// i as sequence i (the decode step).  include/sparsifyme.h has the definition to the letter.  Pitches in elements, 0 = the extent: ldq / ldqo
+// q_heads * head_dim, ldk / ldv / ldko / ldkv kv_heads * head_dim, page_stride page_size * ldkv, ldcs rot_dim, ldbt max_pages.  Enqueue only.
+template <typename type_t>
+int rope_append(const type_t* d_Q, const type_t* d_K, const type_t* d_V, type_t* d_Qo, type_t* d_Ko, type_t* d_Kc, type_t* d_Vc, const float* d_cs,
+                const int* d_positions, const int* d_token_seq, const int* d_seq_lens, const int* d_block_table, std::size_t tokens, std::size_t seqs,
+                std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t rot_dim, std::size_t max_pos, std::size_t num_pages,
+                std::size_t page_size, std::size_t max_pages, int style = SM_ROPE_NEOX, hipStream_t stream = nullptr, std::size_t ldq = 0, std::size_t ldk = 0,
+                std::size_t ldv = 0, std::size_t ldqo = 0, std::size_t ldko = 0, std::size_t ldkv = 0, std::size_t page_stride = 0, std::size_t ldcs = 0,
+                std::size_t ldbt = 0) {
+  const std::size_t qw = q_heads * head_dim, kw = kv_heads * head_dim, kv = ldkv ? ldkv : kw;
+  return detail::spmma_fns<type_t>::rope_append_on(d_Q, d_K, d_V, d_Qo, d_Ko, d_Kc, d_Vc, d_cs, d_positions, d_token_seq, d_seq_lens, d_block_table, tokens, seqs,
+                                                   q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages, page_size, max_pages, ldq ? ldq : qw, ldk ? ldk : kw,
+                                                   ldv ? ldv : kw, ldqo ? ldqo : qw, ldko ? ldko : kw, kv, page_stride ? page_stride : page_size * kv,
+                                                   ldcs ? ldcs : rot_dim, ldbt ? ldbt : max_pages, style, stream);
+}
+// The plain RoPE table on the host: cs[p][j] = cos(p theta_j), cs[p][rot_dim / 2 + j] = sin(p theta_j), theta_j = base^(-2 j / rot_dim),
+// evaluated in double and rounded once to float.  A set-up op, once per model; a scaled table is the caller's to build in this layout.
+inline void rope_table(float* cs, std::size_t max_pos, std::size_t rot_dim, double base = 10000.0) {
+  const std::size_t half = rot_dim / 2;
+  for (std::size_t j = 0; j < half; ++j) {
+    const double theta = std::pow(base, -2.0 * (double)j / (double)rot_dim);
+    for (std::size_t p = 0; p < max_pos; ++p) {
+      cs[p * rot_dim + j] = (float)std::cos((double)p * theta);
+      cs[p * rot_dim + half + j] = (float)std::sin((double)p * theta);
+    }
+  }
 }
 
 // Extension (fp16 / bfloat16): the un-permute and weighted sum over top_k that close the block (sm_moe_combine_*):

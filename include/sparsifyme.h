@@ -844,6 +844,86 @@ int sm_attn_decode_bf16(const void* Q, const void* Kc, const void* Vc, const int
 int sm_attn_decode_workspace_size(size_t seqs, size_t q_heads, size_t head_dim, size_t page_size, size_t max_pages, size_t* bytes);
 int sm_attn_decode_form(size_t seqs, size_t q_heads, size_t kv_heads, size_t head_dim, size_t page_size, size_t max_pages, int* form);
 
+/* ---- RoPE + paged KV-cache append (extension): the op between the QKV projection and sm_attn_decode_*, in one launch: rotate every Q
+ *      and K head of a token by its row of a cos/sin table, and write K and V into the token's slot of the paged cache; fp16 / bf16.
+ *      The same call is the decode step (one token per sequence) and the prefill (all tokens of several sequences).  All pitches are in
+ *      elements.
+ *      Q[tokens][q_heads][head_dim] (row pitch ldq), K[tokens][kv_heads][head_dim] (ldk) and V (ldv): the three column slices of one
+ *      fused QKV output, used as they are.  Qo (ldqo) receives the rotated Q; it may be Q itself, at equal pitch.  Ko (ldko) receives the
+ *      rotated K, or is NULL; it may be K itself, at equal pitch (what a framework attention needs at prefill).  Kc / Vc are the cache in
+ *      exactly sm_attn_decode_*'s layout, [num_pages][page_size][kv_heads][head_dim] with token pitch ldkv and page pitch page_stride;
+ *      both are given, or both are NULL, and with both NULL Ko is required.  cs[max_pos][rot_dim] is an fp32 table (row pitch ldcs): row
+ *      p holds cos(p * theta_j) for j < rot_dim / 2, then sin(p * theta_j).  The table is the caller's: linear, NTK, YaRN or llama-3
+ *      scaling is a matter of the table, not of this call.  positions[tokens], token_seq[tokens], seq_lens[seqs] and
+ *      block_table[seqs][max_pages] (pitch ldbt) are int32 in DEVICE memory.
+ *      Definition, per token i:
+ *        s_i = token_seq ? token_seq[i] : i.  The NULL case is the decode step: token i is sequence i.
+ *        pos_i = positions ? positions[i] : seq_lens[s_i] - 1.  The NULL case is the slot of the token the length already counts: the
+ *          host bumps seq_lens, then this call and sm_attn_decode_* read the same array.  seq_lens is read only when 0 <= s_i < seqs;
+ *          otherwise pos_i = -1.
+ *        A token with pos_i outside [0, max_pos) is a PADDING token: nothing is read from its rows and nothing is written for it -- not
+ *          Qo, Ko, Kc or Vc -- and no address is formed from its pos_i.  With rot_dim == 0 there is no table: cs may be NULL, max_pos is
+ *          ignored, and a token is padding only when pos_i < 0.
+ *        Rotation of every Q head and every K head: half = rot_dim / 2, c_j = cs[pos_i][j], s_j = cs[pos_i][half + j].  SM_ROPE_NEOX
+ *          pairs (a, b) = (j, j + half); SM_ROPE_INTERLEAVED pairs (a, b) = (2j, 2j + 1).  All arithmetic is in fp32 and is NOT
+ *          contracted:
+ *        y_a = rne16(fp32(x_a) * c_j - fp32(x_b) * s_j)
+ *        y_b = rne16(fp32(x_b) * c_j + fp32(x_a) * s_j)
+ *          Each line is two fp32 multiplies, each rounded, then one fp32 subtract or add, then one rounding to nearest even to the
+ *          16-bit type: never an fma.  Elements d >= rot_dim are copied bit for bit.  NaN, inf, -0 and subnormals go through this
+ *          arithmetic as IEEE has it; fp32 subnormals are not flushed.
+ *        Append: when 0 <= s_i < seqs, pos_i < max_pages * page_size and pg = block_table[s_i][pos_i / page_size] lies in
+ *          [0, num_pages), the rotated K goes to Kc[pg][pos_i % page_size] and V goes bit for bit to the same slot of Vc.  Otherwise the
+ *          token's Qo / Ko are still written, but the cache is not: no address is formed from an id out of range, and no table entry is
+ *          read for a padding token.  The cache offset is 64-bit arithmetic (pg * page_stride exceeds 2^31 on real caches).
+ *        Two tokens that name the same slot: either one's row ends up there, whole 16-byte pieces only; memory safe, not an error.
+ *      Aliasing allowed: Qo == Q and Ko == K, at equal pitch.  A lane reads both elements of every pair it owns before it stores
+ *      either.  Nothing else may alias.
+ *      Forms (sm_rope_append_form; the entry points switch on it; the op is elementwise with fixed arithmetic, so both forms give the
+ *      same bits): SM_ROPE_APPEND_FORM_BLOCK, tokens <= SM_ROPE_APPEND_BLOCK_MAX_TOKENS: one four-wave workgroup per token, the heads
+ *      dealt over its waves (the decode regime); _WAVE: one wave per token, four tokens per workgroup (the prefill regime); _EMPTY:
+ *      tokens == 0, q_heads + kv_heads == 0 or head_dim == 0; _INVALID: a head_dim or rot_dim the entry points refuse, a count or
+ *      q_heads * head_dim, kv_heads * head_dim >= 2^31.
+ *      Limits: head_dim % 8 == 0 and head_dim <= SM_ROPE_APPEND_MAX_HEAD_DIM (256); rot_dim <= head_dim and rot_dim %
+ *      SM_ROPE_APPEND_ROT_DIM_MULTIPLE (16) == 0; with a cache, page_size within sm_attn_decode_*'s limits: a power of two from
+ *      SM_ATTN_DECODE_MIN_PAGE_SIZE (16) to SM_ATTN_DECODE_MAX_PAGE_SIZE (128); style is SM_ROPE_NEOX or SM_ROPE_INTERLEAVED; rows of
+ *      every 16-bit operand 16-byte aligned (pointer and pitches % 8 == 0); rows of cs 16-byte aligned (pointer, ldcs % 4 == 0) when a
+ *      table is given.  What is not read is not checked: ldko without Ko; ldkv, page_stride, ldbt, num_pages, page_size and max_pages
+ *      without a cache; cs, ldcs and max_pos with rot_dim == 0.
+ *      Status, decided before any device work, in this order: a null Q, K, V or Qo; exactly one of Kc / Vc null; Kc null together
+ *      with Ko null; a null block_table with a cache; positions and seq_lens both null; cs null with rot_dim > 0; style not one of the
+ *      two; a pitch below its extent (ldq, ldqo >= q_heads * head_dim; ldk, ldv, ldko, ldkv >= kv_heads * head_dim; page_stride >=
+ *      page_size * ldkv; ldcs >= rot_dim; ldbt >= max_pages); rot_dim > head_dim; token_seq null with tokens > seqs; an aliasing not
+ *      listed above (two operands at one address other than Qo == Q and Ko == K, or those at different pitches):
+ *      SM_STATUS_INVALID_VALUE; then a dimension, a pitch, q_heads * head_dim, kv_heads * head_dim or max_pages * page_size >= 2^31,
+ *      then the limits above in the listed order: SM_STATUS_NOT_SUPPORTED (the text names the limit); tokens == 0, q_heads + kv_heads
+ *      == 0 or head_dim == 0: success, nothing enqueued.
+ *      Enqueue only: no allocation, no workspace, no atomics, no memset node, no synchronisation; capturable into a hipGraph, and a
+ *      captured graph stays valid when positions, token_seq, seq_lens and block_table change on the device.  Nothing outside Qo, Ko and
+ *      the addressed cache rows is written.
+ *      Not covered: an fp8 cache, multi-axis (M-RoPE) positions, per-head QK-norm, a 16-bit table, computing the table on the device,
+ *      incrementing seq_lens, a cache layout other than sm_attn_decode_*'s. */
+#define SM_ROPE_NEOX 0
+#define SM_ROPE_INTERLEAVED 1
+#define SM_ROPE_APPEND_MAX_HEAD_DIM 256
+#define SM_ROPE_APPEND_ROT_DIM_MULTIPLE 16
+#define SM_ROPE_APPEND_BLOCK_MAX_TOKENS 32768
+#define SM_ROPE_APPEND_FORM_INVALID 0
+#define SM_ROPE_APPEND_FORM_EMPTY 1
+#define SM_ROPE_APPEND_FORM_BLOCK 2
+#define SM_ROPE_APPEND_FORM_WAVE 3
+int sm_rope_append_f16(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc, void* Vc, const float* cs,
+                       const int* positions, const int* token_seq, const int* seq_lens, const int* block_table, size_t tokens, size_t seqs,
+                       size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim, size_t max_pos, size_t num_pages, size_t page_size,
+                       size_t max_pages, size_t ldq, size_t ldk, size_t ldv, size_t ldqo, size_t ldko, size_t ldkv, size_t page_stride,
+                       size_t ldcs, size_t ldbt, int style, sm_stream_t stream);
+int sm_rope_append_bf16(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc, void* Vc, const float* cs,
+                        const int* positions, const int* token_seq, const int* seq_lens, const int* block_table, size_t tokens, size_t seqs,
+                        size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim, size_t max_pos, size_t num_pages, size_t page_size,
+                        size_t max_pages, size_t ldq, size_t ldk, size_t ldv, size_t ldqo, size_t ldko, size_t ldkv, size_t page_stride,
+                        size_t ldcs, size_t ldbt, int style, sm_stream_t stream);
+int sm_rope_append_form(size_t tokens, size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim, int* form);
+
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +
  * sm_spmma_f32 to fp32 accumulation order.  Needs k % 32 == 0, n % 4 == 0, 16-byte aligned rows. */

@@ -206,6 +206,10 @@ for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_attn_decode_" + _sfx16] = [_c_ptr] * 8 + [_c_size] * 13 + [_c_f, _c_ptr]
 _SIGS["sm_attn_decode_workspace_size"] = [_c_size] * 5 + [ctypes.POINTER(_c_size)]
 _SIGS["sm_attn_decode_form"] = [_c_size] * 6 + [ctypes.POINTER(_c_i)]
+# RoPE + paged KV-cache append (rope_append.hip)
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_rope_append_" + _sfx16] = [_c_ptr] * 12 + [_c_size] * 19 + [_c_i, _c_ptr]
+_SIGS["sm_rope_append_form"] = [_c_size] * 5 + [ctypes.POINTER(_c_i)]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -1066,6 +1070,112 @@ def attn_decode(q, k_cache, v_cache, block_table, seq_lens, scale=None, out=None
               _dev(workspace) if workspace is not None else None, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages,
               ldq, ldkv, page_stride, ldbt, ldo, float(head_dim ** -0.5 if scale is None else scale), _stream()), "sm_attn_decode")
     return out
+
+
+# include/sparsifyme.h: SM_ROPE_APPEND_FORM_* (index = value), SM_ROPE_*, SM_ROPE_APPEND_* limits and the BLOCK / WAVE threshold
+ROPE_APPEND_FORMS = ("invalid", "empty", "block", "wave")
+ROPE_NEOX, ROPE_INTERLEAVED = 0, 1
+ROPE_APPEND_MAX_HEAD_DIM = 256
+ROPE_APPEND_ROT_DIM_MULTIPLE = 16
+ROPE_APPEND_BLOCK_MAX_TOKENS = 32768
+_ROPE_STYLES = {"neox": ROPE_NEOX, "interleaved": ROPE_INTERLEAVED, ROPE_NEOX: ROPE_NEOX, ROPE_INTERLEAVED: ROPE_INTERLEAVED}
+
+
+def rope_append_form(tokens, q_heads, kv_heads, head_dim, rot_dim):
+    """The name (ROPE_APPEND_FORMS) of the form rope_append runs -- sm_rope_append_form, the rule the entry points switch on.  Host only."""
+    form = _c_i(-1)
+    _check(lib().sm_rope_append_form(tokens, q_heads, kv_heads, head_dim, rot_dim, ctypes.byref(form)), "sm_rope_append_form")
+    return ROPE_APPEND_FORMS[form.value]
+
+
+def rope_table(max_pos, rot_dim, base=10000.0, device=None):
+    """The plain RoPE table rope_append reads: float32 [max_pos][rot_dim], row p = cos(p * theta_j) for j < rot_dim / 2, then sin(p * theta_j),
+    theta_j = base ** (-2 j / rot_dim); evaluated in float64 on the host and rounded once to float32.  A set-up op, once per model: a scaled
+    (linear, NTK, YaRN, llama-3) table is the caller's to build in the same layout."""
+    import numpy as np
+    torch = _t()
+    if rot_dim % 2 != 0 or rot_dim < 0 or max_pos < 0:
+        raise SparsifymeError("rope_table: rot_dim is even, max_pos and rot_dim are not negative")
+    half = rot_dim // 2
+    theta = np.float64(base) ** (-2.0 * np.arange(half, dtype=np.float64) / max(rot_dim, 1))
+    ang = np.arange(max_pos, dtype=np.float64)[:, None] * theta[None, :]
+    t = torch.from_numpy(np.concatenate([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32))
+    return t if device is None else t.to(device)
+
+
+def rope_append(q, k, v, cs, block_table=None, k_cache=None, v_cache=None, positions=None, token_seq=None, seq_lens=None, rot_dim=None, style="neox",
+                q_out=None, k_out=None):
+    """RoPE on every Q and K head and the append of K and V to the paged cache, in one launch (sm_rope_append_*).  q: [tokens][q_heads][head_dim],
+    k, v: [tokens][kv_heads][head_dim], float16 / bfloat16 with contiguous heads (any row pitch: column slices of a fused QKV output); cs: the
+    float32 table [max_pos][rot_dim] (rope_table; any row pitch), or None with rot_dim 0; rot_dim: cs.shape[1] when None.  k_cache, v_cache:
+    [num_pages][page_size][kv_heads][head_dim] in attn_decode's layout with block_table int32 [seqs][max_pages], or all three None (then k_out is
+    required).  positions, token_seq: int32 [tokens] or None; seq_lens: int32 [seqs] or None -- positions None takes seq_lens[s] - 1, token_seq
+    None takes token i as sequence i (the decode step).  style: "neox" or "interleaved".  q_out: None means in place (q itself); k_out: None means
+    not written, k itself is the in-place update.  Returns q_out."""
+    torch = _t()
+    what = "rope_append"
+    sfx = _quant_src_sfx(q, what)
+    if style not in _ROPE_STYLES:
+        raise SparsifymeError(f"{what}: style is 'neox' or 'interleaved'")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise SparsifymeError(f"{what}: q is [tokens][q_heads][head_dim], k and v are [tokens][kv_heads][head_dim]")
+    tokens, q_heads, head_dim = q.shape
+    kv_heads = k.shape[1]
+    if tuple(k.shape) != (tokens, kv_heads, head_dim) or tuple(v.shape) != tuple(k.shape) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise SparsifymeError(f"{what}: k and v are [tokens][kv_heads][head_dim] of q's dtype")
+    if q_out is None:
+        q_out = q
+    for name, t, heads in (("q", q, q_heads), ("k", k, kv_heads), ("v", v, kv_heads), ("q_out", q_out, q_heads), ("k_out", k_out, kv_heads)):
+        if t is not None and (t.dtype != q.dtype or tuple(t.shape) != (tokens, heads, head_dim) or (head_dim > 1 and t.stride(2) != 1) or
+                              (heads > 1 and t.stride(1) != head_dim)):
+            raise SparsifymeError(f"{what}: {name} is [tokens][heads][head_dim] of one dtype with contiguous heads (any row pitch)")
+    if cs is None:
+        if rot_dim not in (None, 0):
+            raise SparsifymeError(f"{what}: rot_dim > 0 needs the table cs")
+        rot_dim, max_pos, ldcs = 0, 0, 0
+    else:
+        if cs.dim() != 2 or cs.dtype != torch.float32 or (cs.shape[1] > 1 and cs.stride(1) != 1):
+            raise SparsifymeError(f"{what}: cs is float32 [max_pos][rot_dim] with contiguous rows (any row pitch)")
+        max_pos = cs.shape[0]
+        rot_dim = cs.shape[1] if rot_dim is None else rot_dim
+        if rot_dim > cs.shape[1]:
+            raise SparsifymeError(f"{what}: rot_dim exceeds the table's row")
+        ldcs = cs.stride(0) if max_pos > 1 else max(cs.stride(0), cs.shape[1])
+    pitch = lambda t, d, least: t.stride(d) if t.shape[d] > 1 else max(t.stride(d), least)
+    row = lambda t, heads: pitch(t, 0, heads * head_dim)
+    num_pages = page_size = max_pages = ldkv = page_stride = ldbt = 0
+    seqs = None
+    if (k_cache is None) != (v_cache is None) or (k_cache is None) != (block_table is None):
+        raise SparsifymeError(f"{what}: k_cache, v_cache and block_table are given together, or not at all")
+    if k_cache is not None:
+        if k_cache.dim() != 4 or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype or \
+                tuple(k_cache.shape[2:]) != (kv_heads, head_dim) or v_cache.stride() != k_cache.stride():
+            raise SparsifymeError(f"{what}: the caches are [num_pages][page_size][kv_heads][head_dim] of q's dtype, one shape and the same strides")
+        if (head_dim > 1 and k_cache.stride(3) != 1) or (kv_heads > 1 and k_cache.stride(2) != head_dim):
+            raise SparsifymeError(f"{what}: a cache token is [kv_heads][head_dim], contiguous")
+        num_pages, page_size = k_cache.shape[:2]
+        if block_table.dim() != 2 or block_table.dtype != torch.int32 or (block_table.shape[1] > 1 and block_table.stride(1) != 1):
+            raise SparsifymeError(f"{what}: block_table is int32 [seqs][max_pages] with contiguous rows")
+        seqs, max_pages = block_table.shape
+        ldkv = pitch(k_cache, 1, kv_heads * head_dim)
+        page_stride = pitch(k_cache, 0, page_size * ldkv)
+        ldbt = pitch(block_table, 0, max_pages)
+    for name, t in (("positions", positions), ("token_seq", token_seq)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (tokens,) or not t.is_contiguous()):
+            raise SparsifymeError(f"{what}: {name} is a contiguous int32 [tokens]")
+    if seq_lens is not None:
+        if seq_lens.dtype != torch.int32 or seq_lens.dim() != 1 or not seq_lens.is_contiguous() or (seqs is not None and seq_lens.shape[0] != seqs):
+            raise SparsifymeError(f"{what}: seq_lens is a contiguous int32 [seqs]")
+        seqs = seq_lens.shape[0]
+    if seqs is None:
+        seqs = tokens                  # no cache and no lengths: the sequence ids address nothing
+    ptr = lambda t: _dev(t) if t is not None else None
+    fn = getattr(lib(), "sm_rope_append_" + sfx)
+    _check(fn(_dev(q), _dev(k), _dev(v), _dev(q_out), ptr(k_out), ptr(k_cache), ptr(v_cache), ptr(cs) if rot_dim else None, ptr(positions), ptr(token_seq),
+              ptr(seq_lens), ptr(block_table), tokens, seqs, q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages, page_size, max_pages,
+              row(q, q_heads), row(k, kv_heads), row(v, kv_heads), row(q_out, q_heads), row(k_out, kv_heads) if k_out is not None else 0, ldkv, page_stride,
+              ldcs, ldbt, _ROPE_STYLES[style], _stream()), "sm_rope_append")
+    return q_out
 
 
 def quantize_compress24_fp8(A, blob, row_scale, rows, k, fmt_dtype, lda=None):
