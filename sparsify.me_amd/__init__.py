@@ -1011,6 +1011,32 @@ ATTN_DECODE_MAX_GROUP = 16
 ATTN_DECODE_MAX_CONTEXT = 2 ** 31 - 1
 
 
+def _pitch(t, d, least):
+    """the stride of dimension d, or -- one entry, its stride says nothing -- at least the extent"""
+    return t.stride(d) if t.shape[d] > 1 else max(t.stride(d), least)
+
+
+def _heads3(what, name, t, dtype, shape):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or (shape[2] > 1 and t.stride(2) != 1) or (shape[1] > 1 and t.stride(1) != shape[2]):
+        raise SparsifymeError(f"{what}: {name} is [rows][heads][head_dim] = {list(shape)} of one dtype with contiguous heads (any row pitch)")
+
+
+def _paged_cache(what, k_cache, v_cache, block_table, dtype, kv_heads, head_dim):
+    """The paged KV cache as attn_decode and rope_append take it (csrc/paged_kv.h), checked; returns (num_pages, page_size, max_pages, seqs,
+    ldkv, page_stride, ldbt)."""
+    if k_cache.dim() != 4 or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.dtype != dtype or v_cache.dtype != dtype or \
+            tuple(k_cache.shape[2:]) != (kv_heads, head_dim) or v_cache.stride() != k_cache.stride():
+        raise SparsifymeError(f"{what}: the caches are [num_pages][page_size][kv_heads][head_dim] of q's dtype, one shape and the same strides")
+    if (head_dim > 1 and k_cache.stride(3) != 1) or (kv_heads > 1 and k_cache.stride(2) != head_dim):
+        raise SparsifymeError(f"{what}: a cache token is [kv_heads][head_dim], contiguous")
+    if block_table.dim() != 2 or block_table.dtype != _t().int32 or (block_table.shape[1] > 1 and block_table.stride(1) != 1):
+        raise SparsifymeError(f"{what}: block_table is int32 [seqs][max_pages] with contiguous rows")
+    num_pages, page_size = k_cache.shape[:2]
+    seqs, max_pages = block_table.shape
+    ldkv = _pitch(k_cache, 1, kv_heads * head_dim)
+    return num_pages, page_size, max_pages, seqs, ldkv, _pitch(k_cache, 0, page_size * ldkv), _pitch(block_table, 0, max_pages)
+
+
 def attn_decode_form(seqs, q_heads, kv_heads, head_dim, page_size, max_pages):
     """The name (ATTN_DECODE_FORMS) of the form attn_decode runs -- sm_attn_decode_form, the rule the entry points switch on.  Host only."""
     form = _c_i(-1)
@@ -1033,34 +1059,22 @@ def attn_decode(q, k_cache, v_cache, block_table, seq_lens, scale=None, out=None
     [seqs][q_heads], or None; workspace: a uint8 tensor of attn_decode_workspace_size bytes (allocated when None and the form is split).
     Returns out."""
     torch = _t()
-    sfx = _quant_src_sfx(q, "attn_decode")
-    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4 or block_table.dim() != 2 or seq_lens.dim() != 1:
-        raise SparsifymeError("attn_decode: q is [seqs][q_heads][head_dim], the caches [num_pages][page_size][kv_heads][head_dim], block_table "
-                              "[seqs][max_pages], seq_lens [seqs]")
+    what = "attn_decode"
+    sfx = _quant_src_sfx(q, what)
+    if q.dim() != 3 or seq_lens.dim() != 1:
+        raise SparsifymeError(f"{what}: q is [seqs][q_heads][head_dim], seq_lens [seqs]")
     seqs, q_heads, head_dim = q.shape
-    num_pages, page_size, kv_heads, _ = k_cache.shape
-    max_pages = block_table.shape[1]
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.shape[3] != head_dim:
-        raise SparsifymeError("attn_decode: the caches have q's dtype and head_dim, and one shape")
-    if v_cache.stride() != k_cache.stride():
-        raise SparsifymeError("attn_decode: the caches have the same strides")
-    if block_table.dtype != torch.int32 or seq_lens.dtype != torch.int32 or block_table.shape[0] != seqs or seq_lens.shape[0] != seqs or \
-            not seq_lens.is_contiguous() or (max_pages > 1 and block_table.stride(1) != 1):
-        raise SparsifymeError("attn_decode: block_table is int32 [seqs][max_pages] with contiguous rows, seq_lens a contiguous int32 [seqs]")
+    kv_heads = k_cache.shape[2] if k_cache.dim() == 4 else 0
+    num_pages, page_size, max_pages, table_seqs, ldkv, page_stride, ldbt = _paged_cache(what, k_cache, v_cache, block_table, q.dtype, kv_heads, head_dim)
+    if table_seqs != seqs or seq_lens.dtype != torch.int32 or seq_lens.shape[0] != seqs or not seq_lens.is_contiguous():
+        raise SparsifymeError(f"{what}: block_table is [seqs][max_pages], seq_lens a contiguous int32 [seqs]")
     if out is None:
         out = torch.empty((seqs, q_heads, head_dim), dtype=q.dtype, device=q.device)
     for name, t in (("q", q), ("out", out)):
-        if t.dtype != q.dtype or tuple(t.shape) != (seqs, q_heads, head_dim) or (head_dim > 1 and t.stride(2) != 1) or (q_heads > 1 and t.stride(1) != head_dim):
-            raise SparsifymeError(f"attn_decode: {name} is [seqs][q_heads][head_dim] of one dtype with contiguous heads (any row pitch)")
-    if (head_dim > 1 and k_cache.stride(3) != 1) or (kv_heads > 1 and k_cache.stride(2) != head_dim):
-        raise SparsifymeError("attn_decode: a cache token is [kv_heads][head_dim], contiguous")
+        _heads3(what, name, t, q.dtype, (seqs, q_heads, head_dim))
     if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != (seqs, q_heads) or not lse.is_contiguous()):
-        raise SparsifymeError("attn_decode: lse is a contiguous float32 [seqs][q_heads]")
-    pitch = lambda t, d, least: t.stride(d) if t.shape[d] > 1 else max(t.stride(d), least)
-    ldq, ldo = pitch(q, 0, q_heads * head_dim), pitch(out, 0, q_heads * head_dim)
-    ldkv = pitch(k_cache, 1, kv_heads * head_dim)
-    page_stride = pitch(k_cache, 0, page_size * ldkv)
-    ldbt = pitch(block_table, 0, max_pages)
+        raise SparsifymeError(f"{what}: lse is a contiguous float32 [seqs][q_heads]")
+    ldq, ldo = _pitch(q, 0, q_heads * head_dim), _pitch(out, 0, q_heads * head_dim)
     need = attn_decode_workspace_size(seqs, q_heads, head_dim, page_size, max_pages)
     if workspace is None and need:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
@@ -1126,9 +1140,8 @@ def rope_append(q, k, v, cs, block_table=None, k_cache=None, v_cache=None, posit
     if q_out is None:
         q_out = q
     for name, t, heads in (("q", q, q_heads), ("k", k, kv_heads), ("v", v, kv_heads), ("q_out", q_out, q_heads), ("k_out", k_out, kv_heads)):
-        if t is not None and (t.dtype != q.dtype or tuple(t.shape) != (tokens, heads, head_dim) or (head_dim > 1 and t.stride(2) != 1) or
-                              (heads > 1 and t.stride(1) != head_dim)):
-            raise SparsifymeError(f"{what}: {name} is [tokens][heads][head_dim] of one dtype with contiguous heads (any row pitch)")
+        if t is not None:
+            _heads3(what, name, t, q.dtype, (tokens, heads, head_dim))
     if cs is None:
         if rot_dim not in (None, 0):
             raise SparsifymeError(f"{what}: rot_dim > 0 needs the table cs")
@@ -1141,25 +1154,13 @@ def rope_append(q, k, v, cs, block_table=None, k_cache=None, v_cache=None, posit
         if rot_dim > cs.shape[1]:
             raise SparsifymeError(f"{what}: rot_dim exceeds the table's row")
         ldcs = cs.stride(0) if max_pos > 1 else max(cs.stride(0), cs.shape[1])
-    pitch = lambda t, d, least: t.stride(d) if t.shape[d] > 1 else max(t.stride(d), least)
-    row = lambda t, heads: pitch(t, 0, heads * head_dim)
+    row = lambda t, heads: _pitch(t, 0, heads * head_dim)
     num_pages = page_size = max_pages = ldkv = page_stride = ldbt = 0
     seqs = None
     if (k_cache is None) != (v_cache is None) or (k_cache is None) != (block_table is None):
         raise SparsifymeError(f"{what}: k_cache, v_cache and block_table are given together, or not at all")
     if k_cache is not None:
-        if k_cache.dim() != 4 or tuple(v_cache.shape) != tuple(k_cache.shape) or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype or \
-                tuple(k_cache.shape[2:]) != (kv_heads, head_dim) or v_cache.stride() != k_cache.stride():
-            raise SparsifymeError(f"{what}: the caches are [num_pages][page_size][kv_heads][head_dim] of q's dtype, one shape and the same strides")
-        if (head_dim > 1 and k_cache.stride(3) != 1) or (kv_heads > 1 and k_cache.stride(2) != head_dim):
-            raise SparsifymeError(f"{what}: a cache token is [kv_heads][head_dim], contiguous")
-        num_pages, page_size = k_cache.shape[:2]
-        if block_table.dim() != 2 or block_table.dtype != torch.int32 or (block_table.shape[1] > 1 and block_table.stride(1) != 1):
-            raise SparsifymeError(f"{what}: block_table is int32 [seqs][max_pages] with contiguous rows")
-        seqs, max_pages = block_table.shape
-        ldkv = pitch(k_cache, 1, kv_heads * head_dim)
-        page_stride = pitch(k_cache, 0, page_size * ldkv)
-        ldbt = pitch(block_table, 0, max_pages)
+        num_pages, page_size, max_pages, seqs, ldkv, page_stride, ldbt = _paged_cache(what, k_cache, v_cache, block_table, q.dtype, kv_heads, head_dim)
     for name, t in (("positions", positions), ("token_seq", token_seq)):
         if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (tokens,) or not t.is_contiguous()):
             raise SparsifymeError(f"{what}: {name} is a contiguous int32 [tokens]")

@@ -8,7 +8,7 @@
 //           padded to 16, are the B operand (col l&15).  All K loads of a wave are issued before the first matrix instruction.
 //           D: lane l holds q row l&15 at tokens 4 (l>>4) + r of each 16-token tile.  A tile lies inside one page (tiles start on
 //           multiples of 16, pages hold at least 16 tokens): one block-table read per tile, and only for tiles that start below L.
-//   mask    by selection: a token at or beyond L, or of an absent page, is never loaded (its K and V fragments are zeros made in
+//   mask    by selection: a token at or beyond L, or of an absent page (paged_kv.h), is never loaded (its K and V fragments are zeros made in
 //           registers), its score is -inf and its p is +0.
 //   max     over the lane's registers, the four lane groups (xor 16, 32), the four waves (LDS).
 //   p       exp2f((s - m) log2e) by v_exp_f32, rounded to the 16-bit type; l sums the rounded values; p goes to LDS as [token][q row].
@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "mma_tile.h"
+#include "paged_kv.h"
 #include "quant_fp8.h"
 
 namespace sm {
@@ -36,13 +37,11 @@ constexpr unsigned AD_NT = AD_TPW / 16;    // 16-token tiles per wave
 constexpr float AD_LOG2E = 1.4426950408889634f;
 static_assert(AD_CHUNK % SM_ATTN_DECODE_MAX_PAGE_SIZE == 0 && AD_CHUNK % 64 == 0 && AD_CHUNK <= 512, "the chunk is a multiple of every page size");
 
-inline size_t ad_mul(size_t a, size_t b) { return (a != 0 && b > SIZE_MAX / a) ? SIZE_MAX : a * b; }  // saturating
 inline bool ad_head_dim_ok(size_t d) { return d == SM_ATTN_DECODE_MIN_HEAD_DIM || d == SM_ATTN_DECODE_MAX_HEAD_DIM; }
-inline bool ad_page_ok(size_t ps) { return ps >= SM_ATTN_DECODE_MIN_PAGE_SIZE && ps <= SM_ATTN_DECODE_MAX_PAGE_SIZE && (ps & (ps - 1)) == 0; }
-inline size_t ad_chunks(size_t page_size, size_t max_pages) { return ceil_div(ad_mul(page_size, max_pages), (size_t)AD_CHUNK); }
+inline size_t ad_chunks(size_t page_size, size_t max_pages) { return ceil_div(mul_sat(page_size, max_pages), (size_t)AD_CHUNK); }
 
 inline int attn_decode_form(size_t seqs, size_t q_heads, size_t kv_heads, size_t head_dim, size_t page_size, size_t max_pages) {
-  if (!ad_head_dim_ok(head_dim) || !ad_page_ok(page_size) || ad_mul(page_size, max_pages) > 0x7fffffffull) return SM_ATTN_DECODE_FORM_INVALID;
+  if (!ad_head_dim_ok(head_dim) || !kv_page_size_ok(page_size) || !kv_context_fits(page_size, max_pages)) return SM_ATTN_DECODE_FORM_INVALID;
   if (q_heads > 0 && (kv_heads == 0 || q_heads % kv_heads != 0 || q_heads / kv_heads > SM_ATTN_DECODE_MAX_GROUP)) return SM_ATTN_DECODE_FORM_INVALID;
   if (seqs == 0 || q_heads == 0) return SM_ATTN_DECODE_FORM_EMPTY;
   return page_size * max_pages <= AD_CHUNK ? SM_ATTN_DECODE_FORM_DIRECT : SM_ATTN_DECODE_FORM_SPLIT;
@@ -50,8 +49,8 @@ inline int attn_decode_form(size_t seqs, size_t q_heads, size_t kv_heads, size_t
 
 // the workspace: acc[seqs][q_heads][chunks][head_dim] fp32, then (m, l)[seqs][q_heads][chunks]; SIZE_MAX: it overflows
 inline size_t attn_decode_ws_bytes(size_t seqs, size_t q_heads, size_t head_dim, size_t page_size, size_t max_pages) {
-  if (ad_mul(page_size, max_pages) <= AD_CHUNK) return 0;
-  return ad_mul(ad_mul(ad_mul(seqs, q_heads), ad_chunks(page_size, max_pages)), ad_mul(head_dim + 2, sizeof(float)));
+  if (mul_sat(page_size, max_pages) <= AD_CHUNK) return 0;
+  return mul_sat(mul_sat(mul_sat(seqs, q_heads), ad_chunks(page_size, max_pages)), mul_sat(head_dim + 2, sizeof(float)));
 }
 
 struct AdArgs {
@@ -60,7 +59,7 @@ struct AdArgs {
   uint16_t* O;
   float *lse, *ws_acc, *ws_ml;  // lse: or null; ws_*: null in the DIRECT form
   size_t ldq, ldkv, page_stride, ldbt, ldo;
-  unsigned q_heads, kv_heads, group, num_pages, page_size, page_shift, cap, nchunks;
+  unsigned q_heads, kv_heads, group, num_pages, page_size, page_shift, cap, nchunks;  // bt .. cap: the PagedKv fields (paged_kv.h)
   float scale;
 };
 
@@ -98,16 +97,16 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AdArgs p) {
   }
   const unsigned row = lane & 15u, kg = lane >> 4, w0 = c0 + wave * AD_TPW;
 
-  // the page of every tile: read only for a tile that starts below L; absent: an id outside [0, num_pages)
+  // the page of every tile: read only for a tile that starts below L
   size_t pbase[AD_NT];
   bool present[AD_NT];
 #pragma unroll
   for (unsigned i = 0; i < AD_NT; ++i) {
     const unsigned t0 = w0 + i * 16u;
     int id = -1;
-    if (t0 < L) id = p.bt[(size_t)s * p.ldbt + (t0 >> p.page_shift)];
-    present[i] = id >= 0 && (unsigned)id < p.num_pages;
-    pbase[i] = present[i] ? (size_t)id * p.page_stride + (size_t)(t0 & (p.page_size - 1u)) * p.ldkv + (size_t)kvh * HD : 0;
+    if (t0 < L) id = kv_page_id(p, s, t0);
+    present[i] = kv_present(p, id);
+    pbase[i] = present[i] ? KV_OFFSET(p, id, t0) + (size_t)kvh * HD : 0;
   }
 
   // Q: the B operand, rows beyond the group are zeros
@@ -184,7 +183,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AdArgs p) {
     for (int e = 0; e < 8; ++e) acc[g][e] = 0.0f;
 #pragma unroll
   for (unsigned j = 0; j < NVS; ++j) {
-    float v[8];
+    float v[8];  // (unpack8 of quant_fp8.h, written out: through the call the CHUNK 512 build pairs the bf16 conversions differently, 118 -> 120 AGPRs)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       v[2 * e] = Src16<BF>::f32(vf[j][e] & 0xffffu);
@@ -280,8 +279,8 @@ static int attn_decode(const void* Q, const void* Kc, const void* Vc, const int*
     set_error("%s: invalid argument (null Q, Kc, Vc, block_table, seq_lens or O)", who);
     return SM_STATUS_INVALID_VALUE;
   }
-  if (ldq < ad_mul(q_heads, head_dim) || ldkv < ad_mul(kv_heads, head_dim) || page_stride < ad_mul(page_size, ldkv) || ldbt < max_pages ||
-      ldo < ad_mul(q_heads, head_dim)) {
+  if (ldq < mul_sat(q_heads, head_dim) || ldo < mul_sat(q_heads, head_dim) ||
+      !kv_pitches_ok(mul_sat(kv_heads, head_dim), page_size, max_pages, ldkv, page_stride, ldbt)) {
     set_error("%s: invalid argument (a pitch below its extent: ldq, ldo >= q_heads * head_dim, ldkv >= kv_heads * head_dim, page_stride >= page_size * ldkv, "
               "ldbt >= max_pages)", who);
     return SM_STATUS_INVALID_VALUE;
@@ -294,7 +293,7 @@ static int attn_decode(const void* Q, const void* Kc, const void* Vc, const int*
     set_error("%s: invalid argument (q_heads is not a multiple of kv_heads)", who);
     return SM_STATUS_INVALID_VALUE;
   }
-  const bool split = ad_mul(page_size, max_pages) > AD_CHUNK;
+  const bool split = mul_sat(page_size, max_pages) > AD_CHUNK;
   if (split && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3u) != 0 ||
                 workspace_bytes < attn_decode_ws_bytes(seqs, q_heads, head_dim, page_size, max_pages))) {
     set_error("%s: invalid argument (max_pages * page_size exceeds SM_ATTN_DECODE_CHUNK (%d): the SPLIT form needs a 4-byte aligned workspace of "
@@ -305,9 +304,9 @@ static int attn_decode(const void* Q, const void* Kc, const void* Vc, const int*
     set_error("%s: invalid argument (scale is NaN)", who);
     return SM_STATUS_INVALID_VALUE;
   }
-  const size_t lim = 0x7fffffffull;
-  if (seqs > lim || q_heads > lim || kv_heads > lim || head_dim > lim || num_pages > lim || page_size > lim || max_pages > lim || ldq > lim || ldkv > lim ||
-      page_stride > lim || ldbt > lim || ldo > lim || ad_mul(q_heads, head_dim) > lim || ad_mul(kv_heads, head_dim) > lim || ad_mul(seqs, q_heads) > lim) {
+  const size_t lim = KV_I32_MAX;
+  if (seqs > lim || q_heads > lim || kv_heads > lim || head_dim > lim || ldq > lim || ldo > lim || mul_sat(q_heads, head_dim) > lim ||
+      mul_sat(kv_heads, head_dim) > lim || mul_sat(seqs, q_heads) > lim || !kv_fields_fit(num_pages, page_size, max_pages, ldkv, page_stride, ldbt)) {
     set_error("%s: a dimension, a pitch, q_heads * head_dim, kv_heads * head_dim or seqs * q_heads exceeds 2^31-1", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
@@ -315,7 +314,7 @@ static int attn_decode(const void* Q, const void* Kc, const void* Vc, const int*
     set_error("%s: head_dim is SM_ATTN_DECODE_MIN_HEAD_DIM (%d) or SM_ATTN_DECODE_MAX_HEAD_DIM (%d)", who, SM_ATTN_DECODE_MIN_HEAD_DIM, SM_ATTN_DECODE_MAX_HEAD_DIM);
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (!ad_page_ok(page_size)) {
+  if (!kv_page_size_ok(page_size)) {
     set_error("%s: page_size is a power of two from SM_ATTN_DECODE_MIN_PAGE_SIZE (%d) to SM_ATTN_DECODE_MAX_PAGE_SIZE (%d)", who, SM_ATTN_DECODE_MIN_PAGE_SIZE,
               SM_ATTN_DECODE_MAX_PAGE_SIZE);
     return SM_STATUS_NOT_SUPPORTED;
@@ -324,20 +323,20 @@ static int attn_decode(const void* Q, const void* Kc, const void* Vc, const int*
     set_error("%s: the group q_heads / kv_heads exceeds SM_ATTN_DECODE_MAX_GROUP (%d)", who, SM_ATTN_DECODE_MAX_GROUP);
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (page_size * max_pages > lim) {
+  if (!kv_context_fits(page_size, max_pages)) {
     set_error("%s: max_pages * page_size exceeds 2^31-1 (SM_ATTN_DECODE_MAX_CONTEXT)", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (!aligned16(Q) || !aligned16(Kc) || !aligned16(Vc) || !aligned16(O) || ldq % 8 != 0 || ldkv % 8 != 0 || page_stride % 8 != 0 || ldo % 8 != 0) {
+  if (!aligned16(Q) || !aligned16(Kc) || !aligned16(Vc) || !aligned16(O) || ldq % 8 != 0 || ldo % 8 != 0 || !kv_rows_aligned16(ldkv, page_stride)) {
     set_error("%s: needs 16-byte aligned rows of Q, Kc, Vc and O (pointer, ldq, ldkv, page_stride, ldo %% 8 == 0)", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
   if (seqs == 0 || q_heads == 0) return SM_STATUS_SUCCESS;
   AdArgs a = {};
-  a.Q = (const uint16_t*)Q; a.K = (const uint16_t*)Kc; a.V = (const uint16_t*)Vc; a.bt = block_table; a.sl = seq_lens; a.O = (uint16_t*)O; a.lse = lse;
-  a.ldq = ldq; a.ldkv = ldkv; a.page_stride = page_stride; a.ldbt = ldbt; a.ldo = ldo;
-  a.q_heads = (unsigned)q_heads; a.kv_heads = (unsigned)kv_heads; a.group = (unsigned)(q_heads / kv_heads); a.num_pages = (unsigned)num_pages;
-  a.page_size = (unsigned)page_size; a.page_shift = (unsigned)__builtin_ctzll(page_size); a.cap = (unsigned)(page_size * max_pages);
+  a.Q = (const uint16_t*)Q; a.K = (const uint16_t*)Kc; a.V = (const uint16_t*)Vc; a.sl = seq_lens; a.O = (uint16_t*)O; a.lse = lse;
+  a.ldq = ldq; a.ldo = ldo;
+  paged_kv_fill(a, block_table, num_pages, page_size, max_pages, ldkv, page_stride, ldbt);
+  a.q_heads = (unsigned)q_heads; a.kv_heads = (unsigned)kv_heads; a.group = (unsigned)(q_heads / kv_heads);
   a.nchunks = (unsigned)(split ? ad_chunks(page_size, max_pages) : 1);
   a.scale = scale;
   if (split) {

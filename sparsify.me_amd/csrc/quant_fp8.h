@@ -13,7 +13,7 @@ struct F8Lim {
   static constexpr float fmax = FMT == SM_FP8_E4M3 ? 448.0f : 57344.0f;
 };
 
-// 16-bit source kinds: magnitude bits of the infinity, fp32 value of the bits
+// 16-bit source kinds: magnitude bits of the infinity, fp32 value of the bits, the bits of an fp32 value
 template <bool BF>
 struct Src16 {
   static constexpr uint32_t inf = BF ? 0x7f80u : 0x7c00u;
@@ -21,7 +21,27 @@ struct Src16 {
     if constexpr (BF) return __builtin_bit_cast(float, h << 16);
     else return (float)__builtin_bit_cast(_Float16, (uint16_t)h);
   }
+  static __device__ __forceinline__ uint32_t bits(float x) {  // rounded to nearest even, once
+    if constexpr (BF) return __builtin_bit_cast(uint16_t, (__bf16)x);
+    else return __builtin_bit_cast(uint16_t, (_Float16)x);
+  }
 };
+// four dwords of eight 16-bit elements <-> eight fp32 (rope_append.hip; attn_decode.hip writes the first out, see there)
+template <bool BF>
+__device__ __forceinline__ void unpack8(const u4 v, float (&x)[8]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    x[2 * e] = Src16<BF>::f32(v[e] & 0xffffu);
+    x[2 * e + 1] = Src16<BF>::f32(v[e] >> 16);
+  }
+}
+template <bool BF>
+__device__ __forceinline__ u4 pack8(const float (&y)[8]) {
+  u4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = Src16<BF>::bits(y[2 * e]) | (Src16<BF>::bits(y[2 * e + 1]) << 16);
+  return v;
+}
 
 // two fp32 -> two fp8 bytes in the low / high half of `old` (v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32: OCP encodings on
 // gfx950, round to nearest even, subnormals of the format included)

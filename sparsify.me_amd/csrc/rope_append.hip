@@ -12,8 +12,9 @@
 //   BLOCK  one four-wave workgroup per token, head step h = wave * (64 / L) + lane / L, stride 4 * (64 / L): the decode regime
 //   WAVE   one wave per token, four tokens per workgroup, stride 64 / L: the prefill regime
 // The token's sequence, position, table entry and page offset are wave-uniform: read once per wave and kept in SGPRs.  A padding token's
-// wave leaves before any load.  No LDS, no barrier, no atomics.
+// wave leaves before any load.  No LDS, no barrier, no atomics.  The cache, its page lookup and the geometry the entry point checks: paged_kv.h.
 #include "mma_tile.h"
+#include "paged_kv.h"
 #include "quant_fp8.h"
 
 namespace sm {
@@ -23,13 +24,11 @@ namespace sm {
 #define ROPE_APPEND_BLOCK_MAX SM_ROPE_APPEND_BLOCK_MAX_TOKENS
 #endif
 
-inline size_t ra_mul(size_t a, size_t b) { return (a != 0 && b > SIZE_MAX / a) ? SIZE_MAX : a * b; }  // saturating
-inline bool ra_page_ok(size_t ps) { return ps >= SM_ATTN_DECODE_MIN_PAGE_SIZE && ps <= SM_ATTN_DECODE_MAX_PAGE_SIZE && (ps & (ps - 1)) == 0; }
 inline bool ra_style_ok(int s) { return s == SM_ROPE_NEOX || s == SM_ROPE_INTERLEAVED; }
 
 inline int rope_append_form(size_t tokens, size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim) {
   const size_t lim = 0x7fffffffull;
-  if (tokens > lim || q_heads > lim || kv_heads > lim || ra_mul(q_heads, head_dim) > lim || ra_mul(kv_heads, head_dim) > lim) return SM_ROPE_APPEND_FORM_INVALID;
+  if (tokens > lim || q_heads > lim || kv_heads > lim || mul_sat(q_heads, head_dim) > lim || mul_sat(kv_heads, head_dim) > lim) return SM_ROPE_APPEND_FORM_INVALID;
   if (head_dim % 8 != 0 || head_dim > SM_ROPE_APPEND_MAX_HEAD_DIM || rot_dim > head_dim || rot_dim % 16 != 0) return SM_ROPE_APPEND_FORM_INVALID;
   if (tokens == 0 || q_heads + kv_heads == 0 || head_dim == 0) return SM_ROPE_APPEND_FORM_EMPTY;
   return tokens <= (size_t)ROPE_APPEND_BLOCK_MAX ? SM_ROPE_APPEND_FORM_BLOCK : SM_ROPE_APPEND_FORM_WAVE;
@@ -41,26 +40,10 @@ struct RaArgs {
   const float* cs;              // or null (rot == 0)
   const int *pos, *tseq, *sl, *bt;
   size_t ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride, ldcs, ldbt;
-  unsigned tokens, seqs, q_heads, kv_heads, hd, rot, half, pos_end, num_pages, page_size, page_shift, cap;
+  unsigned tokens, seqs, q_heads, kv_heads, hd, rot, half, pos_end, num_pages, page_size, page_shift, cap;  // the PagedKv fields (paged_kv.h): zeros without a cache
   unsigned items, rot_items, hps;  // items per head, how many of them rotate, heads per wave step (64 / items)
 };
 
-template <bool BF>
-__device__ __forceinline__ void ra_unpack(const u4 v, float (&x)[8]) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    x[2 * e] = Src16<BF>::f32(v[e] & 0xffffu);
-    x[2 * e + 1] = Src16<BF>::f32(v[e] >> 16);
-  }
-}
-template <bool BF>
-__device__ __forceinline__ u4 ra_pack(const float (&y)[8]) {
-  u4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    v[e] = (uint32_t)__builtin_bit_cast(uint16_t, to_elt<BF>(y[2 * e])) | ((uint32_t)__builtin_bit_cast(uint16_t, to_elt<BF>(y[2 * e + 1])) << 16);
-  return v;
-}
 // (y_a, y_b) of the definition in fp32: two products, each rounded, then the subtraction / the addition -- never an fma
 __device__ __forceinline__ void ra_rot(float xa, float xb, float c, float s, float& ya, float& yb) {
 #pragma clang fp contract(off)
@@ -86,10 +69,10 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const RaArgs p) {
   size_t slot = 0;
   bool append = false;
   if (p.Kc && s_ok && (unsigned)pos < p.cap) {
-    int pg = p.bt[(size_t)s * p.ldbt + ((unsigned)pos >> p.page_shift)];
+    int pg = kv_page_id(p, (size_t)s, (unsigned)pos);
     pg = __builtin_amdgcn_readfirstlane(pg);
-    append = pg >= 0 && (unsigned)pg < p.num_pages;
-    if (append) slot = (size_t)pg * p.page_stride + (size_t)((unsigned)pos & (p.page_size - 1u)) * p.ldkv;
+    append = kv_present(p, pg);
+    if (append) slot = KV_OFFSET(p, pg, (unsigned)pos);
   }
 
   // this lane's item: its piece(s) and its c / s values
@@ -148,18 +131,18 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const RaArgs p) {
     }
     if (rotate) {
       float xa[8], ya[8];
-      ra_unpack<BF>(a, xa);
+      unpack8<BF>(a, xa);
       if constexpr (NEOX) {
         float xb[8], yb[8];
-        ra_unpack<BF>(b, xb);
+        unpack8<BF>(b, xb);
 #pragma unroll
         for (int e = 0; e < 8; ++e) ra_rot(xa[e], xb[e], c[e], sn[e], ya[e], yb[e]);
-        b = ra_pack<BF>(yb);
+        b = pack8<BF>(yb);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) ra_rot(xa[2 * e], xa[2 * e + 1], c[e], sn[e], ya[2 * e], ya[2 * e + 1]);
       }
-      a = ra_pack<BF>(ya);
+      a = pack8<BF>(ya);
     }
     if (d1) *reinterpret_cast<u4*>(d1 + colA) = a;
     if (d2) *reinterpret_cast<u4*>(d2 + colA) = a;
@@ -214,8 +197,8 @@ static int rope_append(const void* Q, const void* K, const void* V, void* Qo, vo
     set_error("%s: invalid argument (style is SM_ROPE_NEOX or SM_ROPE_INTERLEAVED)", who);
     return SM_STATUS_INVALID_VALUE;
   }
-  const size_t qw = ra_mul(q_heads, head_dim), kw = ra_mul(kv_heads, head_dim);
-  if (ldq < qw || ldqo < qw || ldk < kw || ldv < kw || (Ko && ldko < kw) || (cache && (ldkv < kw || page_stride < ra_mul(page_size, ldkv) || ldbt < max_pages)) ||
+  const size_t qw = mul_sat(q_heads, head_dim), kw = mul_sat(kv_heads, head_dim);
+  if (ldq < qw || ldqo < qw || ldk < kw || ldv < kw || (Ko && ldko < kw) || (cache && !kv_pitches_ok(kw, page_size, max_pages, ldkv, page_stride, ldbt)) ||
       (table && ldcs < rot_dim)) {
     set_error("%s: invalid argument (a pitch below its extent: ldq, ldqo >= q_heads * head_dim; ldk, ldv, ldko, ldkv >= kv_heads * head_dim; page_stride >= "
               "page_size * ldkv; ldcs >= rot_dim; ldbt >= max_pages)", who);
@@ -239,10 +222,10 @@ static int rope_append(const void* Q, const void* K, const void* V, void* Qo, vo
       return SM_STATUS_INVALID_VALUE;
     }
   }
-  const size_t lim = 0x7fffffffull;
+  const size_t lim = KV_I32_MAX;
   if (tokens > lim || seqs > lim || q_heads > lim || kv_heads > lim || head_dim > lim || rot_dim > lim || (table && max_pos > lim) || ldq > lim || ldk > lim ||
       ldv > lim || ldqo > lim || (Ko && ldko > lim) || (table && ldcs > lim) || qw > lim || kw > lim ||
-      (cache && (num_pages > lim || page_size > lim || max_pages > lim || ldkv > lim || page_stride > lim || ldbt > lim || ra_mul(max_pages, page_size) > lim))) {
+      (cache && !(kv_fields_fit(num_pages, page_size, max_pages, ldkv, page_stride, ldbt) && kv_context_fits(page_size, max_pages)))) {
     set_error("%s: a dimension, a pitch, q_heads * head_dim, kv_heads * head_dim or max_pages * page_size exceeds 2^31-1", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
@@ -254,13 +237,13 @@ static int rope_append(const void* Q, const void* K, const void* V, void* Qo, vo
     set_error("%s: rot_dim is a multiple of SM_ROPE_APPEND_ROT_DIM_MULTIPLE (%d)", who, SM_ROPE_APPEND_ROT_DIM_MULTIPLE);
     return SM_STATUS_NOT_SUPPORTED;
   }
-  if (cache && !ra_page_ok(page_size)) {
+  if (cache && !kv_page_size_ok(page_size)) {
     set_error("%s: page_size is a power of two from SM_ATTN_DECODE_MIN_PAGE_SIZE (%d) to SM_ATTN_DECODE_MAX_PAGE_SIZE (%d)", who, SM_ATTN_DECODE_MIN_PAGE_SIZE,
               SM_ATTN_DECODE_MAX_PAGE_SIZE);
     return SM_STATUS_NOT_SUPPORTED;
   }
   if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(Qo) || !aligned16(Ko) || !aligned16(Kc) || !aligned16(Vc) || ldq % 8 != 0 || ldk % 8 != 0 ||
-      ldv % 8 != 0 || ldqo % 8 != 0 || (Ko && ldko % 8 != 0) || (cache && (ldkv % 8 != 0 || page_stride % 8 != 0))) {
+      ldv % 8 != 0 || ldqo % 8 != 0 || (Ko && ldko % 8 != 0) || (cache && !kv_rows_aligned16(ldkv, page_stride))) {
     set_error("%s: needs 16-byte aligned rows of Q, K, V, Qo, Ko, Kc and Vc (pointer, ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride %% 8 == 0)", who);
     return SM_STATUS_NOT_SUPPORTED;
   }
@@ -272,14 +255,12 @@ static int rope_append(const void* Q, const void* K, const void* V, void* Qo, vo
   if (form == SM_ROPE_APPEND_FORM_EMPTY) return SM_STATUS_SUCCESS;
   RaArgs a = {};
   a.Q = (const uint16_t*)Q; a.K = (const uint16_t*)K; a.V = (const uint16_t*)V; a.Qo = (uint16_t*)Qo; a.Ko = (uint16_t*)Ko; a.Kc = (uint16_t*)Kc; a.Vc = (uint16_t*)Vc;
-  a.cs = table ? cs : nullptr; a.pos = positions; a.tseq = token_seq; a.sl = seq_lens; a.bt = block_table;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldqo = ldqo; a.ldko = ldko; a.ldkv = ldkv; a.page_stride = page_stride; a.ldcs = ldcs; a.ldbt = ldbt;
+  a.cs = table ? cs : nullptr; a.pos = positions; a.tseq = token_seq; a.sl = seq_lens;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldqo = ldqo; a.ldko = ldko; a.ldcs = ldcs;
   a.tokens = (unsigned)tokens; a.seqs = (unsigned)seqs; a.q_heads = (unsigned)q_heads; a.kv_heads = (unsigned)kv_heads; a.hd = (unsigned)head_dim;
   a.rot = (unsigned)rot_dim; a.half = (unsigned)(rot_dim / 2);
   a.pos_end = table ? (unsigned)max_pos : 0x80000000u;  // without a table a token is padding only when pos < 0
-  if (cache) {
-    a.num_pages = (unsigned)num_pages; a.page_size = (unsigned)page_size; a.page_shift = (unsigned)__builtin_ctzll(page_size); a.cap = (unsigned)(max_pages * page_size);
-  }
+  if (cache) paged_kv_fill(a, block_table, num_pages, page_size, max_pages, ldkv, page_stride, ldbt);
   const bool neox = style == SM_ROPE_NEOX;
   a.rot_items = (unsigned)(neox ? rot_dim / 16 : rot_dim / 8);
   a.items = (unsigned)(neox ? rot_dim / 16 + (head_dim - rot_dim) / 8 : head_dim / 8);  // 1 .. 32

@@ -74,6 +74,7 @@ static int launch_grid(size_t nwg, unsigned threads, size_t lds_optin, size_t ld
 
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline size_t ceil_div(size_t x, size_t y) { return (x + y - 1) / y; }
+inline size_t mul_sat(size_t a, size_t b) { return (a != 0 && b > SIZE_MAX / a) ? SIZE_MAX : a * b; }  // saturating
 // Raise a device flag from one lane of a wave: the relaxed read first, so that once the flag is up the thousands of waves that also
 // found something do not queue their atomics on one address (an all-invalid 462 MB operand spent 100 us of a 214 us check pass there).
 #ifdef __HIPCC__

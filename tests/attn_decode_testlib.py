@@ -2,12 +2,14 @@
 reference) or in float32 (the restatement: chunked, p rounded to the 16-bit type, the chunks combined in ascending order, exp as exp2f of
 the argument times log2e) -- the bound the device is held to, the case table, the two exact classes (one-hot and uniform) and the cache
 builder of the GPU test (operands at moved bases with pitches above their extents, NaN in all padding, in every slot at or beyond L of a
-sequence's last page and in every page no table refers to, a NaN guard page in front of page 0 and behind the last page).
+sequence's last page and in every page no table refers to, a NaN guard page in front of page 0 and behind the last page).  The block
+table and the cache's place in its buffers are paged_kv_testlib's.
 
 16-bit values travel as uint16 bit patterns; `ty` is "f16" or "bf16".  The chunk is a parameter everywhere: the tests pass the package's."""
 import numpy as np
 
 from guard_testlib import NAN16, Guarded, f32_of, rne16, seed   # noqa: F401  (re-exported)
+from paged_kv_testlib import CacheLayout, PageTable
 
 TYPES = ["f16", "bf16"]
 MANT = {"f16": 10, "bf16": 7}
@@ -58,8 +60,7 @@ def case_id(c):
 
 
 class Problem:
-    """A case made concrete at a chunk size: lengths, the block table (permuted, not monotone; bad ids beyond the live columns), the set of
-    live (page, slot) pairs."""
+    """A case made concrete at a chunk size: lengths, the block table (paged_kv_testlib.PageTable), the set of live (page, slot) pairs."""
 
     def __init__(self, c, chunk, rng):
         self.c, self.chunk, self.ty = c, chunk, c["ty"]
@@ -71,26 +72,8 @@ class Problem:
         self.lens = [int(eval(x, env)) for x in c["lens"]]
         self.raw_lens = [int(eval(x, env)) for x in (c["raw"] or c["lens"])]
         self.seqs = len(self.lens)
-        assert all(0 <= L <= self.cap for L in self.lens)
-        need = [-(-L // self.ps) for L in self.lens]
-        self.num_pages = sum(need) + 3                       # three pages no table refers to
-        perm = rng.permutation(self.num_pages)
-        self.table = np.empty((self.seqs, self.max_pages), dtype=np.int32)
-        at = 0
-        for s in range(self.seqs):
-            row = perm[at:at + need[s]]
-            at += need[s]
-            if need[s] > 1 and not np.any(np.diff(row) < 0):
-                row = row[::-1]
-            if s == 1 and c["shared"]:
-                row = np.concatenate([self.table[0, :c["shared"]], row[c["shared"]:]])
-            bad = np.where(np.arange(self.max_pages - need[s]) % 2 == 0, -1, self.num_pages)       # never read
-            self.table[s] = np.concatenate([row, bad]).astype(np.int32)
-            assert need[s] < 2 or np.any(np.diff(row) < 0), "the page table is not monotone"
-        for s, col, which in c["absent"]:
-            col = int(eval(str(col), env))
-            assert col < need[s]
-            self.table[s, col] = -1 if which == "lo" else self.num_pages
+        pt = PageTable(self.lens, self.ps, self.max_pages, rng, [(s, int(eval(str(col), env)), which) for s, col, which in c["absent"]], c["shared"])
+        self.table, self.num_pages = pt.table, pt.num_pages
 
     def tokens(self, s):
         """(t, page, slot) of the present tokens of sequence s, ascending t"""
@@ -280,22 +263,17 @@ class Layout:
         self.pr, self.torch = pr, torch
         qh, hd, ty = pr.q_heads, pr.hd, pr.ty
         self.dt = {"f16": torch.float16, "bf16": torch.bfloat16}[ty]
-        self.ldq, self.ldo, self.ldkv, self.ldbt = qh * hd + 24, qh * hd + 8, pr.kvh * hd + 16, pr.max_pages + 3
-        self.page_stride = pr.ps * self.ldkv + 8
-        self.qbase, self.obase, self.kbase, self.tbase = 8, 16, 8 + self.page_stride, 5       # kbase: a guard page in front of page 0
+        self.ldq, self.ldo, self.qbase, self.obase = qh * hd + 24, qh * hd + 8, 8, 16
+        self.cache = cl = CacheLayout(pr.num_pages, pr.ps, pr.kvh * hd, pr.seqs, pr.max_pages)
         ar = np.arange
         iq = (self.qbase + ar(pr.seqs)[:, None] * self.ldq + ar(qh * hd)[None, :]).reshape(-1)
         self.Q = Guarded(self.qbase + pr.seqs * self.ldq + 16, NAN16[ty], np.uint16, self.qbase, idx=iq)
         self.Q.host[iq] = Q.reshape(-1)
         live = pr.live()
-        ikv = self.kbase + (ar(pr.num_pages)[:, None, None] * self.page_stride + ar(pr.ps)[None, :, None] * self.ldkv + ar(pr.kvh * hd)[None, None, :])
-        n_kv = self.kbase + (pr.num_pages + 1) * self.page_stride + 16                        # ... and one behind the last page
-        self.K, self.V = (Guarded(n_kv, NAN16[ty], np.uint16, self.kbase, idx=ikv[live].reshape(-1)) for _ in range(2))
+        self.K, self.V = (cl.cache_buffer(NAN16[ty], live) for _ in range(2))
         self.K.host[self.K.idx] = K.reshape(pr.num_pages, pr.ps, -1)[live].reshape(-1)
         self.V.host[self.V.idx] = V.reshape(pr.num_pages, pr.ps, -1)[live].reshape(-1)
-        it = (self.tbase + ar(pr.seqs)[:, None] * self.ldbt + ar(pr.max_pages)[None, :]).reshape(-1)
-        self.T = Guarded(self.tbase + pr.seqs * self.ldbt + 7, 0x7FFFFFF0, np.uint32, self.tbase, idx=it)
-        self.T.host[it] = pr.table.reshape(-1).view(np.uint32)
+        self.T = cl.table_buffer(pr.table)
         self.Ls = Guarded.around(np.array(pr.raw_lens, dtype=np.int32), 0x7FFFFFF0, 3, 5)
         self.io = (self.obase + ar(pr.seqs)[:, None] * self.ldo + ar(qh * hd)[None, :]).reshape(-1)
         self.O = Guarded(self.obase + pr.seqs * self.ldo + 16, SENT16, np.uint16, self.obase, idx=self.io)
@@ -308,8 +286,8 @@ class Layout:
         pr, tv = self.pr, lambda g, dt: g.dev.view(dt)
         q = tv(self.Q, self.dt).as_strided((pr.seqs, pr.q_heads, pr.hd), (self.ldq, pr.hd, 1), self.qbase)
         o = tv(self.O, self.dt).as_strided((pr.seqs, pr.q_heads, pr.hd), (self.ldo, pr.hd, 1), self.obase)
-        kv = [tv(g, self.dt).as_strided((pr.num_pages, pr.ps, pr.kvh, pr.hd), (self.page_stride, self.ldkv, pr.hd, 1), self.kbase) for g in (self.K, self.V)]
-        bt = self.T.dev.as_strided((pr.seqs, pr.max_pages), (self.ldbt, 1), self.tbase)
+        kv = [self.cache.cache_view(tv(g, self.dt), pr.kvh, pr.hd) for g in (self.K, self.V)]
+        bt = self.cache.table_view(self.T.dev)
         sl = self.Ls.dev[3:3 + pr.seqs]
         lse = self.lse.dev.view(self.torch.float32)[6:6 + pr.seqs * pr.q_heads].view(pr.seqs, pr.q_heads)
         return q, kv[0], kv[1], bt, sl, o, lse

@@ -6,19 +6,21 @@ pitch is above its extent, the type's NaN fills all input padding and the rows o
 sentinel -- unaddressed slots, unreferenced pages and a guard page in front of page 0 and behind the last page included -- so that an
 unclamped kernel writes where the check sees it instead of faulting.
 
-16-bit values travel as uint16 bit patterns; `ty` is "f16" or "bf16".  The page tables come from attn_decode_testlib.Problem."""
+16-bit values travel as uint16 bit patterns; `ty` is "f16" or "bf16".  The page tables and the cache's place in its buffers are
+paged_kv_testlib's."""
 from fractions import Fraction
 
 import numpy as np
 
 import attn_decode_testlib as al
 from guard_testlib import NAN16, SIGNED, Guarded, f32_of, is_nan16, rne16, seed   # noqa: F401  (re-exported)
+from paged_kv_testlib import BAD32, CacheLayout, PageTable
 
 TYPES = al.TYPES
 SALT = 0x209E
 SENT16 = al.SENT16
 NEOX, INTERLEAVED = "neox", "interleaved"
-FILL32 = 0x7FFFFFF0                      # around the int32 operands: a position / id that addresses nothing near
+FILL32 = BAD32                           # around the int32 operands: a position / id that addresses nothing near
 
 
 def canon16(bits, ty):
@@ -121,8 +123,8 @@ def wave_twin(block_max, extra):
 
 
 class Problem:
-    """A case made concrete: the tokens' sequence ids and positions as the call is given them, the page table (attn_decode_testlib.Problem:
-    permuted, not monotone, bad ids beyond the live columns), and per token what the definition makes of it."""
+    """A case made concrete: the tokens' sequence ids and positions as the call is given them, the page table (paged_kv_testlib.PageTable)
+    and per token what the definition makes of it."""
 
     def __init__(self, c, rng):
         self.c, self.ty = c, c["ty"]
@@ -133,8 +135,8 @@ class Problem:
         self.max_pages, self.max_pos = ev(c["max_pages"]), ev(c["max_pos"])
         lens = [ev(x) for x in c["lens"]]
         self.seqs = len(lens)
-        ap = al.Problem(al.case(self.ty, 64, 1, 1, self.ps, [str(x) for x in lens], str(self.max_pages), absent=c["absent"]), 256, rng)
-        self.table, self.num_pages, self.cap = ap.table, ap.num_pages, self.max_pages * self.ps
+        pt = PageTable(lens, self.ps, self.max_pages, rng, c["absent"])
+        self.table, self.num_pages, self.cap = pt.table, pt.num_pages, self.max_pages * self.ps
         self.cache = c["alias"] != "nocache"
         sp = c["spelling"]
         toks = c["toks"]
@@ -354,21 +356,15 @@ class Layout:
         self.iko = self.kobase + ar(T)[:, None] * self.ldko + ar(kvh * hd)[None, :]
         self.with_ko = alias in ("out", "nocache")
         # the cache: a sentinel everywhere, a guard page in front of page 0 and behind the last page
-        self.ldkv = kvh * hd + 16
-        self.page_stride = pr.ps * self.ldkv + 8
-        self.kbase = 8 + self.page_stride
-        n_kv = self.kbase + (pr.num_pages + 1) * self.page_stride + 16
-        self.Kc, self.Vc = (Guarded(n_kv, SENT16, np.uint16, self.kbase, size=0) for _ in range(2))
+        self.cache = cl = CacheLayout(pr.num_pages, pr.ps, kvh * hd, pr.seqs, pr.max_pages)
+        self.Kc, self.Vc = (cl.cache_buffer(SENT16) for _ in range(2))
         # the table, NaN in its padding, and the int32 operands between guards
         self.ldcs, self.csbase = pr.rot + 4, 4
         self.cs = Guarded(self.csbase + pr.max_pos * self.ldcs + 8, 0x7FC00000, np.uint32, self.csbase, size=0)
         if pr.rot:
             ics = self.csbase + ar(pr.max_pos)[:, None] * self.ldcs + ar(pr.rot)[None, :]
             self.cs.host[ics.reshape(-1)] = np.ascontiguousarray(cs[:, :pr.rot], dtype=np.float32).view(np.uint32).reshape(-1)
-        self.ldbt, self.tbase = pr.max_pages + 3, 5
-        self.T = Guarded(self.tbase + pr.seqs * self.ldbt + 7, FILL32, np.uint32, self.tbase, size=0)
-        it = self.tbase + ar(pr.seqs)[:, None] * self.ldbt + ar(pr.max_pages)[None, :]
-        self.T.host[it.reshape(-1)] = pr.table.reshape(-1).view(np.uint32)
+        self.T = cl.table_buffer(pr.table)
         wrap = lambda x: None if x is None else Guarded.around(x.astype(np.int32), FILL32, 3, 5)
         self.P, self.S, self.L = wrap(pr.positions), wrap(pr.token_seq), wrap(pr.seq_lens)
         self.bufs = {"qkv": self.X, "Qo": self.Qo, "Ko": self.Ko, "Kc": self.Kc, "Vc": self.Vc, "cs": self.cs, "block_table": self.T, "positions": self.P,
@@ -395,7 +391,7 @@ class Layout:
         app = np.array([i for i in live if pr.slot[i] is not None], dtype=np.int64)
         if app.size:
             pg, sl = np.array([pr.slot[i] for i in app], dtype=np.int64).T
-            at = (self.kbase + pg[:, None] * self.page_stride + sl[:, None] * self.ldkv + ar(kvh * hd)[None, :]).reshape(-1)
+            at = cl.rows(pg, sl).reshape(-1)
             put("Kc", at, ev["kbits"][app].reshape(-1))
             put("Vc", at, V[app].reshape(-1))
 
@@ -411,9 +407,8 @@ class Layout:
             if self.with_ko:
                 kw["k_out"] = tv(self.Ko).as_strided((pr.tokens, pr.kvh, pr.hd), (self.ldko, pr.hd, 1), self.kobase)
         if pr.cache:
-            kw["k_cache"], kw["v_cache"] = (tv(g).as_strided((pr.num_pages, pr.ps, pr.kvh, pr.hd), (self.page_stride, self.ldkv, pr.hd, 1), self.kbase)
-                                            for g in (self.Kc, self.Vc))
-            kw["block_table"] = self.T.dev.as_strided((pr.seqs, pr.max_pages), (self.ldbt, 1), self.tbase)
+            kw["k_cache"], kw["v_cache"] = (self.cache.cache_view(tv(g), pr.kvh, pr.hd) for g in (self.Kc, self.Vc))
+            kw["block_table"] = self.cache.table_view(self.T.dev)
         for name, g, n in (("positions", self.P, pr.tokens), ("token_seq", self.S, pr.tokens), ("seq_lens", self.L, pr.seqs)):
             if g is not None:
                 kw[name] = g.dev[3:3 + n]

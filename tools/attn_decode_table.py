@@ -9,9 +9,7 @@ are skipped); bf16; every sequence holds the full context, pages scattered by a 
   sdpa0   scaled_dot_product_attention alone on an already contiguous, already expanded cache: the route's floor.
   copy    a torch copy that moves the call's algorithmic bytes -- the live K and V rows once -- in the same process: the call is reported as
           a multiple of it and as a fraction of 8 TB/s.
-Two clocks, the columns alternated in one process on warm buffers, median of five:
-  graph   N calls captured into one hipGraph, 3 replays between two events: device time, no host launch cost;
-  eager   N calls between two events, launch gaps included.  N is 20, fewer where a call moves more than 256 MB.
+The graph and the eager clock of tools/tablelib.py, median of five; N is 20, fewer where a call moves more than 256 MB.
 Expectation, stated before the run: no cell is behind the torch route, and at batch >= 8 and context >= 4096 the call is within a small factor
 of the copy.  Nothing is required of the numbers: the table is the finding.
 
@@ -21,34 +19,22 @@ of the copy.  Nothing is required of the numbers: the table is the finding.
   python tools/attn_decode_table.py > profiles/attn_decode_table.txt
 """
 import argparse
-import csv
 import ctypes
 import os
-import statistics
-import subprocess
 import sys
+
+from tablelib import CALLS, REPEATS, REPLAYS, attn_shapes as shapes, clocks, medians, paged_cache, probe_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CONTEXTS = [1024, 4096, 16384, 32768]
 BATCHES = [1, 8, 64]
 CHUNKS = [128, 256, 512]
-REPEATS, CALLS, REPLAYS = 5, 20, 3
-
-
-def shapes():
-    with open(os.path.join(ROOT, "datasets", "attn_shapes.csv")) as fh:
-        rows = [r for r in csv.reader(l for l in fh if not l.startswith("#"))]
-    return [tuple(int(x) for x in r) for r in rows[1:]]
 
 
 def forced_lib(chunk):
     """tools/probes/libattn_decode_c<chunk>.so: attn_decode.hip alone with the chunk forced; built when it is not there"""
-    path = os.path.join(ROOT, "tools", "probes", f"libattn_decode_c{chunk}.so")
-    if not os.path.exists(path):
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", f"-DATTN_DECODE_CHUNK={chunk}",
-                        os.path.join(ROOT, "tools", "probes", "attn_decode_forced.hip"), "-o", path], check=True)
-    L = ctypes.CDLL(path)
+    L = probe_lib(f"attn_decode_c{chunk}", "attn_decode_forced.hip", f"ATTN_DECODE_CHUNK={chunk}")
     L.sm_attn_decode_bf16.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_size_t] * 13 + [ctypes.c_float, ctypes.c_void_p]
     L.sm_attn_decode_bf16.restype = ctypes.c_int
     L.sm_attn_decode_workspace_size.argtypes = [ctypes.c_size_t] * 5 + [ctypes.POINTER(ctypes.c_size_t)]
@@ -72,53 +58,12 @@ def main():
     dev = "cuda:0"
     half_mem = torch.cuda.get_device_properties(0).total_memory // 2
 
-    def timed(run):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        n = run()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1000.0 / n
-
-    def clocks(fn, calls):
-        """(graph, eager): two callables, each returns us per call of fn"""
-        fn()
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            for _ in range(calls):
-                fn()
-        g.replay()
-        torch.cuda.synchronize()
-
-        def graph():
-            for _ in range(REPLAYS):
-                g.replay()
-            return calls * REPLAYS
-
-        def eager():
-            for _ in range(calls):
-                fn()
-            return calls
-        return (lambda: timed(graph)), (lambda: timed(eager))
-
-    def medians(cols):
-        runs = {k: [] for k in cols}
-        for _ in range(REPEATS):
-            for k, f in cols.items():
-                runs[k].append(f())
-        return {k: statistics.median(v) for k, v in runs.items()}, runs
-
     def operands(batch, ctx, qh, kvh, hd, ps):
         gen = torch.Generator(device=dev).manual_seed(batch * 131 + ctx)
         max_pages = ctx // ps
-        num_pages = batch * max_pages
-        o = dict(q=torch.randn((batch, qh, hd), generator=gen, device=dev, dtype=torch.bfloat16),
-                 K=torch.empty((num_pages, ps, kvh, hd), device=dev, dtype=torch.bfloat16).normal_(generator=gen),
-                 V=torch.empty((num_pages, ps, kvh, hd), device=dev, dtype=torch.bfloat16).normal_(generator=gen),
-                 bt=torch.randperm(num_pages, generator=gen, device=dev).to(torch.int32).view(batch, max_pages),
-                 sl=torch.full((batch,), ctx, dtype=torch.int32, device=dev), out=torch.empty((batch, qh, hd), device=dev, dtype=torch.bfloat16))
+        q = torch.randn((batch, qh, hd), generator=gen, device=dev, dtype=torch.bfloat16)
+        K, V, bt = paged_cache(gen, dev, batch, max_pages, ps, kvh, hd, normal=True)
+        o = dict(q=q, K=K, V=V, bt=bt, sl=torch.full((batch,), ctx, dtype=torch.int32, device=dev), out=torch.empty((batch, qh, hd), device=dev, dtype=torch.bfloat16))
         need = pkg.attn_decode_workspace_size(batch, qh, hd, ps, max_pages)
         o["ws"] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
         return o

@@ -5,9 +5,7 @@ tokens; 8 experts top-2, 64 experts top-8, 256 experts top-8; bf16 and fp32 logi
   gate    one sm_moe_gate_* launch: softmax renormalised over the top_k; sigmoid with a selection bias, renormalised, scale 2.5.
   torch   softmax: softmax(x.float()) -> topk -> w / w.sum -> ids.to(int32);
           sigmoid: sigmoid(x.float()) -> + bias -> topk -> gather -> w / w.sum -> * 2.5 -> ids.to(int32).
-Two clocks per side, the two sides alternated in one process on warm buffers, median of five:
-  graph   20 calls captured into one hipGraph, 3 replays between two events: device time, no host launch cost;
-  eager   20 calls between two events, launch gaps included: what a caller outside a graph pays.
+The graph and the eager clock of tools/tablelib.py per side, 20 calls each, median of five.
 Behind the cells: the gate at 8 experts top-2 as a share of the bf16 balanced block of profiles/moe_block_table.txt (t_block, graph replay)
 at the same token count.  Nothing is required of the numbers: the table is the finding.
 
@@ -15,14 +13,14 @@ at the same token count.  Nothing is required of the numbers: the table is the f
 """
 import os
 import re
-import statistics
 import sys
+
+from tablelib import CALLS, REPEATS, REPLAYS, clocks, medians
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 TOKENS = [16, 128, 1024, 8192]
 ROUTERS = [(8, 2), (64, 8), (256, 8)]
-REPEATS, CALLS, REPLAYS = 5, 20, 3
 
 
 def block_times():
@@ -43,37 +41,6 @@ def main():
     pkg = ge.load_package()
     pkg.device_check()
     dev = "cuda:0"
-
-    def timed(run):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        n = run()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1000.0 / n
-
-    def clocks(fn):
-        """(graph, eager): two callables, each returns us per call of fn"""
-        fn()
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            for _ in range(CALLS):
-                fn()
-        g.replay()
-        torch.cuda.synchronize()
-
-        def graph():
-            for _ in range(REPLAYS):
-                g.replay()
-            return CALLS * REPLAYS
-
-        def eager():
-            for _ in range(CALLS):
-                fn()
-            return CALLS
-        return (lambda: timed(graph)), (lambda: timed(eager))
 
     blocks = block_times()
     print(f"# {pkg.version()}; us per gate, median of {REPEATS} alternated repeats (graph: {CALLS} calls x {REPLAYS} replays; eager: {CALLS} calls, "
@@ -108,11 +75,7 @@ def main():
                     cols = {}
                     cols["gate graph"], cols["gate eager"] = clocks(gate)
                     cols["torch graph"], cols["torch eager"] = clocks(ops)
-                    runs = {k: [] for k in cols}
-                    for _ in range(REPEATS):
-                        for k, f in cols.items():
-                            runs[k].append(f())
-                    med = {k: statistics.median(v) for k, v in runs.items()}
+                    med, runs = medians(cols)
                     name = {torch.bfloat16: "bf16", torch.float32: "fp32"}[ty]
                     cell = f"{name} {experts} experts top-{top_k} {scoring} tokens {tokens} [{pkg.moe_gate_form(tokens, experts, top_k)}]"
                     text = "  ".join(f"{k} {med[k]:.1f} [{min(runs[k]):.1f} .. {max(runs[k]):.1f}]" for k in cols)

@@ -9,9 +9,7 @@ tokens; hidden 128 with tokens * 32 rows (the per-head norm), 4096 and 8192; bf1
   torch   the torch spelling: add, fp32 pow / mean / rsqrt / mul / mul, cast; for the third variant sm_quantize_rows_fp8_bf16 on top.
   copy    a torch copy that moves the call's algorithmic bytes (reads + writes), in the same process: the call is reported as a multiple
           of it, not against a fixed TB/s.
-Two clocks per side, the columns alternated in one process on warm buffers, median of five:
-  graph   20 calls captured into one hipGraph, 3 replays between two events: device time, no host launch cost;
-  eager   20 calls between two events, launch gaps included: what a caller outside a graph pays.
+The graph and the eager clock of tools/tablelib.py per side, 20 calls each, median of five.
 Expectation, stated before the run: one launch against five to eight is ahead in every cell, and at 8192 tokens the call sits within a
 small factor of the copy of its own bytes.  Nothing is required of the numbers: the table is the finding.
 
@@ -22,9 +20,9 @@ builds of the rmsnorm translation unit alone (tools/probes/rmsnorm_forced.hip, t
 """
 import ctypes
 import os
-import statistics
-import subprocess
 import sys
+
+from tablelib import CALLS, REPEATS, REPLAYS, clocks, medians, probe_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -33,17 +31,12 @@ HIDDENS = [128, 4096, 8192]
 VARIANTS = ["norm", "add+norm", "add+norm+e4m3"]
 FORCED_HIDDENS = [256, 512, 768, 1024, 1536, 2048, 2560, 3072, 4096, 4608]
 FORCED_TOKENS = [16, 1024, 8192]
-REPEATS, CALLS, REPLAYS = 5, 20, 3
 EPS = 1e-6
 
 
 def forced_lib(name, lanes_max):
     """tools/probes/librmsnorm_<name>.so: rmsnorm.hip alone with the threshold forced; built when it is not there"""
-    path = os.path.join(ROOT, "tools", "probes", f"librmsnorm_{name}.so")
-    if not os.path.exists(path):
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", f"-DRMSNORM_LANES_MAX={lanes_max}",
-                        os.path.join(ROOT, "tools", "probes", "rmsnorm_forced.hip"), "-o", path], check=True)
-    L = ctypes.CDLL(path)
+    L = probe_lib(f"rmsnorm_{name}", "rmsnorm_forced.hip", f"RMSNORM_LANES_MAX={lanes_max}")
     L.sm_rmsnorm_bf16.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_size_t] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
     L.sm_rmsnorm_bf16.restype = ctypes.c_int
     return L
@@ -56,44 +49,6 @@ def main():
     pkg.device_check()
     dev = "cuda:0"
     f8 = torch.float8_e4m3fn
-
-    def timed(run):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        n = run()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1000.0 / n
-
-    def clocks(fn):
-        """(graph, eager): two callables, each returns us per call of fn"""
-        fn()
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            for _ in range(CALLS):
-                fn()
-        g.replay()
-        torch.cuda.synchronize()
-
-        def graph():
-            for _ in range(REPLAYS):
-                g.replay()
-            return CALLS * REPLAYS
-
-        def eager():
-            for _ in range(CALLS):
-                fn()
-            return CALLS
-        return (lambda: timed(graph)), (lambda: timed(eager))
-
-    def medians(cols):
-        runs = {k: [] for k in cols}
-        for _ in range(REPEATS):
-            for k, f in cols.items():
-                runs[k].append(f())
-        return {k: statistics.median(v) for k, v in runs.items()}, runs
 
     def operands(rows, hidden):
         gen = torch.Generator().manual_seed(rows * 131 + hidden)

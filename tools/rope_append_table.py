@@ -10,9 +10,7 @@ the column slices of one fused QKV buffer, Q rotated in place, pages scattered b
   copy    a torch copy that moves the call's algorithmic bytes once -- Q, K and V read, Qo and the two cache rows written, the table row
           read: tokens * (2 q_heads + 4 kv_heads) * head_dim * 2 + tokens * head_dim * 4 bytes, half of them as the copy's source -- in
           the same process: the call is reported as a multiple of it and as a fraction of 8 TB/s.
-Two clocks, the columns alternated in one process on warm buffers, median of five:
-  graph   N calls captured into one hipGraph, 3 replays between two events: device time, no host launch cost;
-  eager   N calls between two events, launch gaps included.  N is 200 up to 64 tokens, 50 up to 2048, 20 above.
+The graph and the eager clock of tools/tablelib.py, median of five; N is 200 up to 64 tokens, 50 up to 2048, 20 above.
 Expectation, stated before the run: no cell is behind the torch route (the route is eight to ten launches and several passes over the
 tokens), and at 1024 tokens and above the call is within a small factor -- two to three times -- of the copy; below that the call is one
 launch's latency, which the copy's launch shares.  Nothing is required of the numbers: the table is the finding.
@@ -23,12 +21,11 @@ forced to BLOCK and to WAVE (tools/probes/rope_append_forced.hip), token counts 
   python tools/rope_append_table.py > profiles/rope_append_table.txt
 """
 import argparse
-import csv
 import ctypes
 import os
-import statistics
-import subprocess
 import sys
+
+from tablelib import REPEATS, REPLAYS, attn_shapes as shapes, clocks, medians, paged_cache, probe_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -36,7 +33,6 @@ DECODE = [1, 8, 64]
 PREFILL = [1024, 8192]
 FORCED_TOKENS = [1, 64, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768]
 FORCED = {"block": 2147483647, "wave": 0}
-REPEATS, REPLAYS = 5, 3
 PREFILL_SEQS = 4
 
 
@@ -45,19 +41,9 @@ def calls_for(tokens):
     return 200 if tokens <= 64 else 50 if tokens <= 2048 else 20
 
 
-def shapes():
-    with open(os.path.join(ROOT, "datasets", "attn_shapes.csv")) as fh:
-        rows = [r for r in csv.reader(l for l in fh if not l.startswith("#"))]
-    return [tuple(int(x) for x in r) for r in rows[1:]]
-
-
 def forced_lib(which):
     """tools/probes/librope_append_<which>.so: rope_append.hip alone with the threshold forced; built when it is not there"""
-    path = os.path.join(ROOT, "tools", "probes", f"librope_append_{which}.so")
-    if not os.path.exists(path):
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic",
-                        f"-DROPE_APPEND_BLOCK_MAX={FORCED[which]}", os.path.join(ROOT, "tools", "probes", "rope_append_forced.hip"), "-o", path], check=True)
-    L = ctypes.CDLL(path)
+    L = probe_lib(f"rope_append_{which}", "rope_append_forced.hip", f"ROPE_APPEND_BLOCK_MAX={FORCED[which]}")
     L.sm_rope_append_bf16.argtypes = [ctypes.c_void_p] * 12 + [ctypes.c_size_t] * 19 + [ctypes.c_int, ctypes.c_void_p]
     L.sm_rope_append_bf16.restype = ctypes.c_int
     L.sm_rope_append_form.argtypes = [ctypes.c_size_t] * 5 + [ctypes.POINTER(ctypes.c_int)]
@@ -79,44 +65,6 @@ def main():
     pkg.device_check()
     dev = "cuda:0"
 
-    def timed(run):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        n = run()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1000.0 / n
-
-    def clocks(fn, calls):
-        """(graph, eager): two callables, each returns us per call of fn"""
-        fn()
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            for _ in range(calls):
-                fn()
-        g.replay()
-        torch.cuda.synchronize()
-
-        def graph():
-            for _ in range(REPLAYS):
-                g.replay()
-            return calls * REPLAYS
-
-        def eager():
-            for _ in range(calls):
-                fn()
-            return calls
-        return (lambda: timed(graph)), (lambda: timed(eager))
-
-    def medians(cols):
-        runs = {k: [] for k in cols}
-        for _ in range(REPEATS):
-            for k, f in cols.items():
-                runs[k].append(f())
-        return {k: statistics.median(v) for k, v in runs.items()}, runs
-
     def operands(tokens, decode, qh, kvh, hd, ps):
         """decode: `tokens` sequences of 1000 + 37 s tokens, the call appends the last; prefill: PREFILL_SEQS sequences share the tokens"""
         gen = torch.Generator(device=dev).manual_seed(tokens * 131 + qh)
@@ -134,10 +82,9 @@ def main():
         W = (qh + 2 * kvh) * hd
         qkv = torch.randn((tokens, W), generator=gen, device=dev, dtype=torch.bfloat16)
         cut = lambda a, b: qkv[:, a * hd:b * hd].view(tokens, b - a, hd)
+        K, V, bt = paged_cache(gen, dev, seqs, max_pages, ps, kvh, hd, normal=False)
         return dict(qkv=qkv, q=cut(0, qh), k=cut(qh, qh + kvh), v=cut(qh + kvh, qh + 2 * kvh), seqs=seqs, max_pages=max_pages, num_pages=num_pages,
-                    K=torch.zeros((num_pages, ps, kvh, hd), device=dev, dtype=torch.bfloat16), V=torch.zeros((num_pages, ps, kvh, hd), device=dev, dtype=torch.bfloat16),
-                    bt=torch.randperm(num_pages, generator=gen, device=dev).to(torch.int32).view(seqs, max_pages), sl=lens, pos=pos, seq=seq,
-                    cs=pkg.rope_table(max_pages * ps, hd, device=dev))
+                    K=K, V=V, bt=bt, sl=lens, pos=pos, seq=seq, cs=pkg.rope_table(max_pages * ps, hd, device=dev))
 
     def moved_bytes(tokens, qh, kvh, hd):
         return tokens * (2 * qh + 4 * kvh) * hd * 2 + tokens * hd * 4
