@@ -136,6 +136,22 @@ struct spmma_fns_f16 {
     return sm_rope_append_f16(Q, K, V, Qo, Ko, Kc, Vc, cs, positions, token_seq, seq_lens, bt, tokens, seqs, q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages,
                               page_size, max_pages, ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride, ldcs, ldbt, style, st);
   }
+  static int attn_decode_kv8_on(const void* Q, const void* Kc8, const void* Vc8, const float* Ksc, const float* Vsc, const int* bt, const int* sl, void* O,
+                                float* lse, void* ws, std::size_t ws_bytes, std::size_t seqs, std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim,
+                                std::size_t num_pages, std::size_t page_size, std::size_t max_pages, std::size_t ldq, std::size_t ldkv, std::size_t page_stride,
+                                std::size_t scale_page_stride, std::size_t ldbt, std::size_t ldo, float scale, int fmt, hipStream_t st) {
+    return sm_attn_decode_kv8_f16(Q, Kc8, Vc8, Ksc, Vsc, bt, sl, O, lse, ws, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages, ldq, ldkv,
+                                  page_stride, scale_page_stride, ldbt, ldo, scale, fmt, st);
+  }
+  static int rope_append_kv8_on(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc8, void* Vc8, float* Ksc, float* Vsc, const float* cs,
+                                const int* positions, const int* token_seq, const int* seq_lens, const int* bt, std::size_t tokens, std::size_t seqs,
+                                std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t rot_dim, std::size_t max_pos, std::size_t num_pages,
+                                std::size_t page_size, std::size_t max_pages, std::size_t ldq, std::size_t ldk, std::size_t ldv, std::size_t ldqo, std::size_t ldko,
+                                std::size_t ldkv, std::size_t page_stride, std::size_t scale_page_stride, std::size_t ldcs, std::size_t ldbt, int style, int fmt,
+                                hipStream_t st) {
+    return sm_rope_append_kv8_f16(Q, K, V, Qo, Ko, Kc8, Vc8, Ksc, Vsc, cs, positions, token_seq, seq_lens, bt, tokens, seqs, q_heads, kv_heads, head_dim, rot_dim,
+                                  max_pos, num_pages, page_size, max_pages, ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride, scale_page_stride, ldcs, ldbt, style, fmt, st);
+  }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;  // fp32 operands only (the 16-bit types run on the sparse matrix instruction as they are)
   }
@@ -229,6 +245,22 @@ struct spmma_fns_bf16 {  // bfloat16 (extension): same blob and rules, v_smfmac_
                             std::size_t page_stride, std::size_t ldcs, std::size_t ldbt, int style, hipStream_t st) {
     return sm_rope_append_bf16(Q, K, V, Qo, Ko, Kc, Vc, cs, positions, token_seq, seq_lens, bt, tokens, seqs, q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages,
                               page_size, max_pages, ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride, ldcs, ldbt, style, st);
+  }
+  static int attn_decode_kv8_on(const void* Q, const void* Kc8, const void* Vc8, const float* Ksc, const float* Vsc, const int* bt, const int* sl, void* O,
+                                float* lse, void* ws, std::size_t ws_bytes, std::size_t seqs, std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim,
+                                std::size_t num_pages, std::size_t page_size, std::size_t max_pages, std::size_t ldq, std::size_t ldkv, std::size_t page_stride,
+                                std::size_t scale_page_stride, std::size_t ldbt, std::size_t ldo, float scale, int fmt, hipStream_t st) {
+    return sm_attn_decode_kv8_bf16(Q, Kc8, Vc8, Ksc, Vsc, bt, sl, O, lse, ws, ws_bytes, seqs, q_heads, kv_heads, head_dim, num_pages, page_size, max_pages, ldq, ldkv,
+                                  page_stride, scale_page_stride, ldbt, ldo, scale, fmt, st);
+  }
+  static int rope_append_kv8_on(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc8, void* Vc8, float* Ksc, float* Vsc, const float* cs,
+                                const int* positions, const int* token_seq, const int* seq_lens, const int* bt, std::size_t tokens, std::size_t seqs,
+                                std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t rot_dim, std::size_t max_pos, std::size_t num_pages,
+                                std::size_t page_size, std::size_t max_pages, std::size_t ldq, std::size_t ldk, std::size_t ldv, std::size_t ldqo, std::size_t ldko,
+                                std::size_t ldkv, std::size_t page_stride, std::size_t scale_page_stride, std::size_t ldcs, std::size_t ldbt, int style, int fmt,
+                                hipStream_t st) {
+    return sm_rope_append_kv8_bf16(Q, K, V, Qo, Ko, Kc8, Vc8, Ksc, Vsc, cs, positions, token_seq, seq_lens, bt, tokens, seqs, q_heads, kv_heads, head_dim, rot_dim,
+                                  max_pos, num_pages, page_size, max_pages, ldq, ldk, ldv, ldqo, ldko, ldkv, page_stride, scale_page_stride, ldcs, ldbt, style, fmt, st);
   }
   static int fused_split(void*, void*, void*, std::size_t, std::size_t, std::size_t, std::size_t, int, void*, std::size_t, float, float) {
     return SM_STATUS_NOT_SUPPORTED;
@@ -759,6 +791,41 @@ int rope_append(const type_t* d_Q, const type_t* d_K, const type_t* d_V, type_t*
                                                    q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages, page_size, max_pages, ldq ? ldq : qw, ldk ? ldk : kw,
                                                    ldv ? ldv : kw, ldqo ? ldqo : qw, ldko ? ldko : kw, kv, page_stride ? page_stride : page_size * kv,
                                                    ldcs ? ldcs : rot_dim, ldbt ? ldbt : max_pages, style, stream);
+}
+// Extension (fp16 / bfloat16 Q, K, V; an fp8 cache): rope_append with the append going to the fp8 paged cache (sm_rope_append_kv8_*): d_Kc8 /
+// d_Vc8 are fp8 bytes [num_pages][page_size][kv_heads][head_dim] in fmt (SM_FP8_E4M3 / SM_FP8_E5M2, one for both), d_Ksc / d_Vsc fp32
+// [num_pages][kv_heads][page_size]: every appended K head (rotated, rounded to type_t) and V head is one row of quantize_rows_fp8 -- its
+// bytes go to the token's cache row, its row_scale to [page][head][slot].  All four are required; d_Qo and d_Ko are bit for bit
+// rope_append's.  head_dim 64 or 128.  Pitches as rope_append (ldkv, page_stride in bytes, % 16 == 0), scale_page_stride 0 = kv_heads *
+// page_size.  Enqueue only.
+template <typename type_t>
+int rope_append_kv8(const type_t* d_Q, const type_t* d_K, const type_t* d_V, type_t* d_Qo, type_t* d_Ko, void* d_Kc8, void* d_Vc8, float* d_Ksc, float* d_Vsc,
+                    const float* d_cs, const int* d_positions, const int* d_token_seq, const int* d_seq_lens, const int* d_block_table, std::size_t tokens,
+                    std::size_t seqs, std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t rot_dim, std::size_t max_pos,
+                    std::size_t num_pages, std::size_t page_size, std::size_t max_pages, int fmt, int style = SM_ROPE_NEOX, hipStream_t stream = nullptr,
+                    std::size_t ldq = 0, std::size_t ldk = 0, std::size_t ldv = 0, std::size_t ldqo = 0, std::size_t ldko = 0, std::size_t ldkv = 0,
+                    std::size_t page_stride = 0, std::size_t scale_page_stride = 0, std::size_t ldcs = 0, std::size_t ldbt = 0) {
+  const std::size_t qw = q_heads * head_dim, kw = kv_heads * head_dim, kv = ldkv ? ldkv : kw;
+  return detail::spmma_fns<type_t>::rope_append_kv8_on(d_Q, d_K, d_V, d_Qo, d_Ko, d_Kc8, d_Vc8, d_Ksc, d_Vsc, d_cs, d_positions, d_token_seq, d_seq_lens, d_block_table,
+                                                       tokens, seqs, q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages, page_size, max_pages, ldq ? ldq : qw,
+                                                       ldk ? ldk : kw, ldv ? ldv : kw, ldqo ? ldqo : qw, ldko ? ldko : kw, kv,
+                                                       page_stride ? page_stride : page_size * kv, scale_page_stride ? scale_page_stride : kv_heads * page_size,
+                                                       ldcs ? ldcs : rot_dim, ldbt ? ldbt : max_pages, style, fmt, stream);
+}
+// Extension: attn_decode over that cache (sm_attn_decode_kv8_*): element d of a token is fp32(byte) * scale[page][head][slot]; d_Q, d_O, d_lse,
+// the workspace (attn_decode_workspace_size serves this call too), scale and the pitches as attn_decode.  Enqueue only.
+template <typename type_t>
+int attn_decode_kv8(const type_t* d_Q, const void* d_Kc8, const void* d_Vc8, const float* d_Ksc, const float* d_Vsc, const int* d_block_table,
+                    const int* d_seq_lens, type_t* d_O, std::size_t seqs, std::size_t q_heads, std::size_t kv_heads, std::size_t head_dim, std::size_t num_pages,
+                    std::size_t page_size, std::size_t max_pages, int fmt, void* workspace = nullptr, std::size_t workspace_bytes = 0, float* d_lse = nullptr,
+                    float scale = 0.0f, hipStream_t stream = nullptr, std::size_t ldq = 0, std::size_t ldkv = 0, std::size_t page_stride = 0,
+                    std::size_t scale_page_stride = 0, std::size_t ldbt = 0, std::size_t ldo = 0) {
+  const std::size_t kv = ldkv ? ldkv : kv_heads * head_dim;
+  return detail::spmma_fns<type_t>::attn_decode_kv8_on(d_Q, d_Kc8, d_Vc8, d_Ksc, d_Vsc, d_block_table, d_seq_lens, d_O, d_lse, workspace, workspace_bytes, seqs, q_heads,
+                                                       kv_heads, head_dim, num_pages, page_size, max_pages, ldq ? ldq : q_heads * head_dim, kv,
+                                                       page_stride ? page_stride : page_size * kv, scale_page_stride ? scale_page_stride : kv_heads * page_size,
+                                                       ldbt ? ldbt : max_pages, ldo ? ldo : q_heads * head_dim,
+                                                       scale != 0.0f ? scale : 1.0f / std::sqrt((float)head_dim), fmt, stream);
 }
 // The plain RoPE table on the host: cs[p][j] = cos(p theta_j), cs[p][rot_dim / 2 + j] = sin(p theta_j), theta_j = base^(-2 j / rot_dim),
 // evaluated in double and rounded once to float.  A set-up op, once per model; a scaled table is the caller's to build in this layout.

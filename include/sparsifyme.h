@@ -822,6 +822,7 @@ int sm_rmsnorm_form(size_t hidden, int* form);
  *      and block_table change on the device.  Nothing outside O, lse and the workspace is written.
  *      Not covered: more than one query token per sequence, a sliding window, soft-capping, ALiBi, an fp8 cache, head dimensions
  *      other than the two, RoPE, the cache append, prefill. */
+/* (An fp8 cache is sm_attn_decode_kv8_*, after the append below; RoPE and the cache append are sm_rope_append_*.) */
 #define SM_ATTN_DECODE_CHUNK 256
 #define SM_ATTN_DECODE_MIN_HEAD_DIM 64
 #define SM_ATTN_DECODE_MAX_HEAD_DIM 128
@@ -901,7 +902,7 @@ int sm_attn_decode_form(size_t seqs, size_t q_heads, size_t kv_heads, size_t hea
  *      Enqueue only: no allocation, no workspace, no atomics, no memset node, no synchronisation; capturable into a hipGraph, and a
  *      captured graph stays valid when positions, token_seq, seq_lens and block_table change on the device.  Nothing outside Qo, Ko and
  *      the addressed cache rows is written.
- *      Not covered: an fp8 cache, multi-axis (M-RoPE) positions, per-head QK-norm, a 16-bit table, computing the table on the device,
+ *      Not covered: an fp8 cache (that is sm_rope_append_kv8_* below), multi-axis (M-RoPE) positions, per-head QK-norm, a 16-bit table, computing the table on the device,
  *      incrementing seq_lens, a cache layout other than sm_attn_decode_*'s. */
 #define SM_ROPE_NEOX 0
 #define SM_ROPE_INTERLEAVED 1
@@ -923,6 +924,91 @@ int sm_rope_append_bf16(const void* Q, const void* K, const void* V, void* Qo, v
                         size_t max_pages, size_t ldq, size_t ldk, size_t ldv, size_t ldqo, size_t ldko, size_t ldkv, size_t page_stride,
                         size_t ldcs, size_t ldbt, int style, sm_stream_t stream);
 int sm_rope_append_form(size_t tokens, size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim, int* form);
+
+/* ---- The fp8 paged KV cache (extension): the cache of sm_attn_decode_* and sm_rope_append_* held in OCP fp8 with one fp32 scale per
+ *      (token, kv head): half the cache bytes, twice the context in a given cache.  Written by sm_rope_append_kv8_*, read by
+ *      sm_attn_decode_kv8_*.
+ *      Bytes: Kc8 and Vc8 are fp8 bytes [num_pages][page_size][kv_heads][head_dim], token pitch ldkv, page pitch page_stride, both in
+ *      elements (= bytes).  fmt is SM_FP8_E4M3 or SM_FP8_E5M2; one fmt covers both caches.
+ *      Scales: Ksc and Vsc are fp32 [num_pages][kv_heads][page_size], page pitch scale_page_stride >= kv_heads * page_size: head-major
+ *      inside a page, so that the 16 scales of 16 consecutive tokens of a head are 64 contiguous bytes.
+ *      Meaning: element d of the token in (page, slot), kv head g, has the value fp32(byte) * Ksc[page][g][slot] (Vsc for V).
+ *      block_table, seq_lens, the page sizes and the ABSENT rule are the 16-bit cache's: a page whose id lies outside [0, num_pages) has
+ *      no bytes and no scales read or written, and no address is formed from its id.  head_dim is 64 or 128 in both calls: the reader
+ *      accepts nothing else.  Rows are 16-byte aligned: the four pointers, ldkv % 16 == 0, page_stride % 16 == 0, scale_page_stride % 4
+ *      == 0.
+ *
+ *      sm_rope_append_kv8_{f16,bf16}: sm_rope_append_* with the append going to the fp8 cache.  The arguments are sm_rope_append_*'s
+ *      with Kc8, Vc8, Ksc, Vsc in the place of Kc, Vc -- all four required: without an fp8 cache the 16-bit call is the one to use --,
+ *      scale_page_stride after page_stride and fmt after style.
+ *      Definition: everything sm_rope_append_* states about tokens, padding tokens, positions, the rotation, Qo, Ko and aliasing holds
+ *      unchanged; Qo and Ko are bit for bit what sm_rope_append_* writes.  Append, under sm_rope_append_*'s condition: let y[g][.] be
+ *      the rotated K head g already rounded to the 16-bit type (the bits Ko receives).  The cache receives exactly what
+ *      sm_quantize_rows_fp8_* gives for the row y[g][0 .. head_dim): Ksc[pg][g][pos_i % page_size] gets that row's row_scale and
+ *      Kc8[pg][pos_i % page_size][g] that row's bytes -- amax = max(max |y| over the finite elements, 2^-100), row_scale = amax / FMAX
+ *      and inv = FMAX / amax (two correctly rounded fp32 divisions), byte = rne_fmt(fp32(y) * inv) (one multiply), NaN -> 0x7f, +-inf ->
+ *      0x7f (e4m3) / 0x7c | sign (e5m2) by a select on the source bits; an all-zero row has row_scale 2^-100 / FMAX and zero bytes (-0
+ *      keeps its sign).  V is handled the same way from the bits of V (no rotation) into Vsc and Vc8.  A refused append (an absent page,
+ *      pos_i >= max_pages * page_size, s_i out of range) writes neither bytes nor scales; a padding token writes nothing at all.
+ *      Forms: sm_rope_append_form serves this call too (same rule, same threshold, same bits in both forms).
+ *      Limits: head_dim is SM_ATTN_DECODE_MIN_HEAD_DIM (64) or SM_ATTN_DECODE_MAX_HEAD_DIM (128); rot_dim, page_size, style and the rows
+ *      of Q, K, V, Qo, Ko and cs as in sm_rope_append_*; the rows of the byte and scale arrays as above.  What is not read is not
+ *      checked: ldko without Ko; cs, ldcs and max_pos with rot_dim == 0.
+ *      Status, decided before any device work, in this order: a null Q, K, V, Qo, Kc8, Vc8, Ksc or Vsc; a null block_table; positions
+ *      and seq_lens both null; cs null with rot_dim > 0; style not one of the two; a pitch below its extent (sm_rope_append_*'s list);
+ *      fmt not SM_FP8_E4M3 or SM_FP8_E5M2; scale_page_stride < kv_heads * page_size; rot_dim > head_dim; token_seq null with tokens >
+ *      seqs; an aliasing other than Qo == Q and Ko == K at equal pitches (among Q, K, V, Qo, Ko, Kc8, Vc8, Ksc, Vsc):
+ *      SM_STATUS_INVALID_VALUE; then a dimension, a pitch, q_heads * head_dim, kv_heads * head_dim or max_pages * page_size >= 2^31;
+ *      head_dim not 64 or 128; rot_dim % SM_ROPE_APPEND_ROT_DIM_MULTIPLE != 0; page_size; the 16-byte rows of Q, K, V, Qo and Ko; the
+ *      16-byte rows of Kc8, Vc8, Ksc and Vsc; the 16-byte rows of cs: SM_STATUS_NOT_SUPPORTED (the text names the limit); tokens == 0 or
+ *      q_heads + kv_heads == 0: success, nothing enqueued.
+ *      Enqueue only: one kernel node, no allocation, no workspace, no atomics, no memset node, no synchronisation; capturable into a
+ *      hipGraph, and a captured graph stays valid when positions, token_seq, seq_lens and block_table change on the device.  Nothing
+ *      outside Qo, Ko and the addressed cache rows and scales is written.
+ *
+ *      sm_attn_decode_kv8_{f16,bf16}: sm_attn_decode_* over the fp8 cache.  The arguments are sm_attn_decode_*'s with Ksc, Vsc after Vc8,
+ *      scale_page_stride after page_stride and fmt after scale.  Q and O are 16-bit, lse fp32, as there.  The form and the workspace are
+ *      functions of the geometry alone: sm_attn_decode_form and sm_attn_decode_workspace_size serve this call too.
+ *      Definition: sm_attn_decode_*'s, with two lines changed (k8, v8 the cache bytes, ks_t, vs_t the scales of token t and the head):
+ *        s_t = (dot_t * ks_t) * scale, with dot_t = sum_d fp32(q_d) * fp32(k8_t,d) in an order the definition does not fix, then the two
+ *          fp32 multiplies in that order
+ *        acc_c,d = sum_t (fp32(p_t) * vs_t) * fp32(v8_t,d): one rounded fp32 multiply per token, then the sum
+ *        l_c still sums the rounded p_t themselves.
+ *      The chunks, the rounding of p, the ascending combine, the masking by selection (the bytes AND the scales of a masked or absent
+ *      token are never loaded; the cache may hold NaN bytes and NaN scales there), L == 0, the clamp and the NaN behaviour are as stated
+ *      for sm_attn_decode_*.  The widening of a byte to Q's 16-bit type and to fp32 is exact: every e4m3 and e5m2 value is a value of
+ *      fp16 and of bf16.
+ *      Limits: sm_attn_decode_*'s, with the rows of the byte and scale arrays as above in the place of the rows of Kc and Vc.
+ *      Status, decided before any device work, in this order: a null Q, Kc8, Vc8, Ksc, Vsc, block_table, seq_lens or O; a pitch below
+ *      its extent; fmt not SM_FP8_E4M3 or SM_FP8_E5M2; scale_page_stride < kv_heads * page_size; kv_heads == 0 with q_heads > 0; q_heads
+ *      % kv_heads != 0; max_pages * page_size > CHUNK with a null, misaligned or short workspace; scale NaN: SM_STATUS_INVALID_VALUE;
+ *      then a dimension, a pitch, q_heads * head_dim, kv_heads * head_dim or seqs * q_heads >= 2^31; head_dim; page_size; the group; the
+ *      context; the 16-byte rows of Q and O; the 16-byte rows of Kc8, Vc8, Ksc and Vsc: SM_STATUS_NOT_SUPPORTED (the text names the
+ *      limit); seqs == 0 or q_heads == 0: success, nothing enqueued.
+ *      Enqueue only, capturable, and a captured graph stays valid when seq_lens and block_table change on the device, as
+ *      sm_attn_decode_*.  Nothing outside O, lse and the workspace is written.
+ *      Not covered: prefill attention, fp8 Q or P on the 1-byte matrix instruction, per-tensor or calibrated static scales, different
+ *      formats for K and V, head dimensions other than the two, converting a 16-bit cache in place. */
+int sm_rope_append_kv8_f16(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc8, void* Vc8, float* Ksc, float* Vsc,
+                           const float* cs, const int* positions, const int* token_seq, const int* seq_lens, const int* block_table,
+                           size_t tokens, size_t seqs, size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim, size_t max_pos,
+                           size_t num_pages, size_t page_size, size_t max_pages, size_t ldq, size_t ldk, size_t ldv, size_t ldqo, size_t ldko,
+                           size_t ldkv, size_t page_stride, size_t scale_page_stride, size_t ldcs, size_t ldbt, int style, int fmt,
+                           sm_stream_t stream);
+int sm_rope_append_kv8_bf16(const void* Q, const void* K, const void* V, void* Qo, void* Ko, void* Kc8, void* Vc8, float* Ksc, float* Vsc,
+                            const float* cs, const int* positions, const int* token_seq, const int* seq_lens, const int* block_table,
+                            size_t tokens, size_t seqs, size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim, size_t max_pos,
+                            size_t num_pages, size_t page_size, size_t max_pages, size_t ldq, size_t ldk, size_t ldv, size_t ldqo, size_t ldko,
+                            size_t ldkv, size_t page_stride, size_t scale_page_stride, size_t ldcs, size_t ldbt, int style, int fmt,
+                            sm_stream_t stream);
+int sm_attn_decode_kv8_f16(const void* Q, const void* Kc8, const void* Vc8, const float* Ksc, const float* Vsc, const int* block_table,
+                           const int* seq_lens, void* O, float* lse, void* workspace, size_t workspace_bytes, size_t seqs, size_t q_heads,
+                           size_t kv_heads, size_t head_dim, size_t num_pages, size_t page_size, size_t max_pages, size_t ldq, size_t ldkv,
+                           size_t page_stride, size_t scale_page_stride, size_t ldbt, size_t ldo, float scale, int fmt, sm_stream_t stream);
+int sm_attn_decode_kv8_bf16(const void* Q, const void* Kc8, const void* Vc8, const float* Ksc, const float* Vsc, const int* block_table,
+                            const int* seq_lens, void* O, float* lse, void* workspace, size_t workspace_bytes, size_t seqs, size_t q_heads,
+                            size_t kv_heads, size_t head_dim, size_t num_pages, size_t page_size, size_t max_pages, size_t ldq, size_t ldkv,
+                            size_t page_stride, size_t scale_page_stride, size_t ldbt, size_t ldo, float scale, int fmt, sm_stream_t stream);
 
 /* fp32 form: the STRIP rule applied to the A fragments in registers of the dense fp32 MFMA kernel (there is no fp32 sparse
  * matrix instruction).  Equals sm_gemm_rowmajor_f32 of the STRIP-pruned A bit for bit; agrees with sm_compress24_f32 +

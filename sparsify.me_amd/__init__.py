@@ -210,6 +210,10 @@ _SIGS["sm_attn_decode_form"] = [_c_size] * 6 + [ctypes.POINTER(_c_i)]
 for _sfx16 in ("f16", "bf16"):
     _SIGS["sm_rope_append_" + _sfx16] = [_c_ptr] * 12 + [_c_size] * 19 + [_c_i, _c_ptr]
 _SIGS["sm_rope_append_form"] = [_c_size] * 5 + [ctypes.POINTER(_c_i)]
+# the fp8 paged KV cache: quantising append (rope_append_kv8.hip) and decode attention (attn_decode_kv8.hip)
+for _sfx16 in ("f16", "bf16"):
+    _SIGS["sm_rope_append_kv8_" + _sfx16] = [_c_ptr] * 14 + [_c_size] * 20 + [_c_i, _c_i, _c_ptr]
+    _SIGS["sm_attn_decode_kv8_" + _sfx16] = [_c_ptr] * 10 + [_c_size] * 14 + [_c_f, _c_i, _c_ptr]
 _RET = {"sm_version": ctypes.c_char_p, "sm_last_error": ctypes.c_char_p}
 
 # every symbol include/sparsifyme.h declares (checked by tests/test_abi.py without a GPU)
@@ -1177,6 +1181,104 @@ def rope_append(q, k, v, cs, block_table=None, k_cache=None, v_cache=None, posit
               row(q, q_heads), row(k, kv_heads), row(v, kv_heads), row(q_out, q_heads), row(k_out, kv_heads) if k_out is not None else 0, ldkv, page_stride,
               ldcs, ldbt, _ROPE_STYLES[style], _stream()), "sm_rope_append")
     return q_out
+
+
+def _paged_cache8(what, k_cache, v_cache, k_scale, v_scale, block_table, kv_heads, head_dim):
+    """The fp8 paged KV cache as attn_decode_kv8 and rope_append_kv8 take it (csrc/paged_kv.h), checked: the byte tensors through _paged_cache
+    in their own fp8 dtype, the scales float32 [num_pages][kv_heads][page_size] with contiguous heads (any page pitch).  Returns _paged_cache's
+    tuple, then scale_page_stride and fmt."""
+    fmt = fp8_format(k_cache.dtype)
+    geo = _paged_cache(what, k_cache, v_cache, block_table, k_cache.dtype, kv_heads, head_dim)
+    num_pages, page_size = geo[0], geo[1]
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t.dtype != _t().float32 or tuple(t.shape) != (num_pages, kv_heads, page_size) or (page_size > 1 and t.stride(2) != 1) or \
+                (kv_heads > 1 and t.stride(1) != page_size) or t.stride() != k_scale.stride():
+            raise SparsifymeError(f"{what}: {name} is float32 [num_pages][kv_heads][page_size] with contiguous heads, both at the same strides")
+    return geo + (_pitch(k_scale, 0, kv_heads * page_size), fmt)
+
+
+def rope_append_kv8(q, k, v, cs, block_table, k_cache, v_cache, k_scale, v_scale, positions=None, token_seq=None, seq_lens=None, rot_dim=None,
+                    style="neox", q_out=None, k_out=None):
+    """rope_append with the append going to the fp8 cache (sm_rope_append_kv8_*): k_cache, v_cache are float8_e4m3fn or float8_e5m2
+    [num_pages][page_size][kv_heads][head_dim] (one dtype for both), k_scale, v_scale float32 [num_pages][kv_heads][page_size]; each
+    appended K head (rotated, rounded to q's dtype) and V head is one row of quantize_rows_fp8: its bytes go to the token's cache row, its
+    row_scale to [page][head][slot].  All four and block_table are required; everything else as rope_append.  Returns q_out."""
+    torch = _t()
+    what = "rope_append_kv8"
+    sfx = _quant_src_sfx(q, what)
+    if style not in _ROPE_STYLES:
+        raise SparsifymeError(f"{what}: style is 'neox' or 'interleaved'")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise SparsifymeError(f"{what}: q is [tokens][q_heads][head_dim], k and v are [tokens][kv_heads][head_dim]")
+    tokens, q_heads, head_dim = q.shape
+    kv_heads = k.shape[1]
+    if tuple(k.shape) != (tokens, kv_heads, head_dim) or tuple(v.shape) != tuple(k.shape) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise SparsifymeError(f"{what}: k and v are [tokens][kv_heads][head_dim] of q's dtype")
+    if q_out is None:
+        q_out = q
+    for name, t, heads in (("q", q, q_heads), ("k", k, kv_heads), ("v", v, kv_heads), ("q_out", q_out, q_heads), ("k_out", k_out, kv_heads)):
+        if t is not None:
+            _heads3(what, name, t, q.dtype, (tokens, heads, head_dim))
+    if cs is None:
+        if rot_dim not in (None, 0):
+            raise SparsifymeError(f"{what}: rot_dim > 0 needs the table cs")
+        rot_dim, max_pos, ldcs = 0, 0, 0
+    else:
+        if cs.dim() != 2 or cs.dtype != torch.float32 or (cs.shape[1] > 1 and cs.stride(1) != 1):
+            raise SparsifymeError(f"{what}: cs is float32 [max_pos][rot_dim] with contiguous rows (any row pitch)")
+        max_pos = cs.shape[0]
+        rot_dim = cs.shape[1] if rot_dim is None else rot_dim
+        if rot_dim > cs.shape[1]:
+            raise SparsifymeError(f"{what}: rot_dim exceeds the table's row")
+        ldcs = cs.stride(0) if max_pos > 1 else max(cs.stride(0), cs.shape[1])
+    row = lambda t, heads: _pitch(t, 0, heads * head_dim)
+    num_pages, page_size, max_pages, seqs, ldkv, page_stride, ldbt, sps, fmt = _paged_cache8(what, k_cache, v_cache, k_scale, v_scale, block_table, kv_heads, head_dim)
+    for name, t in (("positions", positions), ("token_seq", token_seq)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (tokens,) or not t.is_contiguous()):
+            raise SparsifymeError(f"{what}: {name} is a contiguous int32 [tokens]")
+    if seq_lens is not None and (seq_lens.dtype != torch.int32 or seq_lens.dim() != 1 or not seq_lens.is_contiguous() or seq_lens.shape[0] != seqs):
+        raise SparsifymeError(f"{what}: seq_lens is a contiguous int32 [seqs]")
+    ptr = lambda t: _dev(t) if t is not None else None
+    fn = getattr(lib(), "sm_rope_append_kv8_" + sfx)
+    _check(fn(_dev(q), _dev(k), _dev(v), _dev(q_out), ptr(k_out), _dev(k_cache), _dev(v_cache), _dev(k_scale), _dev(v_scale), ptr(cs) if rot_dim else None,
+              ptr(positions), ptr(token_seq), ptr(seq_lens), _dev(block_table), tokens, seqs, q_heads, kv_heads, head_dim, rot_dim, max_pos, num_pages, page_size,
+              max_pages, row(q, q_heads), row(k, kv_heads), row(v, kv_heads), row(q_out, q_heads), row(k_out, kv_heads) if k_out is not None else 0, ldkv,
+              page_stride, sps, ldcs, ldbt, _ROPE_STYLES[style], fmt, _stream()), "sm_rope_append_kv8")
+    return q_out
+
+
+def attn_decode_kv8(q, k_cache, v_cache, k_scale, v_scale, block_table, seq_lens, scale=None, out=None, lse=None, workspace=None):
+    """attn_decode over the fp8 cache (sm_attn_decode_kv8_*): k_cache, v_cache float8_e4m3fn or float8_e5m2 [num_pages][page_size][kv_heads]
+    [head_dim] (one dtype for both), k_scale, v_scale float32 [num_pages][kv_heads][page_size]; q, out, lse, scale and workspace as
+    attn_decode (attn_decode_form and attn_decode_workspace_size serve this call too).  Returns out."""
+    torch = _t()
+    what = "attn_decode_kv8"
+    sfx = _quant_src_sfx(q, what)
+    if q.dim() != 3 or seq_lens.dim() != 1:
+        raise SparsifymeError(f"{what}: q is [seqs][q_heads][head_dim], seq_lens [seqs]")
+    seqs, q_heads, head_dim = q.shape
+    kv_heads = k_cache.shape[2] if k_cache.dim() == 4 else 0
+    num_pages, page_size, max_pages, table_seqs, ldkv, page_stride, ldbt, sps, fmt = _paged_cache8(what, k_cache, v_cache, k_scale, v_scale, block_table, kv_heads,
+                                                                                                   head_dim)
+    if table_seqs != seqs or seq_lens.dtype != torch.int32 or seq_lens.shape[0] != seqs or not seq_lens.is_contiguous():
+        raise SparsifymeError(f"{what}: block_table is [seqs][max_pages], seq_lens a contiguous int32 [seqs]")
+    if out is None:
+        out = torch.empty((seqs, q_heads, head_dim), dtype=q.dtype, device=q.device)
+    for name, t in (("q", q), ("out", out)):
+        _heads3(what, name, t, q.dtype, (seqs, q_heads, head_dim))
+    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != (seqs, q_heads) or not lse.is_contiguous()):
+        raise SparsifymeError(f"{what}: lse is a contiguous float32 [seqs][q_heads]")
+    ldq, ldo = _pitch(q, 0, q_heads * head_dim), _pitch(out, 0, q_heads * head_dim)
+    need = attn_decode_workspace_size(seqs, q_heads, head_dim, page_size, max_pages)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ws_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    fn = getattr(lib(), "sm_attn_decode_kv8_" + sfx)
+    _check(fn(_dev(q), _dev(k_cache), _dev(v_cache), _dev(k_scale), _dev(v_scale), _dev(block_table), _dev(seq_lens), _dev(out),
+              _dev(lse) if lse is not None else None, _dev(workspace) if workspace is not None else None, ws_bytes, seqs, q_heads, kv_heads, head_dim,
+              num_pages, page_size, max_pages, ldq, ldkv, page_stride, sps, ldbt, ldo, float(head_dim ** -0.5 if scale is None else scale), fmt, _stream()),
+           "sm_attn_decode_kv8")
+    return out
 
 
 def quantize_compress24_fp8(A, blob, row_scale, rows, k, fmt_dtype, lda=None):

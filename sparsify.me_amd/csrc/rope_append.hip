@@ -16,6 +16,7 @@
 #include "mma_tile.h"
 #include "paged_kv.h"
 #include "quant_fp8.h"
+#include "rope_common.h"  // ra_style_ok, ra_rot
 
 namespace sm {
 
@@ -23,8 +24,6 @@ namespace sm {
 #ifndef ROPE_APPEND_BLOCK_MAX
 #define ROPE_APPEND_BLOCK_MAX SM_ROPE_APPEND_BLOCK_MAX_TOKENS
 #endif
-
-inline bool ra_style_ok(int s) { return s == SM_ROPE_NEOX || s == SM_ROPE_INTERLEAVED; }
 
 inline int rope_append_form(size_t tokens, size_t q_heads, size_t kv_heads, size_t head_dim, size_t rot_dim) {
   const size_t lim = 0x7fffffffull;
@@ -43,14 +42,6 @@ struct RaArgs {
   unsigned tokens, seqs, q_heads, kv_heads, hd, rot, half, pos_end, num_pages, page_size, page_shift, cap;  // the PagedKv fields (paged_kv.h): zeros without a cache
   unsigned items, rot_items, hps;  // items per head, how many of them rotate, heads per wave step (64 / items)
 };
-
-// (y_a, y_b) of the definition in fp32: two products, each rounded, then the subtraction / the addition -- never an fma
-__device__ __forceinline__ void ra_rot(float xa, float xb, float c, float s, float& ya, float& yb) {
-#pragma clang fp contract(off)
-  const float ac = xa * c, bs = xb * s, bc = xb * c, as = xa * s;
-  ya = ac - bs;
-  yb = bc + as;
-}
 
 template <bool BF, bool NEOX, bool BLOCK>
 __global__ __launch_bounds__(256) void rope_append_kernel(const RaArgs p) {
